@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- decoded codewords/s of the LDPC hot path on N MI355X GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--kernel auto|qc|table]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--kernel auto|qc|table] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is ONE pass of the decode hot path (bldpc_decode: 50 flooding min-sum iterations, early exit
@@ -12,11 +12,16 @@ block generated once on the host and tiled to the batch.  Frames
 with no data-path collective (weak scaling); RCCL carries only the final all-reduce of the five error
 counters.
 
-Prints ONE JSON line on rank 0.  `roofline` prices the dominant kernel against HBM (the bound
-SURVEY.md 8d prescribes): algorithmic bytes = (8N+4) per codeword * codewords per launch over the
-kernel's average duration measured with HIP events around the decode call alone.  `cpu_baseline` times
-the CPU oracle (a port of the reference kernels -- the binary reference has no CPU decode path) on a
-bounded sample of the same workload on this box's host cores.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and reports the
+headline (`value`, `ms_per_step`) with the error statistics the steps counted.  `--full` adds the
+secondary figures: `roofline` prices the dominant kernel against HBM (the bound SURVEY.md 8d
+prescribes): algorithmic bytes = (8N+4) per codeword * codewords per launch over the kernel's average
+duration measured with HIP events around the decode call alone.  `cpu_baseline` times the CPU oracle (a
+port of the reference kernels -- the binary reference has no CPU decode path) on a bounded sample of
+the same workload on this box's host cores.
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller as DIR/<name>.npy (see
+dump_outputs); the inputs are fixed by the arguments, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -31,6 +36,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+DUMP_BUDGET = 48 << 20  # bytes of per-frame outputs --dump-outputs writes (float32); larger outputs are sampled by frame
 
 WORKLOADS = {
     # name: (file, J, L, Z, frames per GPU, Es/N0 dB, iterations)
@@ -61,9 +67,32 @@ def parse():
     ap.add_argument("--frames", type=int, default=0, help="override frames per GPU")
     ap.add_argument("--snr", type=float, default=None, help="override the SNR point (experiments only)")
     ap.add_argument("--iters", type=int, default=0, help="override the iteration count (experiments only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary figures: roofline (per-kernel HIP events, committed profiles) and cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
     ap.add_argument("--cpu-frames", type=int, default=0, help="frames in the cpu_baseline sample (0 = auto)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+def dump_outputs(path, per_frame, other, frames):
+    """--dump-outputs: what the last timed step returned to its caller, one DIR/<name>.npy per array.  per_frame: {name: (device
+    tensor, frame axis)}, written as float32 (the integer outputs are exact in float32); when they hold more than DUMP_BUDGET bytes
+    the same fixed, seeded sample of frames is kept from each, in ascending order (frames.npy: the frame indices kept).
+    other: {name: numbers}, written as float64."""
+    os.makedirs(path, exist_ok=True)
+    per_frame_bytes = sum(4 * t.numel() // t.shape[ax] for t, ax in per_frame.values())
+    keep = min(frames, max(1, DUMP_BUDGET // max(per_frame_bytes, 1)))
+    idx = np.arange(frames) if keep == frames else np.sort(np.random.default_rng(173).choice(frames, keep, replace=False))
+    np.save(os.path.join(path, "frames.npy"), idx.astype(np.float64))
+    for name, (t, ax) in per_frame.items():
+        sel = torch.from_numpy(idx).to(t.device)
+        np.save(os.path.join(path, name + ".npy"), t.index_select(ax, sel).to(torch.float32).cpu().numpy())
+    for name, a in other.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, np.float64).reshape(-1))
 
 
 def cpu_baseline(name, J, L, Z, snr, iters, y_block, nframes):
@@ -238,13 +267,16 @@ def run_nb(args, rank, world, dev, dist):
     for _ in range(args.warmup):
         nb.Statistic(code, counters, decode(), cwd, stream=stream)
     counters.zero_()
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+    # --full: one HIP event pair per timed step around the decode call (roofline.kernel_ms)
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)] if args.full else None
     barrier()
     t0 = time.perf_counter()
     for k in range(args.steps):
-        ev[k][0].record(stream)
+        if ev:
+            ev[k][0].record(stream)
         r = decode()
-        ev[k][1].record(stream)
+        if ev:
+            ev[k][1].record(stream)
         nb.Statistic(code, counters, r, cwd, stream=stream)
     tot = counters.clone()
     if world > 1:
@@ -255,15 +287,14 @@ def run_nb(args, rank, world, dev, dist):
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
-    kern_ms = sum(a.elapsed_time(b) for a, b in ev) / args.steps
     if rank != 0:
         return
+    c = tot.cpu().tolist()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {k: (v, 0) for k, v in r.items() if v is not None}, {"counters": c}, frames)
     n_all = frames * world * args.steps
-    alg_bytes = (4 * code.N * (code.q - 1) + 4 * code.N) * frames  # L_ch in + symbols out
     kname = {0: "k_nb_ems2<64>" if q == 64 else "k_nb_ems_wide<%d>" % q, 1: "k_nb_tmm<64, false>", 3: "k_nb_tmm<64, true>"}[method]
     mname = {0: "GF(%d) EMS" % q, 1: "GF(64) trellis min-max", 3: "GF(64) layered trellis min-max"}[method]
-    achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
-    c = tot.cpu().tolist()
     out = {
         "metric": "decoded codewords/sec (%s, maxIT %d, per-frame syndrome exit as the reference)" % (mname, iters),
         "value": n_all / elapsed, "unit": "codewords/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -272,15 +303,19 @@ def run_nb(args, rank, world, dev, dist):
         "config": {"workload": "myNBLDPC %s %s batch=%d codewords/GPU Eb/N0=%.1fdB" % ("BDS N576_K288" if q == 64 else name.replace(".txt", ""),
                                                                                      ("GF(%d) EMS(Nm=2,Nc=2)" % q) if method == 0 else mname, frames, snr),
                    "kernel": "%s %s" % (kname, "two frames in flight per workgroup (walking waves + sorting waves)" if kname.startswith("k_nb_ems2") else "one frame per workgroup"), "frames_per_gpu": frames, "sharding": "frames, no data-path collective"},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                     "traffic": pmc_traffic(kname)[0], "traffic_source": pmc_traffic(kname)[1], "kernel": kname, "kernel_ms": kern_ms,
-                     # (a frame occupies one half of a workgroup's pipeline for mean_iterations + P(converged) half-steps)
-                     "onchip": pmc_onchip(kname, kern_ms, frames=frames, iters=c[2] / n_all + 1.0 - c[0] / n_all),
-                     "algorithmic_bytes_per_launch": alg_bytes},
         "stats": {"frames": n_all, "error_frames": c[0], "symbol_errors": c[1], "FER": c[0] / n_all, "SER": c[1] / n_all / code.N,
                   "mean_iterations": c[2] / n_all},
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        kern_ms = sum(a.elapsed_time(b) for a, b in ev) / args.steps
+        alg_bytes = (4 * code.N * (code.q - 1) + 4 * code.N) * frames  # L_ch in + symbols out
+        achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
+        out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                           "traffic": pmc_traffic(kname)[0], "traffic_source": pmc_traffic(kname)[1], "kernel": kname, "kernel_ms": kern_ms,
+                           # (a frame occupies one half of a workgroup's pipeline for mean_iterations + P(converged) half-steps)
+                           "onchip": pmc_onchip(kname, kern_ms, frames=frames, iters=c[2] / n_all + 1.0 - c[0] / n_all),
+                           "algorithmic_bytes_per_launch": alg_bytes}
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cb = nb_cpu_baseline(snr, args.cpu_frames, method, q, name)
         if cb:
             out["cpu_baseline"] = cb
@@ -349,19 +384,22 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    code.set_profiling(True)
+    code.set_profiling(args.full)  # --full: the library records an event pair around the dominant kernel of every call
     for _ in range(args.warmup):
         step()
     SIM._dev.zero_()
     torch.cuda.synchronize(dev)
-    code.kernel_ms_mean()  # drop the warm-up pairs
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+    if args.full and args.warmup:
+        code.kernel_ms_mean()  # drop the warm-up pairs
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)] if args.full else None
     barrier()
     t0 = time.perf_counter()
     for k in range(args.steps):
-        ev[k][0].record(stream)  # HIP events on the stream the kernel is launched on
-        C.Decode_Statistic(code, y, SIM._dev, max_iter=iters, exit_mode=C.EXIT_FIXED, kernel=kernel, D=D, stream=stream)
-        ev[k][1].record(stream)
+        if ev:
+            ev[k][0].record(stream)  # HIP events on the stream the kernel is launched on
+        r = C.Decode_Statistic(code, y, SIM._dev, max_iter=iters, exit_mode=C.EXIT_FIXED, kernel=kernel, D=D, stream=stream)
+        if ev:
+            ev[k][1].record(stream)
     counters = SIM._dev.clone()
     if world > 1:
         dist.all_reduce(counters)  # the only collective: 5 int64 error counters
@@ -371,24 +409,12 @@ def main():
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
-    call_ms = sum(a.elapsed_time(b) for a, b in ev) / args.steps  # whole bldpc_decode call (regroup + decode + unpack)
-    # dominant kernel alone: every timed step recorded its own event pair inside bldpc_decode (on the kernel's stream); the mean
-    # over ALL timed steps (the library keeps the last 64 pairs), queried after the timed region so that nothing synchronises in it
-    kern_ms, kern_n = code.kernel_ms_mean()
 
     if rank == 0:
         total_cw = frames * world * args.steps
-        alg_bytes = (8 * N + 4) * frames  # fp32 LLR in + int32 hard bits out + flag, per launch
-        model = "io: (8N+4) B per codeword"
-        if code.last_kernel.startswith("table"):
-            # the table kernels keep Memory_RQ in HBM: their algorithmic traffic is the reference schedule's
-            # streaming model, 8N + iters*(16E+8N) bytes per codeword (secondary figure; E = nnz*Z edges);
-            # the timed "kernel" is the whole VN/CN launch sequence of the call
-            E = code.nnz * code.Z
-            alg_bytes = (8 * N + (iters - 1) * (16 * E + 8 * N) + (8 * E + 8 * N)) * frames  # last iteration has no CN pass
-            model = "streaming: 8N + iters*(16E+8N) B per codeword (messages resident in HBM)"
-        achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
         c = counters.cpu().tolist()
+        if args.dump_outputs:  # D of the last step (row N: the per-frame flag), the counters accumulated over the timed steps
+            dump_outputs(args.dump_outputs, {"D": (D, 1)}, {"counters": c, "iteraTime": r["iteraTime"]}, frames)
         out = {
             "metric": "decoded codewords/sec (50-iter flooding min-sum, fixed iterations)",
             "value": total_cw / elapsed, "unit": "codewords/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -396,16 +422,31 @@ def main():
             "dtype": "f32", "data": "synthetic",
             "config": {"workload": "%s rate-%.3f batch=%d codewords/GPU %d iters Es/N0=%.1fdB" % (args.workload, code.K / N, frames, iters, snr),
                        "kernel": code.last_kernel, "frames_per_gpu": frames, "sharding": "frames, no data-path collective"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": pmc_traffic(code.last_kernel)[0], "traffic_source": pmc_traffic(code.last_kernel)[1],
-                         "kernel": code.last_kernel, "kernel_ms": kern_ms, "kernel_ms_launches_averaged": kern_n, "decode_call_ms": call_ms,
-                         "achieved_decode_call": alg_bytes / (call_ms * 1e-3) / 1e9,  # the whole bldpc_decode_statistic call: (regroup +) decode + unpack with the error counts + the counters
-                         "algorithmic_bytes_per_launch": alg_bytes, "model": model,
-                         "onchip": pmc_onchip(code.last_kernel, kern_ms, frames=frames, iters=iters)},
             "stats": {"frames": frames * world * args.steps, "error_frames": c[0], "error_bits": c[1],
                       "FER": c[0] / (frames * world * args.steps), "BER": c[1] / (frames * world * args.steps) / code.K},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            call_ms = sum(a.elapsed_time(b) for a, b in ev) / args.steps  # whole bldpc_decode call (regroup + decode + unpack)
+            # dominant kernel alone: every timed step recorded its own event pair inside bldpc_decode (on the kernel's stream); the mean
+            # over ALL timed steps (the library keeps the last 64 pairs), queried after the timed region so that nothing synchronises in it
+            kern_ms, kern_n = code.kernel_ms_mean()
+            alg_bytes = (8 * N + 4) * frames  # fp32 LLR in + int32 hard bits out + flag, per launch
+            model = "io: (8N+4) B per codeword"
+            if code.last_kernel.startswith("table"):
+                # the table kernels keep Memory_RQ in HBM: their algorithmic traffic is the reference schedule's
+                # streaming model, 8N + iters*(16E+8N) bytes per codeword (secondary figure; E = nnz*Z edges);
+                # the timed "kernel" is the whole VN/CN launch sequence of the call
+                E = code.nnz * code.Z
+                alg_bytes = (8 * N + (iters - 1) * (16 * E + 8 * N) + (8 * E + 8 * N)) * frames  # last iteration has no CN pass
+                model = "streaming: 8N + iters*(16E+8N) B per codeword (messages resident in HBM)"
+            achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                               "traffic": pmc_traffic(code.last_kernel)[0], "traffic_source": pmc_traffic(code.last_kernel)[1],
+                               "kernel": code.last_kernel, "kernel_ms": kern_ms, "kernel_ms_launches_averaged": kern_n, "decode_call_ms": call_ms,
+                               "achieved_decode_call": alg_bytes / (call_ms * 1e-3) / 1e9,  # the whole bldpc_decode_statistic call: (regroup +) decode + unpack with the error counts + the counters
+                               "algorithmic_bytes_per_launch": alg_bytes, "model": model,
+                               "onchip": pmc_onchip(code.last_kernel, kern_ms, frames=frames, iters=iters)}
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(name, J, L, Z, snr, iters, y_block, args.cpu_frames)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -8,7 +8,7 @@ set -e -o pipefail
 tag=$1; name=$2; match=$3; shift 3
 out=gpurun_out/${tag}_${name}
 export TMPDIR=/tmp
-python bench.py "$@" > ${out}_bench.json 2> ${out}_bench.err
+python bench.py --full "$@" > ${out}_bench.json 2> ${out}_bench.err
 rocprofv3 --kernel-trace --stats -d ${out}_trace -o run -- python bench.py "$@" --no-cpu-baseline --steps 20 --warmup 2 > ${out}_trace.log 2>&1
 rocprofv3 --pmc FETCH_SIZE -d ${out}_fetch -o run -- python bench.py "$@" --no-cpu-baseline --steps 2 --warmup 1 > ${out}_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE -d ${out}_write -o run -- python bench.py "$@" --no-cpu-baseline --steps 2 --warmup 1 > ${out}_write.log 2>&1

@@ -559,13 +559,13 @@ def test_rccl_world_size_one_smoke(C):
 
 
 def test_bench_contract_line(C):
-    """bench.py prints ONE JSON line with the driver's contract fields plus `roofline` and `cpu_baseline`."""
+    """bench.py --full prints ONE JSON line with the driver's contract fields plus `roofline` and `cpu_baseline`."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.check_output([sys.executable, os.path.join(root, "bench.py"), "--frames", "2048", "--steps", "2", "--warmup", "1",
-                                   "--cpu-frames", "32"], stderr=subprocess.DEVNULL).decode().strip().splitlines()
+                                   "--full", "--cpu-frames", "32"], stderr=subprocess.DEVNULL).decode().strip().splitlines()
     lines = [ln for ln in out if ln.startswith("{")]
     assert len(lines) == 1
     j = json.loads(lines[0])
@@ -578,6 +578,40 @@ def test_bench_contract_line(C):
     assert r["bound"] in ("hbm", "mfma") and r["unit"] == "GB/s" and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9 and "traffic" in r
     cb = j["cpu_baseline"]
     assert cb["kind"] in ("reference", "port") and cb["cores"] >= 1 and cb["value"] > 0 and cb["sample"]
+
+
+def test_bench_plain_run_dumps_outputs(C, tmp_path):
+    """A plain bench.py run reports the headline without the --full figures, runs exactly --steps timed steps, and
+    --dump-outputs writes what its last step returned: D equals a decode of the same input made here, and the counters are the
+    sum of --steps identical steps."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    F, steps = 2048, 3
+    out = subprocess.check_output([sys.executable, os.path.join(root, "bench.py"), "--frames", str(F), "--steps", str(steps), "--warmup", "1",
+                                   "--dump-outputs", str(tmp_path)], stderr=subprocess.DEVNULL).decode().strip().splitlines()
+    lines = [ln for ln in out if ln.startswith("{")]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in j, k
+    assert "roofline" not in j and "cpu_baseline" not in j
+    assert j["steps"] == steps and j["stats"]["frames"] == F * steps and j["ms_per_step"] > 0
+    assert abs(j["value"] - F * 1e3 / j["ms_per_step"]) <= 1e-6 * j["value"]
+    D = np.load(str(tmp_path / "D.npy"))
+    counters = np.load(str(tmp_path / "counters.npy"))
+    assert D.dtype == np.float32 and counters.dtype == np.float64
+    assert np.array_equal(np.load(str(tmp_path / "frames.npy")), np.arange(F, dtype=np.float64))
+    code = C.BinaryCode.from_blockh(_path(4, 24, 96), 4, 24, 96)
+    seed = np.array([173, 173, 173], np.int32)
+    y = torch.from_numpy(C.AWGNChannel_CPU(seed, C.sigma_of(3.0), code.N, F)).cuda()
+    cnt = torch.zeros(5, dtype=torch.int64, device=y.device)
+    r = C.Decode_Statistic(code, y, cnt, max_iter=50, exit_mode=C.EXIT_FIXED)
+    torch.cuda.synchronize()
+    assert D.shape == (code.N + 1, F) and np.array_equal(D, r["D"].cpu().numpy().astype(np.float32))
+    assert np.array_equal(counters, steps * cnt.cpu().numpy().astype(np.float64))
+    assert counters[0] == j["stats"]["error_frames"] and counters[1] == j["stats"]["error_bits"]
 
 
 @pytest.mark.parametrize("Z,J,L", [(64, 5, 12), (96, 3, 9), (128, 6, 20), (192, 4, 16), (320, 5, 11), (384, 3, 24), (640, 4, 10), (1024, 3, 8)])
