@@ -39,82 +39,39 @@ template <typename GM, bool HIST> __global__ __launch_bounds__(GM::TPB, GM::MINW
     const int rbase = ((jq * WC + h * WCH) * Z + t) * MSG;   // + (rr*GJ*WC + i)*Z*MSG
     const int sbase = (GM::Sslot + cg * Z + t) * MSG;        // + cc*NCG*Z*MSG
     int saddr[RPT][WCH]; // byte addresses of the S values of this thread's edges
-    v2f32 Rr[RPT][WCH];  // this thread's previous outputs R_p (Memory_RQ = 0 at the start, LDPC_Decoder.cu:82)
-    int e0v[RPT], wrv[RPT];
-#pragma unroll
-    for (int rr = 0; rr < RPT; rr++) {
-        e0v[rr] = a.rowptr[jq + rr * GJ];
-        wrv[rr] = a.rowptr[jq + rr * GJ + 1] - e0v[rr];
-    }
-    int wcv[CPT];
-#pragma unroll
-    for (int cc = 0; cc < CPT; cc++) wcv[cc] = LOC ? 0 : a.wv[cg + cc * NCG];
+    v2f32 Rr[RPT][WCH];  // this thread's previous outputs R_p (+0 at the start, Memory_RQ = 0, LDPC_Decoder.cu:82: see vn_first)
     int sst[LOC ? CPT : 1];   // LOC: byte address of S of this thread's variable of column cc, (t + shift of the local block) mod Z
-    int cl[LOC ? CPT : 1];    // LOC, prologue only: that circulant position
+    int raddr[CPT][WV];       // byte addresses of the R values the variable-node phase reads (LOC: the WV-1 other block rows)
+    {   // every address from the host's table (QcPlan::d_lane): one coalesced load, nothing gathered here
+        constexpr int NV = LOC ? CPT : 0, WVR = LOC ? WV - 1 : WV;
+        int w[4 * GM::LW];
 #pragma unroll
-    for (int rr = 0; rr < RPT; rr++) {
-        QcCnEdge ed[WCH];
-#pragma unroll
-        for (int i = 0; i < WCH; i++) ed[i] = a.cn_edges[e0v[rr] + min(h * WCH + i, wrv[rr] - 1)];
-#pragma unroll
-        for (int i = 0; i < WCH; i++) {
-            int c = t + ed[i].shift;
-            c = (c >= Z) ? c - Z : c;
-            const int slot = (h * WCH + i < wrv[rr]) ? GM::Sslot + ed[i].col * Z + c : GM::inf_slot;
-            saddr[rr][i] = slot * MSG;
-            if constexpr (LOC) {
-                if (i < NL) { // the block of local edge i: this thread is also the variable (col, c) -- column cc = i of its column group
-                    sst[i] = slot * MSG;
-                    cl[i] = c;
-                }
-            }
-#if !QC2_PERSIST
-            Rr[rr][i] = v2f32{0.0f, 0.0f};
-            lds_st2(rbase + (rr * GJ * WC + i) * Z * MSG, Rr[rr][i]);
-#endif
+        for (int k = 0; k < GM::LW; k++) {
+            const v4i32 x = a.lane[k * GM::TPB + tid];
+            w[4 * k] = x.x; w[4 * k + 1] = x.y; w[4 * k + 2] = x.z; w[4 * k + 3] = x.w;
         }
+#pragma unroll
+        for (int cc = 0; cc < NV; cc++) sst[LOC ? cc : 0] = (GM::Sslot + w[cc]) * MSG;
+#pragma unroll
+        for (int rr = 0; rr < RPT; rr++)
+#pragma unroll
+            for (int i = 0; i < WCH; i++) saddr[rr][i] = w[NV + rr * WCH + i];
+#pragma unroll
+        for (int cc = 0; cc < CPT; cc++)
+#pragma unroll
+            for (int k = 0; k < WVR; k++) raddr[cc][k] = w[NV + RPT * WCH + cc * WVR + k];
     }
     v2f32 yreg[CPT];
-    int raddr[CPT][WV];
     // channel values of this thread's variable of column cc (LOC: variable index = its S slot)
     auto y_load = [&](int cc) -> v2f32 {
         const int n = LOC ? sst[LOC ? cc : 0] / MSG - GM::Sslot : (cg + cc * NCG) * Z + t;
         return a.y_raw ? *reinterpret_cast<const v2f32 *>(a.y_raw + (size_t)n * F + f0)
                        : *reinterpret_cast<const v2f32 *>(a.y + ((size_t)wg * (L * Z) + n) * NF);
     };
-#pragma unroll
-    for (int cc = 0; cc < CPT; cc++) {
-        const int l = cg + cc * NCG; // LOC: a virtual column (the host lists the columns of every half-row's local blocks)
-        if constexpr (LOC) {
-            // vn_edges[l][k] = the column's block in block row k (e = 0xffff: none); the own row jq is the local edge: slots kk = 0 .. WV-2
-            // are the other rows in ascending order
-            QcVnEdge ed[WV - 1];
-#pragma unroll
-            for (int kk = 0; kk < WV - 1; kk++) ed[kk] = a.vn_edges[l * WV + kk + (kk >= jq ? 1 : 0)];
 #if !QC2_PERSIST
-            yreg[cc] = y_load(cc);
+#pragma unroll
+    for (int cc = 0; cc < CPT; cc++) yreg[cc] = y_load(cc);
 #endif
-#pragma unroll
-            for (int kk = 0; kk < WV - 1; kk++) {
-                int r = cl[cc] - ed[kk].shift;
-                r = (r < 0) ? r + Z : r;
-                raddr[cc][kk] = ((ed[kk].e != 0xffffu) ? ed[kk].e * Z + r : GM::zero_slot) * MSG;
-            }
-        } else {
-        QcVnEdge ed[WV];
-#pragma unroll
-        for (int k = 0; k < WV; k++) ed[k] = a.vn_edges[l * WV + min(k, wcv[cc] - 1)];
-#if !QC2_PERSIST
-        yreg[cc] = y_load(cc);
-#endif
-#pragma unroll
-        for (int k = 0; k < WV; k++) {
-            int r = t - ed[k].shift;
-            r = (r < 0) ? r + Z : r;
-            raddr[cc][k] = ((k < wcv[cc]) ? ed[k].e * Z + r : GM::zero_slot) * MSG;
-        }
-        }
-    }
     if (tid < NF) {
         reinterpret_cast<float *>(lds)[GM::zero_slot * NF + tid] = 0.0f;
         reinterpret_cast<float *>(lds)[GM::inf_slot * NF + tid] = __builtin_inff();
@@ -197,6 +154,29 @@ template <typename GM, bool HIST> __global__ __launch_bounds__(GM::TPB, GM::MINW
         });
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     };
+    // The first variable-node phase: every R is +0 (Memory_RQ = 0, LDPC_Decoder.cu:82), so the reference's sum ((0+R_0)+...+R_{w-1})+y
+    // is (+0) + y = y + 0.0f bit for bit (y = -0.0f included): no R is read, none had to be zeroed in LDS.
+    auto vn_first = [&](bool (&bad)[NF]) {
+        static_for<CPT>([&](auto CC) {
+            constexpr int cc = decltype(CC)::value;
+            const v2f32 S = yreg[cc] + v2f32{0.0f, 0.0f};
+            int n;
+            if constexpr (LOC) {
+                Sloc[LOC ? cc : 0] = S;
+                lds_st2_imm<0>(sst[LOC ? cc : 0], S);
+                n = sst[LOC ? cc : 0] / MSG - GM::Sslot;
+            } else {
+                lds_st2_imm<cc * NCG * Z * MSG>(sbase, S);
+                n = (cg + cc * NCG) * Z + t;
+            }
+            if (HIST) {
+                const bool in_len = n < a.length;
+                bad[0] = bad[0] || (in_len && S.x < 0);
+                bad[1] = bad[1] || (in_len && S.y < 0);
+            }
+        });
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    };
     auto vn_any = [&](bool (&bad)[NF]) {
         if constexpr (LOC) static_for<GM::J>([&](auto JJ) { if (jqs == decltype(JJ)::value) vn_phase_loc(JJ, bad); });
         else vn_phase(bad);
@@ -261,18 +241,9 @@ template <typename GM, bool HIST> __global__ __launch_bounds__(GM::TPB, GM::MINW
     }
     __syncthreads(); // everybody has the pair before the flag words are reset
     f0 = wg * NF;
-    // this pair's state: every R = +0 (Memory_RQ = 0, LDPC_Decoder.cu:82), its channel values, no flags
+    // this pair's state: its channel values, no flags (every R = +0: the first iteration reads none, see vn_first)
 #pragma unroll
-    for (int rr = 0; rr < RPT; rr++)
-#pragma unroll
-        for (int i = 0; i < WCH; i++) {
-            Rr[rr][i] = v2f32{0.0f, 0.0f};
-            lds_st2(rbase + (rr * GJ * WC + i) * Z * MSG, Rr[rr][i]);
-        }
-#pragma unroll
-    for (int cc = 0; cc < CPT; cc++) {
-        yreg[cc] = y_load(cc);
-    }
+    for (int cc = 0; cc < CPT; cc++) yreg[cc] = y_load(cc);
     if (tid < NF) {
         lds_flag[tid] = 0;
         lds_flag[NF + tid] = 0;
@@ -281,15 +252,17 @@ template <typename GM, bool HIST> __global__ __launch_bounds__(GM::TPB, GM::MINW
     done = 0;
     __syncthreads();
 #endif
-    // The iteration loop; LOC: one instantiation per block row JJ of the wave, chosen ONCE outside the loop (chosen per iteration
-    // the J sums left S in different registers and the back edge carried three v_mov_b64 per wave and iteration, see k_qc)
-    auto iterate = [&](auto JJ) {
-    for (int it = 1; it < a.max_iter; it++) {
+    // Iteration it (1 ... max_iter-1): variable-node phase, barrier, check-node phase, barrier.  FIRST (it = 1): every R is +0, the
+    // variable-node phase is vn_first and the check-node phase's Q = S - R is Q = S (S - (+0) == S for every S, -0.0f included).
+    // True when the per-frame exit has retired every frame of the pair.
+    auto iteration = [&](auto JJ, auto FIRST, int it) -> bool {
+        constexpr bool first = decltype(FIRST)::value;
         bool bad[NF];
 #pragma unroll
         for (int v = 0; v < NF; v++) bad[v] = false;
         __builtin_amdgcn_s_setprio(QC_PRIO_VN);
-        if constexpr (LOC) vn_phase_loc(JJ, bad);
+        if constexpr (first) vn_first(bad);
+        else if constexpr (LOC) vn_phase_loc(JJ, bad);
         else vn_phase(bad);
         if (HIST) flags_publish(bad, it);
         __syncthreads();
@@ -299,7 +272,7 @@ template <typename GM, bool HIST> __global__ __launch_bounds__(GM::TPB, GM::MINW
 #endif
         if (HIST) {
             (void)flags_collect(it);
-            if (a.per_frame && retire(it)) return;
+            if (a.per_frame && retire(it)) return true;
         }
 
         // CN phase (LDPC_Decoder.cu:279-314)
@@ -323,7 +296,7 @@ template <typename GM, bool HIST> __global__ __launch_bounds__(GM::TPB, GM::MINW
                         else Sv[i] = lds_ld2(saddr[rr][c0 + i]);
                     }
 #pragma unroll
-                    for (int i = 0; i < CHK && c0 + i < WCH; i++) Rr[rr][c0 + i] = Sv[i] - Rr[rr][c0 + i]; // Q = S - R  (LDPC_Decoder.cu:206-209), in place of R_p
+                    for (int i = 0; i < CHK && c0 + i < WCH; i++) Rr[rr][c0 + i] = first ? Sv[i] : Sv[i] - Rr[rr][c0 + i]; // Q = S - R  (LDPC_Decoder.cu:206-209), in place of R_p
                     if (c0 + CHK < WCH) __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -368,17 +341,28 @@ template <typename GM, bool HIST> __global__ __launch_bounds__(GM::TPB, GM::MINW
 #ifdef QC_STAMPS
         stamp(__builtin_amdgcn_s_memtime());
 #endif
-    }
+        return false;
     };
-    if constexpr (LOC) static_for<GM::J>([&](auto JJ) { if (jqs == decltype(JJ)::value) iterate(JJ); });
-    else iterate(std::integral_constant<int, 0>{});
+    // The first iteration on its own straight-line path, then the loop; LOC: one instantiation of the loop per block row JJ of the wave,
+    // chosen ONCE outside it (chosen per iteration the J sums left S in different registers and the back edge carried three v_mov_b64
+    // per wave and iteration, see k_qc)
+    const bool retired = a.max_iter > 1 && iteration(std::integral_constant<int, 0>{}, std::true_type{}, 1);
+    auto iterate = [&](auto JJ) {
+        for (int it = 2; it < a.max_iter; it++)
+            if (iteration(JJ, std::false_type{}, it)) return;
+    };
+    if (!retired) {
+        if constexpr (LOC) static_for<GM::J>([&](auto JJ) { if (jqs == decltype(JJ)::value) iterate(JJ); });
+        else iterate(std::integral_constant<int, 0>{});
+    }
 
     int flag = 0;
     if (!(HIST && done == ALL)) { // final iteration: VN only, then outputs
         bool bad[NF];
 #pragma unroll
         for (int v = 0; v < NF; v++) bad[v] = false;
-        vn_any(bad);
+        if (a.max_iter > 1) vn_any(bad);
+        else vn_first(bad);
         if (LOC) __syncthreads(); // emit reads S in the natural layout: other threads' stores
         emit(~done, bad);
         flags_publish(bad, a.max_iter);

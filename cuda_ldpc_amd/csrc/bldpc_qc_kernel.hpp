@@ -63,6 +63,7 @@
 
 namespace cldpc {
 
+typedef int v4i32 __attribute__((ext_vector_type(4)));
 
 struct QcArgs {
     const float *y;             // [ceil(F/NF)][N][NF]  channel values regrouped per workgroup (k_regroup_y)
@@ -76,6 +77,7 @@ struct QcArgs {
     const unsigned short *rowptr; // [J+1]
     const QcVnEdge *vn_edges;   // [L][WV]
     const unsigned char *wv;    // [L]
+    const v4i32 *lane;          // half-row kernel: per-thread LDS addresses, [LW][TPB] (see qc2_lane_words)
     int F, nWG, max_iter, length;
     // compressed-state kernel (k_qcc) only:
     const unsigned *cn_meta;    // [J][WCS] padded row slots
@@ -237,6 +239,13 @@ constexpr int qc_ipow(int b, int e) { return e == 0 ? 1 : b * qc_ipow(b, e - 1);
 // per iteration at J4_L24_Z96.  The variable-node sum keeps the reference's order (ascending block row): with WV == J a column's
 // slot k is block row k (absent rows read the +0.0f slot: adding +0.0f to a sum that is never -0.0f is exact), the local edge of a
 // thread of block row j is slot j, and j is wave-uniform: a scalar switch picks one of J bodies.
+// The half-row kernel's per-thread table (QcPlan::d_lane, built by the host from the block lists): LOC: the variable index of each of
+// the thread's CPT local columns, then the S byte addresses of its RPT x WCH edges, then the R byte addresses its variable-node phase
+// reads (CPT x (WV-1) with local edges, CPT x WV without), padded to whole int4: one coalesced dwordx4 load per 4 words.
+constexpr int qc2_lane_words(int J, int L, int WC, int WV, int GJ, bool loc)
+{
+    return ((loc ? L / (2 * GJ) : 0) + (J / GJ) * (WC / 2) + (L / (2 * GJ)) * (loc ? WV - 1 : WV) + 3) / 4;
+}
 template <int NF_, int J_, int L_, int Z_, int WC_, int WV_, int GJ_, int MINW_, bool LOC_ = false> struct QcGeom2 {
     static constexpr int NF = NF_, J = J_, L = L_, Z = Z_, WC = WC_, WV = WV_, GJ = GJ_, MINW = MINW_;
     static constexpr bool LOC = LOC_;
@@ -249,6 +258,7 @@ template <int NF_, int J_, int L_, int Z_, int WC_, int WV_, int GJ_, int MINW_,
     static constexpr int flag_byte = (inf_slot + 1) * MSG;
     static constexpr int lds_bytes = flag_byte + NF * 8;
     static constexpr int NW = (L * Z) / 32;
+    static constexpr int LW = qc2_lane_words(J, L, WC, WV, GJ, LOC); // int4 words per thread of QcArgs::lane
     static_assert(Z % 32 == 0 && WC % 2 == 0, "half-waves own 32 circulant positions and half a row each");
     static_assert(J % GJ == 0 && L % NCG == 0, "groups must tile the block rows and columns");
     static_assert(TPB <= 1024 && inf_slot < 65536, "geometry out of range");
@@ -690,6 +700,7 @@ struct QcPlan {
     QcVnEdge *d_vn = nullptr;
     unsigned char *d_wv = nullptr;
     unsigned *d_cn_meta = nullptr, *d_vn_meta = nullptr; // compressed-state kernel
+    v4i32 *d_lane = nullptr; // half-row kernel: per-thread LDS addresses (qc2_lane_table)
     int WVS = 0, lds_bytes = 0, lc = 0;
     char name[96] = "qc_lds(unavailable)";
     mutable int ran_to_max = 0; // BATCH_GLOBAL: the previous batch did not stop before max_iter (a performance hint, never a result)
@@ -722,7 +733,8 @@ inline void qc_plan_release(QcPlan *q)
     if (q->d_wv) (void)hipFree(q->d_wv);
     if (q->d_cn_meta) (void)hipFree(q->d_cn_meta);
     if (q->d_vn_meta) (void)hipFree(q->d_vn_meta);
-    q->d_cn_meta = nullptr; q->d_vn_meta = nullptr;
+    if (q->d_lane) (void)hipFree(q->d_lane);
+    q->d_cn_meta = nullptr; q->d_vn_meta = nullptr; q->d_lane = nullptr;
     q->d_cn = nullptr; q->d_rowptr = nullptr; q->d_vn = nullptr; q->d_wv = nullptr;
     q->frames_per_wg = 0;
     if (q->pf) {
@@ -730,6 +742,62 @@ inline void qc_plan_release(QcPlan *q)
         delete q->pf;
         q->pf = nullptr;
     }
+}
+
+// The half-row kernel's per-thread table (see qc2_lane_words) from the block lists as uploaded: what every thread's prologue used to
+// gather from cn_edges / vn_edges itself, two dependent global look-ups in front of its channel loads.  Laid out [word][thread] so that
+// a wave's load of one int4 word is 1 KB contiguous.  False if an address falls outside the kernel's LDS or input (cannot happen).
+inline bool qc2_lane_table(const QcVariant &v, const std::vector<unsigned short> &rowptr, const std::vector<QcCnEdge> &cn,
+                           const std::vector<QcVnEdge> &vn, const std::vector<unsigned char> &wvb, std::vector<int> &tab)
+{
+    const bool loc = v.loc == 1;
+    const int Z = v.Z, WC = v.WC, WV = v.WV, GJ = v.G, L = v.L, TPB = v.threads, MSG = v.NF * 4;
+    const int ZB = Z / 32, WCH = WC / 2, NCG = 2 * GJ, RPT = v.J / GJ, CPT = L / NCG, NV = loc ? CPT : 0, WVR = loc ? WV - 1 : WV;
+    const int Sslot = v.J * WC * Z, zero_slot = Sslot + L * Z, inf_slot = zero_slot + 1;
+    const int LW = qc2_lane_words(v.J, L, WC, WV, GJ, loc);
+    tab.assign((size_t)LW * 4 * TPB, 0);
+    bool ok = true;
+    for (int tid = 0; tid < TPB; tid++) {
+        const int wave = tid >> 6, lane = tid & 63, h = lane >> 5;
+        const int jq = wave / ZB, t = (wave - jq * ZB) * 32 + (lane & 31), cg = jq * 2 + h;
+        std::vector<int> w(LW * 4, 0), cl(CPT, 0);
+        for (int rr = 0; rr < RPT; rr++) {
+            const int e0 = rowptr[jq + rr * GJ], wr = rowptr[jq + rr * GJ + 1] - e0;
+            for (int i = 0; i < WCH; i++) {
+                int slot = inf_slot;
+                if (h * WCH + i < wr) {
+                    const QcCnEdge ed = cn[e0 + h * WCH + i];
+                    const int c = (t + ed.shift) % Z;
+                    slot = Sslot + ed.col * Z + c;
+                    if (loc && i < CPT) { // local edge i: this thread is also the variable (col, c), column i of its column group
+                        w[i] = ed.col * Z + c;
+                        cl[i] = c;
+                    }
+                }
+                w[NV + rr * WCH + i] = slot * MSG;
+            }
+        }
+        for (int cc = 0; cc < CPT; cc++) {
+            const int l = cg + cc * NCG;
+            for (int k = 0; k < WVR; k++) {
+                int slot = zero_slot;
+                if (loc) { // the column's blocks in the other block rows (the own row jq is the local edge), ascending
+                    const QcVnEdge ed = vn[(size_t)l * WV + k + (k >= jq ? 1 : 0)];
+                    if (ed.e != 0xffffu) slot = ed.e * Z + (cl[cc] - ed.shift + Z) % Z;
+                } else if (k < wvb[l]) {
+                    const QcVnEdge ed = vn[(size_t)l * WV + k];
+                    slot = ed.e * Z + (t - ed.shift + Z) % Z;
+                }
+                w[NV + RPT * WCH + cc * WVR + k] = slot * MSG;
+            }
+        }
+        for (int k = 0; k < LW * 4; k++) {
+            const bool var = k < NV, addr = k >= NV && k < NV + RPT * WCH + CPT * WVR;
+            ok = ok && (!var || (w[k] >= 0 && w[k] < L * Z)) && (!addr || (w[k] >= 0 && w[k] < v.lds_bytes - MSG + 1));
+            tab[((size_t)(k / 4) * TPB + tid) * 4 + k % 4] = w[k];
+        }
+    }
+    return ok;
 }
 
 // Pick the first variant whose geometry matches the code, upload its block lists.  Leaves
@@ -979,6 +1047,12 @@ inline int qc_plan_build(QcPlan *q, int J, int L, int Z, const int *H, bool plai
     }
     std::vector<unsigned char> wvb(L);
     for (int l = 0; l < L; l++) wvb[l] = (unsigned char)(v.loc == 2 ? kloc[l] : wv[l]); // row kernel with local edges: per VIRTUAL column, the place of its local block
+    if (!generic && std::string(v.tag).compare(0, 7, "halfrow") == 0) {
+        std::vector<int> tab;
+        if (!qc2_lane_table(v, rowptr, cn, vn, wvb, tab)) { q->variant = -1; return BLDPC_OK; }
+        CLDPC_HIP(hipMalloc((void **)&q->d_lane, tab.size() * sizeof(int)), BLDPC_ENOMEM);
+        CLDPC_HIP(hipMemcpy(q->d_lane, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice), BLDPC_EHIP);
+    }
     CLDPC_HIP(hipMalloc((void **)&q->d_cn, cn.size() * sizeof(QcCnEdge)), BLDPC_ENOMEM);
     CLDPC_HIP(hipMalloc((void **)&q->d_rowptr, rowptr.size() * sizeof(unsigned short)), BLDPC_ENOMEM);
     CLDPC_HIP(hipMalloc((void **)&q->d_vn, vn.size() * sizeof(QcVnEdge)), BLDPC_ENOMEM);
@@ -1042,7 +1116,7 @@ inline int qc_launch(const QcPlan *q, const float *y, int F, int max_iter, int l
     QcArgs a;
     a.y = y; a.y_raw = y_in_place ? y : nullptr; a.D = D; a.bits = bits; a.app = app; a.hist = hist;
     a.per_frame = (iters && hist) ? 1 : 0; a.iters = iters; // per-frame exit lives in the flag-tracking instantiation
-    a.cn_edges = q->d_cn; a.rowptr = q->d_rowptr; a.vn_edges = q->d_vn; a.wv = q->d_wv;
+    a.cn_edges = q->d_cn; a.rowptr = q->d_rowptr; a.vn_edges = q->d_vn; a.wv = q->d_wv; a.lane = q->d_lane;
     a.F = F;
     a.nWG = (F + q->frames_per_wg - 1) / q->frames_per_wg;
     a.max_iter = max_iter; a.length = length;
