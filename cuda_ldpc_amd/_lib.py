@@ -43,6 +43,11 @@ lib.bldpc_last_kernel_ms.argtypes = [c_void_p, ctypes.POINTER(ctypes.c_float)]
 lib.bldpc_kernel_ms_mean.argtypes = [c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(c_int)]
 lib.bldpc_awgn_channel_host.argtypes = [c_void_p, ctypes.c_float, c_void_p, c_void_p, c_int, c_int]
 lib.bldpc_awgn_channel_device.argtypes = [c_void_p, ctypes.c_float, c_void_p, c_void_p, c_int, c_int, c_void_p]
+lib.bldpc_generator_host.argtypes = [c_int, c_int, c_int, c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p, c_void_p]
+lib.bldpc_encoder_info.argtypes = [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p]
+lib.bldpc_encode.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p]
+lib.bldpc_encode_random.argtypes = [c_void_p, ctypes.c_ulonglong, ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p]
+lib.bldpc_syndrome.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]
 lib.bldpc_sigma.restype = ctypes.c_float
 lib.bldpc_sigma.argtypes = [ctypes.c_float, c_int, ctypes.c_float]
 

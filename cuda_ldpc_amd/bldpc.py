@@ -126,6 +126,29 @@ class BinaryCode:
               "bldpc_code_create_table")
         return cls(h, J, L, Z)
 
+    def _encoder_info(self):
+        if getattr(self, "_info_pos", None) is None:
+            k, r = ctypes.c_int(0), ctypes.c_int(0)
+            check(lib.bldpc_encoder_info(self._h, ctypes.byref(k), ctypes.byref(r), None), "bldpc_encoder_info")
+            pos = np.zeros(k.value, np.int32)
+            check(lib.bldpc_encoder_info(self._h, ctypes.byref(k), ctypes.byref(r), _np_ptr(pos)), "bldpc_encoder_info")
+            self._K_info, self._rank, self._info_pos = k.value, r.value, pos
+        return self._K_info, self._rank, self._info_pos
+
+    @property
+    def K_info(self):
+        """K' = N - rank(H): information bits per codeword of the systematic encoder (builds the generator on first use)."""
+        return self._encoder_info()[0]
+
+    @property
+    def rank(self):
+        return self._encoder_info()[1]
+
+    @property
+    def info_positions(self):
+        """int32 [K'] (host, ascending): codeword position of each information bit."""
+        return self._encoder_info()[2]
+
     @property
     def last_kernel(self):
         return lib.bldpc_last_kernel(self._h).decode()
@@ -156,6 +179,102 @@ class BinaryCode:
             self.close()
         except Exception:
             pass
+
+
+def generator_host(H, J, L, Z):
+    """bldpc_generator_host: the systematic generator of the QC code with block shifts H, on the host (no device).
+    Returns dict(K_info, rank, info_pos=int32 [K'], P=uint64 [rank, ceil(K'/64)]): parity bit r (r-th non-information
+    position, ascending) = XOR of the information bits j with bit j%64 of P[r, j//64] set."""
+    H = np.ascontiguousarray(H, np.int32)
+    if H.size != J * L:
+        raise ValueError("H must hold J*L shifts")
+    k, r = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib.bldpc_generator_host(J, L, Z, _np_ptr(H), ctypes.byref(k), ctypes.byref(r), None, None), "bldpc_generator_host")
+    pos = np.zeros(k.value, np.int32)
+    P = np.zeros((r.value, (k.value + 63) // 64), np.uint64)
+    check(lib.bldpc_generator_host(J, L, Z, _np_ptr(H), ctypes.byref(k), ctypes.byref(r), _np_ptr(pos), _np_ptr(P)), "bldpc_generator_host")
+    return dict(K_info=k.value, rank=r.value, info_pos=pos, P=P)
+
+
+def _check_cw(CodeWord, N, F, dev):
+    if not (torch.is_tensor(CodeWord) and CodeWord.is_cuda and CodeWord.device == dev and CodeWord.dtype == torch.int32
+            and CodeWord.is_contiguous() and tuple(CodeWord.shape) == (N, F)):
+        raise ValueError("CodeWord must be a contiguous CUDA int32 tensor [N=%d, F=%d] on %s" % (N, F, dev))
+
+
+def Encode(code, msg, CodeWord=None, stream=None):
+    """bldpc_encode: msg = CUDA int32 tensor [K', F] (frame-fastest, bit 0 read) -> CodeWord int32 [N, F] on the device,
+    systematic on code.info_positions."""
+    K = code.K_info
+    if not (torch.is_tensor(msg) and msg.is_cuda and msg.dtype == torch.int32 and msg.is_contiguous() and msg.dim() == 2
+            and msg.shape[0] == K and msg.shape[1] > 0):
+        raise ValueError("msg must be a contiguous CUDA int32 tensor [K'=%d, F]" % K)
+    F, dev = int(msg.shape[1]), msg.device
+    if CodeWord is None:
+        CodeWord = torch.empty((code.N, F), dtype=torch.int32, device=dev)
+    else:
+        _check_cw(CodeWord, code.N, F, dev)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(dev)).cuda_stream)
+    check(lib.bldpc_encode(code._h, _dev_ptr(msg), F, _dev_ptr(CodeWord), st), "Encode")
+    return CodeWord
+
+
+def PN_CodeWords(code, seed, F, first_frame=0, want_msg=False, device=None, CodeWord=None, stream=None):
+    """bldpc_encode_random: the codewords of frames first_frame .. first_frame+F-1 of the message stream `seed`
+    (counter-based rule of bldpc.h, mirrored by pn_messages below).  Returns CodeWord int32 [N, F] on the device, or
+    (CodeWord, msg [K', F]) with want_msg."""
+    if F <= 0 or first_frame < 0:
+        raise ValueError("F must be positive and first_frame >= 0")
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    if CodeWord is None:
+        CodeWord = torch.empty((code.N, F), dtype=torch.int32, device=device)
+    else:
+        _check_cw(CodeWord, code.N, F, device)
+    msg = torch.empty((code.K_info, F), dtype=torch.int32, device=device) if want_msg else None
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(device)).cuda_stream)
+    check(lib.bldpc_encode_random(code._h, ctypes.c_ulonglong(int(seed) % (1 << 64)), int(first_frame), F, _dev_ptr(msg), _dev_ptr(CodeWord), st),
+          "PN_CodeWords")
+    return (CodeWord, msg) if want_msg else CodeWord
+
+
+_M64 = (1 << 64) - 1
+
+
+def splitmix64(x):
+    """The first output of SplitMix64 seeded with x (uint64 numpy array or int), as bldpc.h defines it."""
+    with np.errstate(over="ignore"):
+        z = np.asarray(x, np.uint64) + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+
+
+def pn_messages(seed, K_info, F, first_frame=0):
+    """Host mirror of bldpc_encode_random's message rule: int32 [K', F] (frame-fastest)."""
+    KW = (K_info + 63) // 64
+    g = np.arange(first_frame, first_frame + F, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        ctr = np.uint64(int(seed) & _M64) + g[None, :] * np.uint64(KW) + np.arange(KW, dtype=np.uint64)[:, None]
+    words = splitmix64(ctr)  # [KW, F]
+    k = np.arange(K_info)
+    return ((words[k // 64] >> (k % 64).astype(np.uint64)[:, None]) & np.uint64(1)).astype(np.int32)
+
+
+def Syndrome(code, D, into_flag_row=True, stream=None):
+    """bldpc_syndrome: H * d_f == 0 for every frame of the hard bits D (CUDA int32 [N+1, F], or [N, F] with
+    into_flag_row=False).  into_flag_row writes the flag into row N of D, where Statistic reads it.
+    Returns dict(flag=int32 [F], unsat=int32 [F]: unsatisfied checks) on the device."""
+    if not (torch.is_tensor(D) and D.is_cuda and D.dtype == torch.int32 and D.is_contiguous() and D.dim() == 2):
+        raise ValueError("D must be a contiguous CUDA int32 tensor")
+    rows = code.N + 1 if into_flag_row else None
+    if (rows is not None and D.shape[0] != rows) or D.shape[0] < code.N or D.shape[1] <= 0:
+        raise ValueError("D must be [N+1=%d, F]%s" % (code.N + 1, "" if into_flag_row else " or [N, F]"))
+    F, dev = int(D.shape[1]), D.device
+    flag = D[code.N] if into_flag_row else torch.empty(F, dtype=torch.int32, device=dev)
+    unsat = torch.empty(F, dtype=torch.int32, device=dev)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(dev)).cuda_stream)
+    check(lib.bldpc_syndrome(code._h, _dev_ptr(D), F, _dev_ptr(flag), _dev_ptr(unsat), st), "Syndrome")
+    return dict(flag=flag, unsat=unsat)
 
 
 def LDPC_Decoder_GPU(code, Channel_Out, max_iter=50, length=0, exit_mode=EXIT_BATCH_GLOBAL, kernel=KERNEL_AUTO,

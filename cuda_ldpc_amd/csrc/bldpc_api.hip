@@ -12,6 +12,7 @@
 #include <new>
 #include <vector>
 
+#include "bldpc_encode.hpp"
 #include "bldpc_qc_kernel.hpp"
 #include "bldpc_table_kernels.hpp"
 #include "common.hpp"
@@ -36,7 +37,14 @@ struct bldpc_code {
     hipEvent_t evr[2 * kEvRing] = {};
     unsigned ev_n = 0; // decode calls recorded since the last bldpc_kernel_ms_mean
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    EncState *enc = nullptr; // systematic encoder and syndrome tables (bldpc_encode.hip), built on first use
 };
+
+CodeView cldpc::code_view(const bldpc_code *c)
+{
+    bldpc_code *m = const_cast<bldpc_code *>(c); // the EncState slot is scratch, like the other cached buffers
+    return CodeView{c->J, c->L, c->Z, c->N, c->M, c->K, c->has_qc ? c->H.data() : nullptr, &m->enc};
+}
 
 extern "C" const char *bldpc_last_error(void) { return err_buf(); }
 
@@ -214,6 +222,7 @@ extern "C" int bldpc_code_destroy(bldpc_code *c)
     if (c->h_cnt) (void)hipHostFree(c->h_cnt);
     c->rq.release(); c->bad.release(); c->cnt.release(); c->bits.release(); c->yg.release(); c->errs.release(); c->itw.release();
     qc_plan_release(&c->qc);
+    enc_state_free(c->enc);
     for (hipEvent_t e : c->evr)
         if (e) (void)hipEventDestroy(e);
     delete c;

@@ -10,14 +10,25 @@ import numpy as np
 import torch
 
 from . import sharding
-from .bldpc import (EXIT_BATCH_GLOBAL, KERNEL_AUTO, AWGNChannel_CPU, AWGNChannel_GPU, Decode_Statistic, SimCounters, sigma_of)
+from ._lib import check, lib
+from .bldpc import (EXIT_BATCH_GLOBAL, EXIT_FIXED, KERNEL_AUTO, AWGNChannel_CPU, AWGNChannel_GPU, Decode_Statistic, LDPC_Decoder_GPU,
+                    PN_CodeWords, SimCounters, Syndrome, _dev_ptr, sigma_of)
 
 
 def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, exit_mode=EXIT_BATCH_GLOBAL, kernel=KERNEL_AUTO,
                    leastErrorFrames=50, leastTestFrames=10000, displayStep=40960, dist=None, device=None, max_batches=None,
-                   log=print, device_channel=False):
+                   log=print, device_channel=False, PN_Message=0, pn_seed=0):
     """One SNR point (Simulation.cu:12-171).  `seed` (int32[3]) is the AWGN->seed state, advanced in place by the
-    WHOLE batch on every rank so that all ranks stay on the reference's single noise stream."""
+    WHOLE batch on every rank so that all ranks stay on the reference's single noise stream.
+
+    PN_Message=1 fills the reference's empty branch (Simulation.cu:107, define.cuh:26): every batch sends random
+    codewords (bldpc_encode_random with stream `pn_seed`; frame b*F + i of the point is the same codeword at any world
+    size), decodes them with a fixed iteration count, replaces the flag row of D by the syndrome check and counts errors
+    against the sent CodeWord.  The decoders' early exit assumes the zero word, so PN_Message=1 needs EXIT_FIXED."""
+    if PN_Message not in (0, 1):
+        raise ValueError("PN_Message must be 0 (all-zero codeword) or 1 (random codewords)")
+    if PN_Message == 1 and exit_mode != EXIT_FIXED:
+        raise ValueError("PN_Message=1 needs exit_mode=EXIT_FIXED: the decoders' early exit tests for the all-zero word")
     rank = dist.get_rank() if dist is not None and dist.is_initialized() else 0
     world = dist.get_world_size() if dist is not None and dist.is_initialized() else 1
     device = device or torch.device("cuda", torch.cuda.current_device())
@@ -31,15 +42,21 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
     while True:
         SIM.num_Frames += F  # Simulation.cu:113
         my_seed = sharding.lcg_jump(seed, first * per_frame)
+        cw = PN_CodeWords(code, pn_seed, count, first_frame=batches * F + first, device=device) if (PN_Message and count) else None
         if not count:
             yd = None
         elif device_channel:  # same draws, generated on the GPU (device libm in the Box-Muller transform)
-            yd = AWGNChannel_GPU(my_seed, sigma, code.N, count, device=device)
+            yd = AWGNChannel_GPU(my_seed, sigma, code.N, count, device=device, CodeWord=cw)
         else:
-            yd = torch.from_numpy(AWGNChannel_CPU(my_seed, sigma, code.N, count)).to(device)
+            yd = torch.from_numpy(AWGNChannel_CPU(my_seed, sigma, code.N, count, CodeWord=None if cw is None else cw.cpu().numpy())).to(device)
         seed[:] = sharding.lcg_jump(seed, F * per_frame)
         dev_cnt.zero_()
-        if count:
+        if count and PN_Message:
+            r = LDPC_Decoder_GPU(code, yd, max_iter=maxIT, length=length, exit_mode=EXIT_FIXED, kernel=kernel, D=D)
+            Syndrome(code, D, into_flag_row=True)  # flag row: "valid codeword" instead of "first `length` bits zero"
+            st = torch.cuda.current_stream(device).cuda_stream
+            check(lib.bldpc_statistic(code._h, _dev_ptr(D), _dev_ptr(cw), count, length, r["iteraTime"], _dev_ptr(dev_cnt), st), "Statistic")
+        elif count:
             Decode_Statistic(code, yd, dev_cnt, max_iter=maxIT, length=length, exit_mode=exit_mode, kernel=kernel, D=D)  # Simulation.cu:143-145
         sharding.allreduce_counters(dev_cnt, dist)
         c = dev_cnt.cpu().tolist()

@@ -160,6 +160,56 @@ int bldpc_awgn_channel_host(int seed[3], float sigma, float *Channel_Out, const 
  * whole batch exactly like bldpc_awgn_channel_host. */
 int bldpc_awgn_channel_device(int seed[3], float sigma, float *Channel_Out, const int *CodeWord, int N, int F, void *stream);
 
+/* -- encoder and syndrome (PN_Message 1, define.cuh:26) ------------------- */
+
+/* The reference simulates only the all-zero codeword: its PN_Message 1 branch (Simulation.cu:107) is empty.  These
+ * entry points encode real messages for codes made by bldpc_code_create_qc (H convention of the decoders: column c of a
+ * block with shift s meets row (c - s) mod Z); codes made by bldpc_code_create_table return BLDPC_EUNSUPPORTED.
+ *
+ * Generator: Gauss-Jordan over GF(2) on the dense H, pivot columns searched from the right (N-1 down to 0).  The pivot
+ * columns are the parity positions, the other K' = N - rank(H) columns the information set info_pos[K'] (ascending);
+ * information bit k of a message goes to codeword position info_pos[k].  Parity row r belongs to the r-th parity
+ * position in ascending order, and that codeword bit is the XOR of the information bits j for which bit j of row r of
+ * P is set: P is uint64 [rank][ceil(K'/64)], bit j in word j/64 at bit j%64.  For codes whose last M columns are
+ * invertible, info_pos = 0 .. K-1 with K = N - M. */
+
+/* Host only (no device needed): the generator of the QC code with block shifts H[J*L].  Sizes come back in *K_info
+ * and *rank; info_pos (int [K']) and P (rank * ceil(K'/64) words) are filled when not NULL, so a call with both NULL
+ * returns the sizes.  Dense elimination on up to 16 threads: a few seconds for N = 38 400, well under one below. */
+int bldpc_generator_host(int J, int L, int Z, const int *H, int *K_info, int *rank, int *info_pos, unsigned long long *P);
+
+/* K', rank and (when not NULL) info_pos[K'] of the code's generator.  The generator is built on the first call of this
+ * function, bldpc_encode or bldpc_encode_random on the code object, and kept with it. */
+int bldpc_encoder_info(bldpc_code *code, int *K_info, int *rank, int *info_pos);
+
+/* Systematic encoding of F messages on the device.
+ *   msg       device int32 [K'][F]  (in)  frame-fastest; only bit 0 of each entry is read
+ *   CodeWord  device int32 [N][F]   (out) frame-fastest, as everywhere in this ABI: 0/1 per bit, H * c = 0,
+ *             CodeWord[info_pos[k]][f] = msg[k][f] & 1
+ * Asynchronous on `stream` (after the generator exists).  K' is limited to 20 480 (the slices of 64 frames fill the LDS
+ * of one CU); every shipped matrix fits. */
+int bldpc_encode(bldpc_code *code, const int *msg, int F, int *CodeWord, void *stream);
+
+/* The same with messages generated on the device by a counter-based rule, so that any frame can be drawn on its own
+ * (a sharded sweep gets the same codewords at any world size).  For global frame g = first_frame + f, f < F:
+ *     bit k of the message = (splitmix64(seed + g * ceil(K'/64) + k / 64) >> (k % 64)) & 1     (uint64 arithmetic, wrapping)
+ * with splitmix64(x) the first output of SplitMix64 seeded with x:
+ *     z = x + 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *     return z ^ (z >> 31);
+ *   first_frame >= 0;  msg  optional device int32 [K'][F] (out): the messages, NULL to skip;  CodeWord as bldpc_encode. */
+int bldpc_encode_random(bldpc_code *code, unsigned long long seed, long long first_frame, int F, int *msg, int *CodeWord,
+                        void *stream);
+
+/* Syndrome check of F hard-decision words: flag[f] = 1 iff H * d_f = 0 over bit 0 of D[0..N-1][f], and unsat[f] = the
+ * number of unsatisfied checks.
+ *   D      device int32 [N][F] (or the [N+1][F] output of bldpc_decode)
+ *   flag   device int32 [F]: may be row N of D (D + N*F), which then takes the meaning "valid codeword" in place of the
+ *          decoders' "first `length` bits are zero"; bldpc_statistic against the sent CodeWord then counts a frame as an
+ *          error frame when it has bit errors or a failed syndrome, and num_False_Frames = undetected errors
+ *   unsat  device int32 [F] or NULL
+ * Asynchronous on `stream`. */
+int bldpc_syndrome(const bldpc_code *code, const int *D, int F, int *flag, int *unsat, void *stream);
+
 /* sigma of the sweep point (main.cu:120-127): snrtype 0 = Eb/N0 (uses rate), 1 = Es/N0. */
 float bldpc_sigma(float SNR, int snrtype, float rate);
 

@@ -38,8 +38,12 @@ def main():
     ap.add_argument("--qam", type=int, default=2, choices=[2, 64], help="nb: n_QAM (define.h:25): 2 = BPSK, 64 = Constellation/GRAY_64QAM.txt, one point per GF(64) symbol")
     ap.add_argument("--method", type=int, default=0, choices=[0, 1, 2, 3], help="NB decoder_method (define.h:37): 0 EMS, 1 TMM, 2 log-QSPA, 3 layered TMM")
     ap.add_argument("--device-channel", action="store_true", help="generate the AWGN samples on the GPU (same RNG draws, device libm)")
+    ap.add_argument("--pn-message", action="store_true", help="binary: send random codewords (PN_Message 1, define.cuh:26) instead of the all-zero word; needs --fixed")
+    ap.add_argument("--pn-seed", type=int, default=1, help="binary --pn-message: seed of the message stream (bldpc_encode_random)")
     ap.add_argument("--as-written", action="store_true", help="decode on the reference's Transform_H table as written (SURVEY F3)")
     args = ap.parse_args()
+    if args.pn_message and (args.which != "binary" or not args.fixed or args.as_written):
+        ap.error("--pn-message needs the binary sweep with --fixed (the decoders' early exit tests for the all-zero word) on a QC code")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -60,13 +64,14 @@ def main():
         else:
             code = C.BinaryCode.from_blockh(args.matrix, args.J, args.L, args.Z)
         if rank == 0:
-            print("# %s N=%d K=%d, %s, maxIT=%d, batch=%d x %d GPU(s)" % (os.path.basename(args.matrix), code.N, code.K,
+            print("# %s N=%d K=%d, %s, maxIT=%d, batch=%d x %d GPU(s)%s" % (os.path.basename(args.matrix), code.N, code.K,
                   "fixed iterations" if args.fixed else ("per-frame early exit" if args.per_frame else "batch-global early exit"),
-                  args.iters or 50, args.batch, world))
+                  args.iters or 50, args.batch, world,
+                  ", random codewords (PN seed %d, K'=%d), syndrome flag" % (args.pn_seed, code.K_info) if args.pn_message else ""))
             print("# SNR      NTF   NEF         FER         BER  AverIT       FER_F      FER_A")
         sweep(code, args.start, args.stop, args.step, snrtype=1, dist=dist, Num_Frames_OneTime=args.batch, maxIT=args.iters or 50,
               exit_mode=C.EXIT_FIXED if args.fixed else (C.EXIT_PER_FRAME if args.per_frame else C.EXIT_BATCH_GLOBAL), max_batches=args.max_batches, displayStep=10 ** 12, device_channel=args.device_channel,
-              log=print if rank == 0 else None)
+              PN_Message=1 if args.pn_message else 0, pn_seed=args.pn_seed, log=print if rank == 0 else None)
     else:
         from cuda_ldpc_amd import nbldpc as nb
         from cuda_ldpc_amd.nb_simulation import sweep
