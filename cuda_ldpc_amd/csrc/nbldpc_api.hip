@@ -20,6 +20,7 @@
 #include "nbldpc_tmm_kernel.hpp"
 #include "nbldpc_wide_kernel.hpp"
 #include "nbldpc_hbm_kernel.hpp"
+#include "nbldpc_encode.hpp"
 
 using namespace cldpc;
 
@@ -46,6 +47,10 @@ struct nbldpc_code {
     // streams never share a slot unless more than kWorkSlots calls on this code object are in flight at once.
     int *d_work = nullptr;
     std::atomic<unsigned> work_next{0};
+    // encoder (nbldpc_encode.hip): host copies of the CN lists and of TableMultiply, and the generator built on first use
+    std::vector<int> h_cn_w, h_cn_vn, h_cn_gf;
+    std::vector<unsigned> h_mul;
+    NbEncState *enc = nullptr;
 };
 constexpr unsigned kWorkSlots = 1024, kWorkStride = 16; // 64 bytes apart: one counter per cache line
 
@@ -221,6 +226,10 @@ extern "C" int nbldpc_code_create(int N, int M, int q, int dv, int dc, const int
     nbldpc_code *c = new (std::nothrow) nbldpc_code;
     if (!c) return fail(NBLDPC_ENOMEM, "out of host memory");
     c->N = N; c->M = M; c->q = q; c->m = m; c->dv = dv; c->dc = dc; c->lds_bytes = lds; c->hbm = hbm;
+    c->h_cn_w.assign(cn_w, cn_w + M);
+    c->h_cn_vn.assign(cn_vn, cn_vn + (size_t)M * dc);
+    c->h_cn_gf.assign(cn_gf, cn_gf + (size_t)M * dc);
+    c->h_mul.assign(mul, mul + (size_t)q * q);
     int r = 0;
     if (!r) r = up((void **)&c->d_vn_w, vn_w, (size_t)N * sizeof(int));
     if (!r) r = up((void **)&c->d_vn_thr, vn_thr.data(), vn_thr.size() * sizeof(int));
@@ -322,8 +331,16 @@ extern "C" int nbldpc_code_destroy(nbldpc_code *c)
     void *ptrs[] = {c->d_vn_w, c->d_vn_thr, c->d_vn_gf, c->d_cn_w, c->d_cn_src, c->d_cn_gf, c->d_cn_vn, c->d_mul, c->d_cn_hinv, c->d_row_order, c->d_level_begin, c->d_work};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
+    nb_enc_state_free(c->enc);
     delete c;
     return NBLDPC_OK;
+}
+
+NbCodeView cldpc::nb_code_view(const nbldpc_code *c)
+{
+    nbldpc_code *w = const_cast<nbldpc_code *>(c); // the generator slot is a cache: building it does not change the code
+    return NbCodeView{c->N, c->M, c->q, c->m, c->dc, c->h_cn_w.data(), c->h_cn_vn.data(), c->h_cn_gf.data(), c->h_mul.data(),
+                      c->d_cn_w, c->d_cn_vn, c->d_cn_gf, c->d_mul, &w->enc};
 }
 
 extern "C" int nbldpc_ems_decode_batch(nbldpc_code *c, const float *Lch, int B, int Nm, int Nc, int maxIT, int maxdc_cfg, int *out,
@@ -469,7 +486,16 @@ extern "C" int nbldpc_statistic(const nbldpc_code *c, const int *out, const int 
                                 long long *counters, void *stream)
 {
     if (!c || !out || !iters || !ok || !cw || !counters || B <= 0) return fail(NBLDPC_EINVAL, "nbldpc_statistic: bad argument");
-    hipLaunchKernelGGL(k_nb_statistic, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, out, iters, ok, cw, B, c->N, counters);
+    hipLaunchKernelGGL(k_nb_statistic, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, out, iters, ok, cw, 0, B, c->N, counters);
+    CLDPC_HIP(hipGetLastError(), NBLDPC_EHIP);
+    return NBLDPC_OK;
+}
+
+extern "C" int nbldpc_statistic_frames(const nbldpc_code *c, const int *out, const int *iters, const int *ok, const int *cw, int B,
+                                       long long *counters, void *stream)
+{
+    if (!c || !out || !iters || !ok || !cw || !counters || B <= 0) return fail(NBLDPC_EINVAL, "nbldpc_statistic_frames: bad argument");
+    hipLaunchKernelGGL(k_nb_statistic, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, out, iters, ok, cw, c->N, B, c->N, counters);
     CLDPC_HIP(hipGetLastError(), NBLDPC_EHIP);
     return NBLDPC_OK;
 }
@@ -534,14 +560,17 @@ __host__ __device__ inline unsigned nb_powmod(unsigned a, unsigned long long k, 
     return r;
 }
 
-// One thread per (frame b, run of kNbRun consecutive bits): jump to draw 4*(b*N*m + i0), then step as RandomModule does.
+// One thread per (frame b, run of kNbRun consecutive bits): jump to draw 4*(b*N*m + i0), then step as RandomModule does.  Frame b
+// sends the word at cw + b * cw_stride (0: one word for all frames).
 constexpr int kNbRun = 16;
-__global__ __launch_bounds__(256) void k_nb_awgn(unsigned s0, unsigned s1, unsigned s2, float sigma, const int *cw, int N, int m, int B, float *rx)
+__global__ __launch_bounds__(256) void k_nb_awgn(unsigned s0, unsigned s1, unsigned s2, float sigma, const int *cw, int cw_stride, int N, int m, int B,
+                                                 float *rx)
 {
     const int runs = (N * m + kNbRun - 1) / kNbRun;
     const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
     if (id >= (long long)B * runs) return;
     const int b = (int)(id / runs), i0 = (int)(id - (long long)b * runs) * kNbRun;
+    cw += (size_t)b * cw_stride;
     const unsigned long long k = 4ull * ((unsigned long long)b * N * m + i0);
     unsigned s[3] = {s0, s1, s2};
 #pragma unroll
@@ -574,17 +603,30 @@ extern "C" int nbldpc_awgn_channel_device(int seed[3], float sigma, const int *c
         if (seed[i] < 0 || (unsigned)seed[i] >= kNbM[i]) return fail(NBLDPC_EINVAL, "seed[%d]=%d outside [0,%u)", i, seed[i], kNbM[i]);
     const long long threads = (long long)B * ((N * m + kNbRun - 1) / kNbRun);
     hipLaunchKernelGGL(k_nb_awgn, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (unsigned)seed[0], (unsigned)seed[1],
-                       (unsigned)seed[2], sigma, cw, N, m, B, rx);
+                       (unsigned)seed[2], sigma, cw, 0, N, m, B, rx);
     CLDPC_HIP(hipGetLastError(), NBLDPC_EHIP);
     const unsigned long long draws = 4ull * (unsigned long long)N * m * B;
     for (int i = 0; i < 3; i++) seed[i] = (int)(((unsigned long long)seed[i] * nb_powmod(kNbA[i], draws, kNbM[i])) % kNbM[i]);
     return NBLDPC_OK;
 }
 
+extern "C" int nbldpc_awgn_channel_device_frames(int seed[3], float sigma, const int *cw, int N, int m, int B, float *rx, void *stream)
+{
+    if (!seed || !cw || !rx || N <= 0 || m <= 0 || B <= 0) return fail(NBLDPC_EINVAL, "nbldpc_awgn_channel_device_frames: bad argument");
+    for (int i = 0; i < 3; i++)
+        if (seed[i] < 0 || (unsigned)seed[i] >= kNbM[i]) return fail(NBLDPC_EINVAL, "seed[%d]=%d outside [0,%u)", i, seed[i], kNbM[i]);
+    const long long threads = (long long)B * ((N * m + kNbRun - 1) / kNbRun);
+    hipLaunchKernelGGL(k_nb_awgn, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (unsigned)seed[0], (unsigned)seed[1],
+                       (unsigned)seed[2], sigma, cw, N, N, m, B, rx);
+    CLDPC_HIP(hipGetLastError(), NBLDPC_EHIP);
+    return nbldpc_seed_jump(seed, 4ull * (unsigned long long)N * m * B);
+}
+
 namespace {
-// QAM: one thread per (frame b, symbol i): jump to draw 4*(b*N + i), Real part from draws 1-2, Image part from draws 3-4.
-__global__ __launch_bounds__(256) void k_nb_awgn_qam(unsigned s0, unsigned s1, unsigned s2, float sigma, const int *cw, const float *con, int N, int B,
-                                                    float *rx)
+// QAM: one thread per (frame b, symbol i): jump to draw 4*(b*N + i), Real part from draws 1-2, Image part from draws 3-4.  Frame b
+// sends the word at cw + b * cw_stride (0: one word for all frames), symbols masked with qmask (-1: as they are).
+__global__ __launch_bounds__(256) void k_nb_awgn_qam(unsigned s0, unsigned s1, unsigned s2, float sigma, const int *cw, int cw_stride, int qmask,
+                                                    const float *con, int N, int B, float *rx)
 {
     const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
     if (id >= (long long)B * N) return;
@@ -605,7 +647,7 @@ __global__ __launch_bounds__(256) void k_nb_awgn_qam(unsigned s0, unsigned s1, u
         t -= (int)t;
         u[d] = t;
     }
-    const int sym = cw[i];
+    const int sym = cw[(size_t)(id / N) * cw_stride + i] & qmask;
 #pragma unroll
     for (int c = 0; c < 2; c++) {
         const float amp = sqrtf(-2.0f * logf(1.0f - u[2 * c]));
@@ -621,11 +663,25 @@ extern "C" int nbldpc_awgn_channel_device_qam(int seed[3], float sigma, const in
         if (seed[i] < 0 || (unsigned)seed[i] >= kNbM[i]) return fail(NBLDPC_EINVAL, "seed[%d]=%d outside [0,%u)", i, seed[i], kNbM[i]);
     const long long threads = (long long)B * N;
     hipLaunchKernelGGL(k_nb_awgn_qam, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (unsigned)seed[0],
-                       (unsigned)seed[1], (unsigned)seed[2], sigma, cw, con, N, B, rx);
+                       (unsigned)seed[1], (unsigned)seed[2], sigma, cw, 0, -1, con, N, B, rx);
     CLDPC_HIP(hipGetLastError(), NBLDPC_EHIP);
     const unsigned long long draws = 4ull * (unsigned long long)N * B;
     for (int i = 0; i < 3; i++) seed[i] = (int)(((unsigned long long)seed[i] * nb_powmod(kNbA[i], draws, kNbM[i])) % kNbM[i]);
     return NBLDPC_OK;
+}
+
+extern "C" int nbldpc_awgn_channel_device_qam_frames(int seed[3], float sigma, const int *cw, int N, const float *con, int q, int B, float *rx,
+                                                     void *stream)
+{
+    if (!seed || !cw || !con || !rx || N <= 0 || B <= 0 || q < 2 || (q & (q - 1)))
+        return fail(NBLDPC_EINVAL, "nbldpc_awgn_channel_device_qam_frames: bad argument");
+    for (int i = 0; i < 3; i++)
+        if (seed[i] < 0 || (unsigned)seed[i] >= kNbM[i]) return fail(NBLDPC_EINVAL, "seed[%d]=%d outside [0,%u)", i, seed[i], kNbM[i]);
+    const long long threads = (long long)B * N;
+    hipLaunchKernelGGL(k_nb_awgn_qam, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (unsigned)seed[0],
+                       (unsigned)seed[1], (unsigned)seed[2], sigma, cw, N, q - 1, con, N, B, rx);
+    CLDPC_HIP(hipGetLastError(), NBLDPC_EHIP);
+    return nbldpc_seed_jump(seed, 4ull * (unsigned long long)N * B);
 }
 
 // ---- the reference's AWGNChannel_CPU as it is declared: noise on a modulated frame (any constellation) -------------------------
@@ -704,12 +760,13 @@ extern "C" int nbldpc_seed_jump(int seed[3], unsigned long long draws)
 
 namespace {
 // errs[b] = number of symbols of frame b that differ from the transmitted word (Statistic, Simulation.cpp:264-267): one wave per frame
-__global__ __launch_bounds__(256) void k_nb_frame_errors(const int *out, const int *cw, int B, int N, int *errs)
+// against cw + b * cw_stride (0: one word for all frames)
+__global__ __launch_bounds__(256) void k_nb_frame_errors(const int *out, const int *cw, int cw_stride, int B, int N, int *errs)
 {
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (b >= B) return;
     int e = 0;
-    for (int i = lane; i < N; i += 64) e += out[(size_t)b * N + i] != cw[i];
+    for (int i = lane; i < N; i += 64) e += out[(size_t)b * N + i] != cw[(size_t)b * cw_stride + i];
 #pragma unroll
     for (int o = 32; o; o >>= 1) e += __shfl_xor(e, o);
     if (lane == 0) errs[b] = e;
@@ -719,7 +776,15 @@ __global__ __launch_bounds__(256) void k_nb_frame_errors(const int *out, const i
 extern "C" int nbldpc_frame_errors(const nbldpc_code *c, const int *out, const int *cw, int B, int *errs, void *stream)
 {
     if (!c || !out || !cw || !errs || B <= 0) return fail(NBLDPC_EINVAL, "nbldpc_frame_errors: bad argument");
-    hipLaunchKernelGGL(k_nb_frame_errors, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, out, cw, B, c->N, errs);
+    hipLaunchKernelGGL(k_nb_frame_errors, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, out, cw, 0, B, c->N, errs);
+    CLDPC_HIP(hipGetLastError(), NBLDPC_EHIP);
+    return NBLDPC_OK;
+}
+
+extern "C" int nbldpc_frame_errors_frames(const nbldpc_code *c, const int *out, const int *cw, int B, int *errs, void *stream)
+{
+    if (!c || !out || !cw || !errs || B <= 0) return fail(NBLDPC_EINVAL, "nbldpc_frame_errors_frames: bad argument");
+    hipLaunchKernelGGL(k_nb_frame_errors, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, out, cw, c->N, B, c->N, errs);
     CLDPC_HIP(hipGetLastError(), NBLDPC_EHIP);
     return NBLDPC_OK;
 }

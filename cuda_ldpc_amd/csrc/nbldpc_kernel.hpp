@@ -717,15 +717,16 @@ __global__ __launch_bounds__(256) void k_nb_demod_qam(const float *rx, const flo
     Lch[id] = ((2 * yr - c0r - ckr) * (ckr - c0r) + (2 * yi - c0i - cki) * (cki - c0i)) / (2 * sigma * sigma);
 }
 
-// Statistic (Simulation.cpp:256-279): one thread per frame.
-__global__ __launch_bounds__(256) void k_nb_statistic(const int *out, const int *iters, const int *ok, const int *cw, int B, int N,
+// Statistic (Simulation.cpp:256-279): one thread per frame.  Frame f is compared with cw + f * cw_stride (0: one word for all frames).
+__global__ __launch_bounds__(256) void k_nb_statistic(const int *out, const int *iters, const int *ok, const int *cw, int cw_stride, int B, int N,
                                                       long long *counters)
 {
     const int f = blockIdx.x * 256 + threadIdx.x;
     long long v[4] = {0, 0, 0, 0};
     if (f < B) {
         int err = 0;
-        for (int i = 0; i < N; i++) err += (out[(size_t)f * N + i] != cw[i]) ? 1 : 0;
+        const int *w = cw + (size_t)f * cw_stride;
+        for (int i = 0; i < N; i++) err += (out[(size_t)f * N + i] != w[i]) ? 1 : 0;
         v[0] = err != 0;
         v[1] = err;
         v[2] = iters[f];

@@ -41,19 +41,30 @@ class NBSim:
 
 
 def Simulation_GPU(code, seed, sigma, SIM, CodeWord_sym, EMS_Nm=2, EMS_Nc=2, maxIT=20, batch=1024, leastErrorFrames=50,
-                   leastTestFrames=1000, max_frames=None, device=None, device_channel=False, decoder_method=0, CONSTELLATION=None):
+                   leastTestFrames=1000, max_frames=None, device=None, device_channel=False, decoder_method=0, CONSTELLATION=None,
+                   PN_Message=0, pn_seed=0):
     """One Eb/N0 point. `seed` (int32[3]) advances exactly as far as the reference would have drawn.
     device_channel: generate the noise on the GPU (same uniforms, device libm) instead of the host, frame by frame.
     decoder_method (define.h:37, Simulation.cpp:54-70): 0 EMS, 1 trellis min-max, 2 log-QSPA = EMS(q, dc-1), 3 layered TMM.
     CONSTELLATION (host float32 [q, 2], Get_CONSTELLATION): the n_QAM = q branches of Modulate / AWGNChannel_CPU / Demodulate
-    (one constellation point per code symbol) instead of BPSK; the caller passes the sigma of that n_QAM."""
+    (one constellation point per code symbol) instead of BPSK; the caller passes the sigma of that n_QAM.
+    PN_Message=1: every frame sends its own random codeword in place of CodeWord_sym (may be None): frame i of the point is
+    PN_CodeWords(code, pn_seed, ..., first_frame=i) (nbldpc_encode_random), and its errors are counted against that word.  The
+    decoders stop on their own syndrome, so the stop rule and the seed roll-back are unchanged."""
+    if PN_Message not in (0, 1):
+        raise ValueError("PN_Message must be 0 (CodeWord_sym for every frame) or 1 (random codewords)")
     device = device or torch.device("cuda", torch.cuda.current_device())
-    cw = np.ascontiguousarray(CodeWord_sym, np.int32)
-    cw_dev = torch.from_numpy(cw).to(device)
+    cw = None if PN_Message else np.ascontiguousarray(CodeWord_sym, np.int32)
+    cw_dev = None if PN_Message else torch.from_numpy(cw).to(device)
     qam = CONSTELLATION is not None
     con = np.ascontiguousarray(CONSTELLATION, np.float32) if qam else None
     con_dev = torch.from_numpy(con).to(device) if qam else None
+    frames = 0  # frames drawn at this point: numbers the random codewords
     while True:
+        if PN_Message:
+            cw_dev = nb.PN_CodeWords(code, pn_seed, batch, first_frame=frames, device=device)
+            cw = None if device_channel else cw_dev.cpu().numpy()
+        frames += batch
         if device_channel:
             seed0 = seed.copy()
             seeds_before = _SeedsAfter(seed0, code, qam)
@@ -63,7 +74,7 @@ def Simulation_GPU(code, seed, sigma, SIM, CodeWord_sym, EMS_Nm=2, EMS_Nc=2, max
             rx = np.empty((batch, code.N, 2) if qam else (batch, code.N * code.m), np.float32)
             for b in range(batch):
                 seeds_before.append(seed.copy())
-                rx[b] = nb.AWGNChannel_CPU(seed, sigma, code, cw, CONSTELLATION=con)
+                rx[b] = nb.AWGNChannel_CPU(seed, sigma, code, cw[b] if PN_Message else cw, CONSTELLATION=con)
             rxt = torch.from_numpy(rx).to(device)
         Lch = nb.Demodulate(code, rxt, sigma, CONSTELLATION=con_dev)
         if decoder_method == 0:
@@ -72,7 +83,7 @@ def Simulation_GPU(code, seed, sigma, SIM, CodeWord_sym, EMS_Nm=2, EMS_Nc=2, max
             r = nb.Decoding_EMS(code, Lch, code.q, code.dc - 1, maxIT)  # Simulation.cpp:63-66
         else:
             r = nb.Decoding_TMM(code, Lch, maxIT, layered=(decoder_method == 3))
-        errs = (r["DecodeOutput"] != cw_dev[None, :]).sum(dim=1).cpu().numpy()
+        errs = (r["DecodeOutput"] != (cw_dev if PN_Message else cw_dev[None, :])).sum(dim=1).cpu().numpy()
         its = r["iter_number"].cpu().numpy()
         for b in range(batch):  # account in stream order; stop where the reference's while-condition fails
             SIM.num_Frames += 1

@@ -33,6 +33,14 @@ lib.nbldpc_awgn_channel_device_qam.argtypes = [c_void_p, c_float, c_void_p, c_in
 lib.nbldpc_demodulate_qam.argtypes = [c_void_p, c_void_p, c_void_p, c_float, c_int, c_void_p, c_void_p]
 lib.nbldpc_sigma.restype = c_float
 lib.nbldpc_sigma.argtypes = [c_float, c_int, c_int, c_float]
+lib.nbldpc_generator_host.argtypes = [c_int] * 4 + [c_void_p] * 4 + [ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p, c_void_p]
+lib.nbldpc_encoder_info.argtypes = [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p]
+lib.nbldpc_encode.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p]
+lib.nbldpc_encode_random.argtypes = [c_void_p, ctypes.c_ulonglong, ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p]
+lib.nbldpc_syndrome.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]
+lib.nbldpc_awgn_channel_device_frames.argtypes = [c_void_p, c_float, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
+lib.nbldpc_awgn_channel_device_qam_frames.argtypes = [c_void_p, c_float, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]
+lib.nbldpc_statistic_frames.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
 
 
 def _check(rc, what):
@@ -61,10 +69,10 @@ def GFInitial(q, path=None, primitive_poly=None):
     return mul, add, inv
 
 
-class NBCode:
-    """Get_H (Simulation.cpp:347-467) + device upload. Holds the flattened VN/CN arrays on the host too."""
+class NBMatrix:
+    """Get_H (Simulation.cpp:347-467) on the host only: N, M, q, dv, dc, rate and the flattened VN/CN arrays."""
 
-    def __init__(self, matrix_path, TableMultiply):
+    def __init__(self, matrix_path):
         dims = np.zeros(5, np.int32)
         _check(lib.nbldpc_read_matrix(str(matrix_path).encode(), _np(dims), None, None, None, None, None, None), "Get_H")
         self.N, self.M, self.q, self.dv, self.dc = (int(x) for x in dims)
@@ -79,12 +87,41 @@ class NBCode:
                                       _np(self.vn_linkCNs_GF), _np(self.cn_weight), _np(self.cn_linkVNs), _np(self.cn_linkVNs_GF)),
                "Get_H")
         self.rate = np.float32(self.N - self.M) / np.float32(self.N)  # H->rate (Simulation.cpp:365)
+
+
+class NBCode(NBMatrix):
+    """Get_H (Simulation.cpp:347-467) + device upload. Holds the flattened VN/CN arrays on the host too."""
+
+    def __init__(self, matrix_path, TableMultiply):
+        super().__init__(matrix_path)
         self.TableMultiply = np.ascontiguousarray(TableMultiply, np.uint32)
         h = c_void_p()
         _check(lib.nbldpc_code_create(self.N, self.M, self.q, self.dv, self.dc, _np(self.vn_weight), _np(self.vn_linkCNs),
                                       _np(self.vn_linkCNs_GF), _np(self.cn_weight), _np(self.cn_linkVNs), _np(self.cn_linkVNs_GF),
                                       _np(self.TableMultiply), ctypes.byref(h)), "nbldpc_code_create")
         self._h = h
+
+    def _encoder_info(self):
+        if getattr(self, "_info_pos", None) is None:
+            k, r = c_int(0), c_int(0)
+            pos = np.zeros(self.N, np.int32)
+            _check(lib.nbldpc_encoder_info(self._h, ctypes.byref(k), ctypes.byref(r), _np(pos)), "nbldpc_encoder_info")
+            self._K_info, self._rank, self._info_pos = k.value, r.value, pos[:k.value].copy()
+        return self._K_info, self._rank, self._info_pos
+
+    @property
+    def K_info(self):
+        """K' = N - rank(H): information symbols per codeword of the systematic encoder (builds the generator on first use)."""
+        return self._encoder_info()[0]
+
+    @property
+    def rank(self):
+        return self._encoder_info()[1]
+
+    @property
+    def info_positions(self):
+        """int32 [K'] (host, ascending): codeword position of each information symbol."""
+        return self._encoder_info()[2]
 
     @property
     def last_kernel(self):
@@ -193,10 +230,16 @@ def AWGNChannel_CPU(seed, sigma, code, CodeWord_sym, CONSTELLATION=None):
 def AWGNChannel_GPU(seed, sigma, code, CodeWord_sym_dev, B, stream=None, CONSTELLATION=None):
     """Device-side Modulate + AWGNChannel for B consecutive frames of the same stream (LCG jump-ahead: the uniforms are
     the reference's, the samples may differ from the host libm's by an ulp).  Returns rx CUDA float32 [B, N*m]; seed
-    advanced exactly like B calls of AWGNChannel_CPU."""
+    advanced exactly like B calls of AWGNChannel_CPU.  CodeWord_sym_dev [N] is sent by every frame; [B, N] (contiguous) gives
+    frame b its own word, row b, with the same draws."""
     if not (isinstance(seed, np.ndarray) and seed.dtype == np.int32 and seed.size == 3):
         raise ValueError("seed must be an int32 numpy array of 3")
-    if not (CodeWord_sym_dev.is_cuda and CodeWord_sym_dev.dtype == torch.int32 and CodeWord_sym_dev.numel() == code.N):
+    per_frame = CodeWord_sym_dev.dim() == 2
+    if per_frame:
+        if not (CodeWord_sym_dev.is_cuda and CodeWord_sym_dev.dtype == torch.int32 and CodeWord_sym_dev.is_contiguous()
+                and tuple(CodeWord_sym_dev.shape) == (B, code.N)):
+            raise ValueError("CodeWord_sym_dev must be a contiguous CUDA int32 tensor [B=%d, N=%d]" % (B, code.N))
+    elif not (CodeWord_sym_dev.is_cuda and CodeWord_sym_dev.dtype == torch.int32 and CodeWord_sym_dev.numel() == code.N):
         raise ValueError("CodeWord_sym_dev must be a CUDA int32 tensor of N symbols")
     if CONSTELLATION is not None:  # n_QAM != 2 branch: rx [B, N, 2], four draws per SYMBOL
         if not (CONSTELLATION.is_cuda and CONSTELLATION.dtype == torch.float32 and CONSTELLATION.is_contiguous()
@@ -204,12 +247,17 @@ def AWGNChannel_GPU(seed, sigma, code, CodeWord_sym_dev, B, stream=None, CONSTEL
             raise ValueError("CONSTELLATION must be a contiguous CUDA float32 tensor [q, 2]")
         rx = torch.empty((B, code.N, 2), dtype=torch.float32, device=CodeWord_sym_dev.device)
         st = c_void_p((stream or torch.cuda.current_stream(rx.device)).cuda_stream)
-        _check(lib.nbldpc_awgn_channel_device_qam(_np(seed), c_float(sigma), _dev(CodeWord_sym_dev), code.N, _dev(CONSTELLATION), B, _dev(rx), st),
-               "AWGNChannel_GPU")
+        if per_frame:
+            _check(lib.nbldpc_awgn_channel_device_qam_frames(_np(seed), c_float(sigma), _dev(CodeWord_sym_dev), code.N, _dev(CONSTELLATION), code.q,
+                                                             B, _dev(rx), st), "AWGNChannel_GPU")
+        else:
+            _check(lib.nbldpc_awgn_channel_device_qam(_np(seed), c_float(sigma), _dev(CodeWord_sym_dev), code.N, _dev(CONSTELLATION), B, _dev(rx), st),
+                   "AWGNChannel_GPU")
         return rx
     rx = torch.empty((B, code.N * code.m), dtype=torch.float32, device=CodeWord_sym_dev.device)
     st = c_void_p((stream or torch.cuda.current_stream(rx.device)).cuda_stream)
-    _check(lib.nbldpc_awgn_channel_device(_np(seed), c_float(sigma), _dev(CodeWord_sym_dev), code.N, code.m, B, _dev(rx), st), "AWGNChannel_GPU")
+    fn = lib.nbldpc_awgn_channel_device_frames if per_frame else lib.nbldpc_awgn_channel_device
+    _check(fn(_np(seed), c_float(sigma), _dev(CodeWord_sym_dev), code.N, code.m, B, _dev(rx), st), "AWGNChannel_GPU")
     return rx
 
 
@@ -226,8 +274,99 @@ def sigma_of(SNR, rate, snrtype=0, n_QAM=2):
 
 
 def Statistic(code, counters, res, CodeWord_sym_dev, stream=None):
-    """Statistic (Simulation.cpp:256-279) on the device; counters: CUDA int64[4], accumulated."""
+    """Statistic (Simulation.cpp:256-279) on the device; counters: CUDA int64[4], accumulated.  CodeWord_sym_dev [N] for every
+    frame, or [B, N] (contiguous): frame b against row b."""
     B = int(res["DecodeOutput"].shape[0])
     st = c_void_p((stream or torch.cuda.current_stream(counters.device)).cuda_stream)
-    _check(lib.nbldpc_statistic(code._h, _dev(res["DecodeOutput"]), _dev(res["iter_number"]), _dev(res["ok"]), _dev(CodeWord_sym_dev),
-                                B, _dev(counters), st), "Statistic")
+    if CodeWord_sym_dev.dim() == 2:
+        if not (CodeWord_sym_dev.is_contiguous() and CodeWord_sym_dev.dtype == torch.int32 and tuple(CodeWord_sym_dev.shape) == (B, code.N)):
+            raise ValueError("CodeWord_sym_dev must be a contiguous int32 tensor [B=%d, N=%d]" % (B, code.N))
+        fn = lib.nbldpc_statistic_frames
+    else:
+        fn = lib.nbldpc_statistic
+    _check(fn(code._h, _dev(res["DecodeOutput"]), _dev(res["iter_number"]), _dev(res["ok"]), _dev(CodeWord_sym_dev), B, _dev(counters), st),
+           "Statistic")
+
+
+def generator_host(code, TableMultiply=None):
+    """nbldpc_generator_host: the systematic generator on the host (no device), from the CN lists of an NBMatrix / NBCode and
+    TableMultiply (default: the code's).  Returns dict(K_info, rank, info_pos=int32 [K'], P=uint8 [rank, K']): parity symbol r
+    (the r-th non-information position, ascending) = XOR_j TableMultiply[msg[j]][P[r, j]]."""
+    mul = np.ascontiguousarray(code.TableMultiply if TableMultiply is None else TableMultiply, np.uint32)
+    if mul.shape != (code.q, code.q):
+        raise ValueError("TableMultiply must be [q, q]")
+    k, r = c_int(0), c_int(0)
+    pos = np.zeros(code.N, np.int32)
+    P = np.zeros(code.N * code.N // 4 + 1, np.uint8)  # rank * K' <= N^2 / 4: one call fills both
+    _check(lib.nbldpc_generator_host(code.N, code.M, code.q, code.dc, _np(code.cn_weight), _np(code.cn_linkVNs), _np(code.cn_linkVNs_GF), _np(mul),
+                                     ctypes.byref(k), ctypes.byref(r), _np(pos), _np(P)), "nbldpc_generator_host")
+    return dict(K_info=k.value, rank=r.value, info_pos=pos[:k.value].copy(), P=P[:r.value * k.value].reshape(r.value, k.value).copy())
+
+
+def _check_cw(CodeWord_sym, B, N, dev):
+    if not (torch.is_tensor(CodeWord_sym) and CodeWord_sym.is_cuda and CodeWord_sym.device == dev and CodeWord_sym.dtype == torch.int32
+            and CodeWord_sym.is_contiguous() and tuple(CodeWord_sym.shape) == (B, N)):
+        raise ValueError("CodeWord_sym must be a contiguous CUDA int32 tensor [B=%d, N=%d] on %s" % (B, N, dev))
+
+
+def Encode(code, msg, CodeWord_sym=None, stream=None):
+    """nbldpc_encode: msg = CUDA int32 tensor [B, K'] (low log2 q bits read) -> CodeWord_sym int32 [B, N] on the device,
+    systematic on code.info_positions."""
+    K = code.K_info
+    if not (torch.is_tensor(msg) and msg.is_cuda and msg.dtype == torch.int32 and msg.is_contiguous() and msg.dim() == 2
+            and msg.shape[1] == K and msg.shape[0] > 0):
+        raise ValueError("msg must be a contiguous CUDA int32 tensor [B, K'=%d]" % K)
+    B, dev = int(msg.shape[0]), msg.device
+    if CodeWord_sym is None:
+        CodeWord_sym = torch.empty((B, code.N), dtype=torch.int32, device=dev)
+    else:
+        _check_cw(CodeWord_sym, B, code.N, dev)
+    st = c_void_p((stream or torch.cuda.current_stream(dev)).cuda_stream)
+    _check(lib.nbldpc_encode(code._h, _dev(msg), B, _dev(CodeWord_sym), st), "Encode")
+    return CodeWord_sym
+
+
+def PN_CodeWords(code, seed, B, first_frame=0, want_msg=False, device=None, CodeWord_sym=None, stream=None):
+    """nbldpc_encode_random: the codewords of frames first_frame .. first_frame+B-1 of the message stream `seed` (counter-based
+    rule of nbldpc.h, mirrored by pn_messages below).  Returns CodeWord_sym int32 [B, N] on the device, or (CodeWord_sym,
+    msg [B, K']) with want_msg."""
+    if B <= 0 or first_frame < 0:
+        raise ValueError("B must be positive and first_frame >= 0")
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    if CodeWord_sym is None:
+        CodeWord_sym = torch.empty((B, code.N), dtype=torch.int32, device=device)
+    else:
+        _check_cw(CodeWord_sym, B, code.N, device)
+    msg = torch.empty((B, code.K_info), dtype=torch.int32, device=device) if want_msg else None
+    st = c_void_p((stream or torch.cuda.current_stream(device)).cuda_stream)
+    _check(lib.nbldpc_encode_random(code._h, ctypes.c_ulonglong(int(seed) % (1 << 64)), int(first_frame), B, _dev(msg), _dev(CodeWord_sym), st),
+           "PN_CodeWords")
+    return (CodeWord_sym, msg) if want_msg else CodeWord_sym
+
+
+def pn_messages(seed, K_info, q, B, first_frame=0):
+    """Host mirror of nbldpc_encode_random's message rule: int32 [B, K']."""
+    from .bldpc import splitmix64
+    m = int(q).bit_length() - 1
+    s = 64 // m
+    W = -(-K_info // s)
+    g = np.arange(first_frame, first_frame + B, dtype=np.uint64)
+    k = np.arange(K_info)
+    with np.errstate(over="ignore"):
+        ctr = np.uint64(int(seed) % (1 << 64)) + g[:, None] * np.uint64(W) + (k // s).astype(np.uint64)[None, :]
+    words = splitmix64(ctr)
+    return ((words >> (m * (k % s)).astype(np.uint64)[None, :]) & np.uint64(q - 1)).astype(np.int32)
+
+
+def Syndrome(code, DecodeOutput, stream=None):
+    """nbldpc_syndrome: H * d_b == 0 over GF(q) for every frame of DecodeOutput (CUDA int32 [B, N], low log2 q bits read).
+    Returns dict(flag=int32 [B], unsat=int32 [B]: unsatisfied checks) on the device."""
+    if not (torch.is_tensor(DecodeOutput) and DecodeOutput.is_cuda and DecodeOutput.dtype == torch.int32 and DecodeOutput.is_contiguous()
+            and DecodeOutput.dim() == 2 and DecodeOutput.shape[1] == code.N and DecodeOutput.shape[0] > 0):
+        raise ValueError("DecodeOutput must be a contiguous CUDA int32 tensor [B, N=%d]" % code.N)
+    B, dev = int(DecodeOutput.shape[0]), DecodeOutput.device
+    flag = torch.empty(B, dtype=torch.int32, device=dev)
+    unsat = torch.empty(B, dtype=torch.int32, device=dev)
+    st = c_void_p((stream or torch.cuda.current_stream(dev)).cuda_stream)
+    _check(lib.nbldpc_syndrome(code._h, _dev(DecodeOutput), B, _dev(flag), _dev(unsat), st), "Syndrome")
+    return dict(flag=flag, unsat=unsat)

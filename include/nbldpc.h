@@ -167,6 +167,60 @@ int nbldpc_frame_errors(const nbldpc_code *code, const int *DecodeOutput, const 
 /* sigma of a sweep point (src/main.cu:221-228). */
 float nbldpc_sigma(float SNR, int snrtype, int n_QAM, float rate);
 
+/* ---- encoder and syndrome check.  The reference sends one fixed CodeWord_sym that every frame shares (src/main.cu:190-212 copies
+ * codeword_test.h).  These entry points encode real messages, one codeword per frame, for any code object (H as the decoders see it:
+ * entry (r, v) of the M x N symbol matrix is the XOR of the coefficients of all edges (r, v); a coefficient 0 contributes nothing).
+ *
+ * Generator: Gauss-Jordan over GF(q) on the dense H, multiplication by TableMultiply[symbol][coefficient], addition XOR, pivot
+ * columns searched from the right (N-1 down to 0), every pivot row normalised to 1.  The pivot columns are the parity positions, the
+ * other K' = N - rank(H) columns the information set info_pos[K'] (ascending); information symbol k of a message goes to codeword
+ * position info_pos[k].  Parity row r belongs to the r-th parity position in ascending order, par_pos[r], and
+ *     c[par_pos[r]] = XOR_j TableMultiply[msg[j]][P[r][j]],     P uint8 [rank][K'].
+ * For codes whose last M columns are invertible, info_pos = 0 .. K-1 with K = N - M.  TableMultiply must be a field table with XOR
+ * addition (commutative, 1 the identity, distributive over XOR, associative, every nonzero element invertible): otherwise
+ * NBLDPC_EUNSUPPORTED. ---- */
+
+/* Host only (no device needed): the generator from the CN lists (as nbldpc_read_matrix returns them) and TableMultiply (host unsigned
+ * [q][q]).  Sizes come back in *K_info and *rank; info_pos (int [K']) and P (rank * K' bytes) are filled when not NULL, so a call with
+ * both NULL returns the sizes.  Dense elimination on up to 16 threads. */
+int nbldpc_generator_host(int N, int M, int q, int dcmax, const int *cn_weight, const int *cn_linkVNs, const int *cn_linkVNs_GF,
+                          const unsigned *TableMultiply, int *K_info, int *rank, int *info_pos, unsigned char *P);
+
+/* K', rank and (when not NULL) info_pos[K'] of the code's generator.  The generator is built on the first call of this function,
+ * nbldpc_encode or nbldpc_encode_random on the code object (from the copies of the CN lists and of TableMultiply that
+ * nbldpc_code_create keeps), kept with it and freed by nbldpc_code_destroy. */
+int nbldpc_encoder_info(nbldpc_code *code, int *K_info, int *rank, int *info_pos);
+
+/* Systematic encoding of B messages on the device.
+ *   msg           DEVICE int32 [B][K']  (in)  frame-outer; only the low m = log2 q bits of each entry are read
+ *   CodeWord_sym  DEVICE int32 [B][N]   (out) H * c = 0 over GF(q), CodeWord_sym[b][info_pos[k]] = msg[b][k] & (q-1)
+ * Asynchronous on `stream` (after the generator exists). */
+int nbldpc_encode(nbldpc_code *code, const int *msg, int B, int *CodeWord_sym, void *stream);
+
+/* The same with messages generated on the device by a counter-based rule, so that any frame can be drawn on its own.  With
+ * m = log2 q, s = floor(64 / m) symbols per word and W = ceil(K' / s) words per frame, symbol k of global frame g = first_frame + b is
+ *     (splitmix64(seed + g * W + k / s) >> (m * (k % s))) & (q - 1)          (uint64 arithmetic, wrapping)
+ * with splitmix64 the function include/bldpc.h defines (the first output of SplitMix64 seeded with x).
+ *   first_frame >= 0;  msg  optional DEVICE int32 [B][K'] (out): the messages, NULL to skip;  CodeWord_sym as nbldpc_encode. */
+int nbldpc_encode_random(nbldpc_code *code, unsigned long long seed, long long first_frame, int B, int *msg, int *CodeWord_sym, void *stream);
+
+/* Syndrome check of B words, the decoders' own check (src/LDPC_Decoder.cpp:219-230) on the low m bits of each symbol:
+ * flag[b] = 1 iff H * d_b = 0 over GF(q), unsat[b] = the number of unsatisfied checks.
+ *   DecodeOutput DEVICE int32 [B][N];  flag DEVICE int32 [B];  unsat DEVICE int32 [B] or NULL.  Asynchronous on `stream`. */
+int nbldpc_syndrome(const nbldpc_code *code, const int *DecodeOutput, int B, int *flag, int *unsat, void *stream);
+
+/* nbldpc_awgn_channel_device / _qam with one word per frame: CodeWord_sym DEVICE int32 [B][N], frame b sends row b.  Draws and seed
+ * advance are those of the shared-word calls (frame b of the batch is frame b of the stream, whatever it sends).  The QAM form reads
+ * the low log2 q bits of each symbol; constellation DEVICE float [q][2]. */
+int nbldpc_awgn_channel_device_frames(int seed[3], float sigma, const int *CodeWord_sym, int N, int m, int B, float *rx, void *stream);
+int nbldpc_awgn_channel_device_qam_frames(int seed[3], float sigma, const int *CodeWord_sym, int N, const float *constellation, int q, int B,
+                                          float *rx, void *stream);
+
+/* nbldpc_statistic / nbldpc_frame_errors against one word per frame: CodeWord_sym DEVICE int32 [B][N]. */
+int nbldpc_statistic_frames(const nbldpc_code *code, const int *DecodeOutput, const int *iter_number, const int *ok, const int *CodeWord_sym,
+                            int B, long long *counters, void *stream);
+int nbldpc_frame_errors_frames(const nbldpc_code *code, const int *DecodeOutput, const int *CodeWord_sym, int B, int *errs, void *stream);
+
 const char *nbldpc_last_error(void);
 
 #ifdef __cplusplus

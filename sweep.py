@@ -35,15 +35,26 @@ def main():
     ap.add_argument("--iters", type=int, default=None)
     ap.add_argument("--fixed", action="store_true", help="fixed iteration count instead of the reference's batch-global early exit")
     ap.add_argument("--per-frame", action="store_true", help="binary: every frame stops on its own flag (the reference rule with Num_Frames_OneTime = 1)")
-    ap.add_argument("--qam", type=int, default=2, choices=[2, 64], help="nb: n_QAM (define.h:25): 2 = BPSK, 64 = Constellation/GRAY_64QAM.txt, one point per GF(64) symbol")
+    ap.add_argument("--qam", type=int, default=2, choices=[2, 64, 256],
+                    help="nb: n_QAM (define.h:25): 2 = BPSK, q = Constellation/GRAY_<q>QAM.txt, one point per GF(q) symbol")
+    ap.add_argument("--nb-matrix", default="BDS.576.288.GF.64.txt", help="nb: matrix file (under data/nb or a path); q from its header")
     ap.add_argument("--method", type=int, default=0, choices=[0, 1, 2, 3], help="NB decoder_method (define.h:37): 0 EMS, 1 TMM, 2 log-QSPA, 3 layered TMM")
     ap.add_argument("--device-channel", action="store_true", help="generate the AWGN samples on the GPU (same RNG draws, device libm)")
-    ap.add_argument("--pn-message", action="store_true", help="binary: send random codewords (PN_Message 1, define.cuh:26) instead of the all-zero word; needs --fixed")
-    ap.add_argument("--pn-seed", type=int, default=1, help="binary --pn-message: seed of the message stream (bldpc_encode_random)")
+    ap.add_argument("--pn-message", action="store_true", help="send random codewords (PN_Message 1, define.cuh:26); binary: needs --fixed")
+    ap.add_argument("--pn-seed", type=int, default=1, help="--pn-message: seed of the message stream (bldpc_encode_random / nbldpc_encode_random)")
     ap.add_argument("--as-written", action="store_true", help="decode on the reference's Transform_H table as written (SURVEY F3)")
     args = ap.parse_args()
-    if args.pn_message and (args.which != "binary" or not args.fixed or args.as_written):
+    if args.which == "binary" and args.pn_message and (not args.fixed or args.as_written):
         ap.error("--pn-message needs the binary sweep with --fixed (the decoders' early exit tests for the all-zero word) on a QC code")
+    nbd = os.path.join(ROOT, "data", "nb")
+    if args.which == "nb":
+        mpath = args.nb_matrix if os.path.exists(args.nb_matrix) else os.path.join(nbd, args.nb_matrix)
+        with open(mpath) as f:
+            nb_q = int(f.readline().split()[2])  # header "N M q" (Get_H, Simulation.cpp:355)
+        if not os.path.exists(os.path.join(nbd, "GF", "Arith.Table.GF.%d.txt" % nb_q)):
+            ap.error("no GF/Arith.Table.GF.%d.txt for the field of %s" % (nb_q, args.nb_matrix))
+        if args.qam != 2 and args.qam != nb_q:
+            ap.error("--qam %d needs a GF(%d) code (one constellation point per symbol); %s is over GF(%d)" % (args.qam, args.qam, args.nb_matrix, nb_q))
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -75,18 +86,24 @@ def main():
     else:
         from cuda_ldpc_amd import nbldpc as nb
         from cuda_ldpc_amd.nb_simulation import sweep
-        nbd = os.path.join(ROOT, "data", "nb")
-        mul, _, _ = nb.GFInitial(64, os.path.join(nbd, "GF", "Arith.Table.GF.64.txt"))
-        code = nb.NBCode(os.path.join(nbd, "BDS.576.288.GF.64.txt"), mul)
-        cw = np.loadtxt(os.path.join(nbd, "codeword_bds_gf64.txt"), dtype=np.int32)
-        con = None if args.qam == 2 else nb.Get_CONSTELLATION(os.path.join(nbd, "Constellation", "GRAY_64QAM.txt"), args.qam)
-        print("# BDS.576.288.GF.64 N=%d symbols GF(%d), %s, maxIT=%d, %s" % (code.N, code.q, ["EMS(2,2)", "trellis min-max", "log-QSPA = EMS(q,dc-1)", "layered trellis min-max"][args.method], args.iters or 20,
-              "BPSK" if args.qam == 2 else "%d-QAM (Gray), one point per symbol" % args.qam))
+        mul, _, _ = nb.GFInitial(nb_q, os.path.join(nbd, "GF", "Arith.Table.GF.%d.txt" % nb_q))
+        code = nb.NBCode(mpath, mul)
+        bds = os.path.basename(mpath) == "BDS.576.288.GF.64.txt"
+        # the one shipped codeword belongs to the BDS code; every other matrix sends the all-zero word unless --pn-message
+        cw = np.loadtxt(os.path.join(nbd, "codeword_bds_gf64.txt"), dtype=np.int32) if bds else np.zeros(code.N, np.int32)
+        con = None if args.qam == 2 else nb.Get_CONSTELLATION(os.path.join(nbd, "Constellation", "GRAY_%dQAM.txt" % args.qam), args.qam)
+        if args.pn_message:
+            words = ", random codewords (PN seed %d, K'=%d)" % (args.pn_seed, code.K_info)
+        else:
+            words = "" if bds else ", all-zero codeword"
+        print("# %s N=%d symbols GF(%d), %s, maxIT=%d, %s%s" % (os.path.basename(mpath).replace(".txt", ""), code.N, code.q,
+              ["EMS(2,2)", "trellis min-max", "log-QSPA = EMS(q,dc-1)", "layered trellis min-max"][args.method], args.iters or 20,
+              "BPSK" if args.qam == 2 else "%d-QAM (Gray), one point per symbol" % args.qam, words))
         print("# SNR      NTF   NEF         FER         BER  AverIT")
         nbatch = args.batch if args.device_channel else min(args.batch, 1024)  # the host channel is serial: keep its batches small
         sweep(code, cw, args.start, args.stop, args.step, maxIT=args.iters or 20, batch=nbatch,
               max_frames=None if args.max_batches is None else args.max_batches * nbatch, device_channel=args.device_channel,
-              decoder_method=args.method, n_QAM=args.qam, CONSTELLATION=con)
+              decoder_method=args.method, n_QAM=args.qam, CONSTELLATION=con, PN_Message=1 if args.pn_message else 0, pn_seed=args.pn_seed)
     if world > 1:
         dist.destroy_process_group()
 
