@@ -48,6 +48,9 @@ lib.bldpc_encoder_info.argtypes = [c_void_p, ctypes.POINTER(c_int), ctypes.POINT
 lib.bldpc_encode.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p]
 lib.bldpc_encode_random.argtypes = [c_void_p, ctypes.c_ulonglong, ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p]
 lib.bldpc_syndrome.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]
+lib.bldpc_decode_layered.argtypes = [c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
+lib.bldpc_decode_layered_host.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_int, c_int, c_int, c_void_p,
+                                          c_void_p, c_void_p]
 lib.bldpc_sigma.restype = ctypes.c_float
 lib.bldpc_sigma.argtypes = [ctypes.c_float, c_int, ctypes.c_float]
 

@@ -15,6 +15,7 @@ from ._lib import check, lib
 
 EXIT_FIXED, EXIT_BATCH_GLOBAL, EXIT_PER_FRAME = 0, 1, 2
 KERNEL_AUTO, KERNEL_TABLE, KERNEL_QC_LDS = 0, 1, 2
+STOP_PREFIX, STOP_SYNDROME = 0, 1  # stop rules of the layered decoder (bldpc.h)
 
 
 def _np_ptr(a):
@@ -311,6 +312,51 @@ def LDPC_Decoder_GPU(code, Channel_Out, max_iter=50, length=0, exit_mode=EXIT_BA
     check(lib.bldpc_decode(code._h, _dev_ptr(Channel_Out), F, max_iter, length, exit_mode, kernel, _dev_ptr(D), _dev_ptr(app),
                            _dev_ptr(hist), ctypes.byref(it), st), "LDPC_Decoder_GPU")
     return dict(D=D, iteraTime=it.value, app=app, flag_hist=hist)
+
+
+def LDPC_Decoder_Layered_GPU(code, Channel_Out, max_iter=25, alpha=1.0, length=0, exit_mode=EXIT_FIXED, stop_rule=STOP_PREFIX, D=None,
+                             want_app=False, stream=None):
+    """bldpc_decode_layered: row-layered normalised min-sum (semantics in include/bldpc.h), codes made from block shifts only.
+
+    Channel_Out: CUDA float32 tensor [N, F] (frame-fastest).  alpha in (0, 1] scales every check message (1.0 = plain min-sum).
+    stop_rule: STOP_PREFIX (first `length` bits zero, the flooding decoders' rule) or STOP_SYNDROME (H d = 0, any codeword);
+    it is what row N of D means and what EXIT_PER_FRAME tests.  EXIT_BATCH_GLOBAL is refused.
+    Returns dict(D=int32 [N+1, F], app=float32 [N, F] or None, iters=int32 [F]: iterations run by each frame)."""
+    if not (torch.is_tensor(Channel_Out) and Channel_Out.is_cuda and Channel_Out.dtype == torch.float32 and Channel_Out.is_contiguous()):
+        raise ValueError("Channel_Out must be a contiguous CUDA float32 tensor")
+    if Channel_Out.dim() != 2 or Channel_Out.shape[0] != code.N or Channel_Out.shape[1] <= 0:
+        raise ValueError("Channel_Out must be [N=%d, F]" % code.N)
+    F = int(Channel_Out.shape[1])
+    dev = Channel_Out.device
+    if D is None:
+        D = torch.empty((code.N + 1, F), dtype=torch.int32, device=dev)
+    else:
+        _check_D(D, code.N, F, dev)
+    app = torch.empty((code.N, F), dtype=torch.float32, device=dev) if want_app else None
+    iters = torch.empty(F, dtype=torch.int32, device=dev)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(dev)).cuda_stream)
+    check(lib.bldpc_decode_layered(code._h, _dev_ptr(Channel_Out), F, int(max_iter), ctypes.c_float(alpha), int(length), int(exit_mode),
+                                   int(stop_rule), _dev_ptr(D), _dev_ptr(app), _dev_ptr(iters), st), "LDPC_Decoder_Layered_GPU")
+    return dict(D=D, app=app, iters=iters)
+
+
+def layered_host(H, J, L, Z, y, max_iter=25, alpha=1.0, length=0, exit_mode=EXIT_FIXED, stop_rule=STOP_PREFIX, want_app=True):
+    """bldpc_decode_layered_host: the layered decoder on the host (no device), the statement of its semantics.  y: float32
+    [N, F] host array (frame-fastest).  Returns dict(D=int32 [N+1, F], app=float32 [N, F] or None, iters=int32 [F])."""
+    H = np.ascontiguousarray(H, np.int32)
+    if H.size != J * L:
+        raise ValueError("H must hold J*L shifts")
+    y = np.ascontiguousarray(y, np.float32)
+    N = L * Z
+    if y.ndim != 2 or y.shape[0] != N or y.shape[1] <= 0:
+        raise ValueError("y must be [N=%d, F]" % N)
+    F = y.shape[1]
+    D = np.zeros((N + 1, F), np.int32)
+    app = np.zeros((N, F), np.float32) if want_app else None
+    iters = np.zeros(F, np.int32)
+    check(lib.bldpc_decode_layered_host(J, L, Z, _np_ptr(H), _np_ptr(y), F, int(max_iter), ctypes.c_float(alpha), int(length), int(exit_mode),
+                                        int(stop_rule), _np_ptr(D), None if app is None else _np_ptr(app), _np_ptr(iters)), "layered_host")
+    return dict(D=D, app=app, iters=iters)
 
 
 def Decode_Statistic(code, Channel_Out, counters, max_iter=50, length=0, exit_mode=EXIT_BATCH_GLOBAL, kernel=KERNEL_AUTO, D=None, stream=None):

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "bldpc_encode.hpp"
+#include "bldpc_layered.hpp"
 #include "bldpc_qc_kernel.hpp"
 #include "bldpc_table_kernels.hpp"
 #include "common.hpp"
@@ -38,7 +39,13 @@ struct bldpc_code {
     unsigned ev_n = 0; // decode calls recorded since the last bldpc_kernel_ms_mean
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     EncState *enc = nullptr; // systematic encoder and syndrome tables (bldpc_encode.hip), built on first use
+    LayPlan *lay = nullptr;  // layered decoder: edge tables and its own scratch (bldpc_layered.hip), built on first use
 };
+
+LayView cldpc::lay_view(bldpc_code *c)
+{
+    return LayView{c->J, c->L, c->Z, c->N, c->M, c->K, c->has_qc ? c->H.data() : nullptr, &c->lay, &c->last_kernel};
+}
 
 CodeView cldpc::code_view(const bldpc_code *c)
 {
@@ -223,6 +230,7 @@ extern "C" int bldpc_code_destroy(bldpc_code *c)
     c->rq.release(); c->bad.release(); c->cnt.release(); c->bits.release(); c->yg.release(); c->errs.release(); c->itw.release();
     qc_plan_release(&c->qc);
     enc_state_free(c->enc);
+    lay_plan_free(c->lay);
     for (hipEvent_t e : c->evr)
         if (e) (void)hipEventDestroy(e);
     delete c;

@@ -11,23 +11,41 @@ import torch
 
 from . import sharding
 from ._lib import check, lib
-from .bldpc import (EXIT_BATCH_GLOBAL, EXIT_FIXED, KERNEL_AUTO, AWGNChannel_CPU, AWGNChannel_GPU, Decode_Statistic, LDPC_Decoder_GPU,
-                    PN_CodeWords, SimCounters, Syndrome, _dev_ptr, sigma_of)
+from .bldpc import (EXIT_BATCH_GLOBAL, EXIT_FIXED, EXIT_PER_FRAME, KERNEL_AUTO, STOP_PREFIX, STOP_SYNDROME, AWGNChannel_CPU, AWGNChannel_GPU,
+                    Decode_Statistic, LDPC_Decoder_GPU, LDPC_Decoder_Layered_GPU, PN_CodeWords, SimCounters, Syndrome, _dev_ptr, sigma_of)
 
 
 def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, exit_mode=EXIT_BATCH_GLOBAL, kernel=KERNEL_AUTO,
                    leastErrorFrames=50, leastTestFrames=10000, displayStep=40960, dist=None, device=None, max_batches=None,
-                   log=print, device_channel=False, PN_Message=0, pn_seed=0):
+                   log=print, device_channel=False, PN_Message=0, pn_seed=0, schedule="flooding", alpha=1.0, stop_rule=None):
     """One SNR point (Simulation.cu:12-171).  `seed` (int32[3]) is the AWGN->seed state, advanced in place by the
     WHOLE batch on every rank so that all ranks stay on the reference's single noise stream.
 
     PN_Message=1 fills the reference's empty branch (Simulation.cu:107, define.cuh:26): every batch sends random
     codewords (bldpc_encode_random with stream `pn_seed`; frame b*F + i of the point is the same codeword at any world
     size), decodes them with a fixed iteration count, replaces the flag row of D by the syndrome check and counts errors
-    against the sent CodeWord.  The decoders' early exit assumes the zero word, so PN_Message=1 needs EXIT_FIXED."""
+    against the sent CodeWord.  The flooding decoders' early exit assumes the zero word, so PN_Message=1 needs EXIT_FIXED there.
+
+    schedule="layered" decodes with LDPC_Decoder_Layered_GPU (normalisation factor `alpha`; EXIT_FIXED or EXIT_PER_FRAME, `kernel`
+    is not used).  stop_rule defaults to STOP_SYNDROME with PN_Message=1 and to STOP_PREFIX otherwise; with STOP_SYNDROME the flag
+    row already means "valid codeword", so random codewords run with EXIT_PER_FRAME and no separate Syndrome call."""
     if PN_Message not in (0, 1):
         raise ValueError("PN_Message must be 0 (all-zero codeword) or 1 (random codewords)")
-    if PN_Message == 1 and exit_mode != EXIT_FIXED:
+    if schedule not in ("flooding", "layered"):
+        raise ValueError("schedule must be 'flooding' or 'layered'")
+    layered = schedule == "layered"
+    if not layered and (alpha != 1.0 or stop_rule is not None):
+        raise ValueError("alpha and stop_rule belong to schedule='layered'")
+    if layered:
+        if stop_rule is None:
+            stop_rule = STOP_SYNDROME if PN_Message else STOP_PREFIX
+        if stop_rule not in (STOP_PREFIX, STOP_SYNDROME):
+            raise ValueError("stop_rule must be STOP_PREFIX or STOP_SYNDROME")
+        if exit_mode not in (EXIT_FIXED, EXIT_PER_FRAME):
+            raise ValueError("schedule='layered' takes EXIT_FIXED or EXIT_PER_FRAME")
+        if PN_Message == 1 and stop_rule != STOP_SYNDROME and exit_mode != EXIT_FIXED:
+            raise ValueError("PN_Message=1 with per-frame exit needs stop_rule=STOP_SYNDROME: STOP_PREFIX tests for the all-zero word")
+    elif PN_Message == 1 and exit_mode != EXIT_FIXED:
         raise ValueError("PN_Message=1 needs exit_mode=EXIT_FIXED: the decoders' early exit tests for the all-zero word")
     rank = dist.get_rank() if dist is not None and dist.is_initialized() else 0
     world = dist.get_world_size() if dist is not None and dist.is_initialized() else 1
@@ -51,7 +69,14 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
             yd = torch.from_numpy(AWGNChannel_CPU(my_seed, sigma, code.N, count, CodeWord=None if cw is None else cw.cpu().numpy())).to(device)
         seed[:] = sharding.lcg_jump(seed, F * per_frame)
         dev_cnt.zero_()
-        if count and PN_Message:
+        if count and layered:
+            r = LDPC_Decoder_Layered_GPU(code, yd, max_iter=maxIT, alpha=alpha, length=length, exit_mode=exit_mode, stop_rule=stop_rule, D=D)
+            if PN_Message and stop_rule != STOP_SYNDROME:
+                Syndrome(code, D, into_flag_row=True)
+            st = torch.cuda.current_stream(device).cuda_stream
+            check(lib.bldpc_statistic_per_frame(code._h, _dev_ptr(D), _dev_ptr(cw), count, length, _dev_ptr(r["iters"]), _dev_ptr(dev_cnt), st),
+                  "Statistic")
+        elif count and PN_Message:
             r = LDPC_Decoder_GPU(code, yd, max_iter=maxIT, length=length, exit_mode=EXIT_FIXED, kernel=kernel, D=D)
             Syndrome(code, D, into_flag_row=True)  # flag row: "valid codeword" instead of "first `length` bits zero"
             st = torch.cuda.current_stream(device).cuda_stream

@@ -210,6 +210,50 @@ int bldpc_encode_random(bldpc_code *code, unsigned long long seed, long long fir
  * Asynchronous on `stream`. */
 int bldpc_syndrome(const bldpc_code *code, const int *D, int F, int *flag, int *unsat, void *stream);
 
+/* -- row-layered normalised min-sum (not in the reference, which only floods) ------------------------------------ */
+
+/* stop rules of bldpc_decode_layered: what the flag row of D means and what the per-frame exit tests */
+#define BLDPC_STOP_PREFIX 0   /* the first `length` hard bits are all zero (the rule of bldpc_decode; all-zero codeword only) */
+#define BLDPC_STOP_SYNDROME 1 /* H * d = 0, the rule of bldpc_syndrome: valid for any sent codeword                        */
+
+/* Layered ("turbo decoding message passing") normalised min-sum for codes made by bldpc_code_create_qc: every block row
+ * of the QC matrix is a layer whose Z checks touch disjoint variables.  Semantics, IEEE fp32 without fused multiply-add:
+ *
+ *   state per frame: S[N] = Channel_Out (a-posteriori values), R = +0.0f per edge.
+ *   one iteration visits the layers j = 0 .. J-1 in order; in layer j, for every t in 0 .. Z-1 (independent of each other),
+ *   with the non-zero blocks of block row j in ascending block column l_0 < ... < l_{w-1}, shifts s_i,
+ *   v_i = l_i*Z + (t + s_i) mod Z:
+ *     1. Q_i = S[v_i] - R_i
+ *     2. sg_i = sign BIT of Q_i;  P = XOR of all sg_i;  a_i = |Q_i|;  m1 <= m2 the two smallest a_i with multiplicity;
+ *        first = lowest i with a_i == m1
+ *     3. mag_i = alpha * (i == first ? m2 : m1)   (one fp32 multiplication; alpha = 1.0f is plain min-sum)
+ *        R_i' = (P xor sg_i) ? -mag_i : +mag_i
+ *     4. S[v_i] = Q_i + R_i';  R_i' replaces R_i
+ *   after each iteration the hard bits are d[v] = S[v] < 0 and the frame's flag is, by stop_rule, BLDPC_STOP_PREFIX
+ *   (length = 0 means K = N - M) or BLDPC_STOP_SYNDROME.
+ *
+ *   exit_mode  BLDPC_EXIT_FIXED: exactly max_iter iterations.  BLDPC_EXIT_PER_FRAME: frame f stops after the first iteration
+ *              at which its flag is set (else after max_iter); column f of D and app hold that iteration's outputs and
+ *              iters[f] its number -- what a fixed run of iters[f] iterations on that frame alone returns.
+ *              BLDPC_EXIT_BATCH_GLOBAL is a property of the reference's flooding driver and is refused (BLDPC_EINVAL).
+ *   alpha      normalisation factor in (0, 1]
+ *   D          device int32 [N+1][F] (out): hard bits, row N = the flag under stop_rule, in both exit modes
+ *   app        optional device float [N][F] (out): S;  iters: device int32 [F] (out), NULL allowed with BLDPC_EXIT_FIXED
+ * Refused: codes built from an address table and block rows of weight < 2 (BLDPC_EUNSUPPORTED); max_iter < 1, alpha outside
+ * (0, 1] or not finite, an unknown rule or mode, iters == NULL with per-frame exit (BLDPC_EINVAL).  NaN inputs are undefined.
+ * Asynchronous on `stream` in both exit modes; no allocation per call once the code object's scratch has grown (the layered
+ * decoder keeps scratch of its own, apart from the flooding decoders').  bldpc_last_kernel names the tier that ran:
+ * "k_lay_reg" / "k_lay" (all iterations on-chip: S in LDS, row states in registers / in LDS) or "k_lay_ws" (S and row states
+ * in a device workspace: codes whose state exceeds the LDS). */
+int bldpc_decode_layered(bldpc_code *code, const float *Channel_Out, int F, int max_iter, float alpha, int length, int exit_mode,
+                         int stop_rule, int *D, float *app, int *iters, void *stream);
+
+/* The same decoder on the host, all pointers host, no device needed: plain C++ that follows the steps above literally (one
+ * R per edge), frames over at most 16 threads.  It is the statement of the semantics inside the product, as
+ * bldpc_generator_host is for the encoder, and what the device kernels are tested against bit for bit.  NOT a fast path. */
+int bldpc_decode_layered_host(int J, int L, int Z, const int *H, const float *Channel_Out, int F, int max_iter, float alpha,
+                              int length, int exit_mode, int stop_rule, int *D, float *app, int *iters);
+
 /* sigma of the sweep point (main.cu:120-127): snrtype 0 = Eb/N0 (uses rate), 1 = Es/N0. */
 float bldpc_sigma(float SNR, int snrtype, float rate);
 
@@ -223,7 +267,7 @@ int bldpc_last_kernel_ms(bldpc_code *code, float *ms);
  * profiled call records its own event pair, nothing synchronises until this function is called.  *launches = calls averaged. */
 int bldpc_kernel_ms_mean(bldpc_code *code, float *mean_ms, int *launches);
 
-/* Name of the kernel variant the last bldpc_decode on this code used (static string). */
+/* Name of the kernel variant the last bldpc_decode / bldpc_decode_layered on this code used (static string). */
 const char *bldpc_last_kernel(const bldpc_code *code);
 
 const char *bldpc_last_error(void);

@@ -42,9 +42,20 @@ def main():
     ap.add_argument("--device-channel", action="store_true", help="generate the AWGN samples on the GPU (same RNG draws, device libm)")
     ap.add_argument("--pn-message", action="store_true", help="send random codewords (PN_Message 1, define.cuh:26); binary: needs --fixed")
     ap.add_argument("--pn-seed", type=int, default=1, help="--pn-message: seed of the message stream (bldpc_encode_random / nbldpc_encode_random)")
+    ap.add_argument("--layered", action="store_true", help="binary: row-layered normalised min-sum (bldpc_decode_layered); with --fixed or --per-frame")
+    ap.add_argument("--alpha", type=float, default=1.0, help="--layered: normalisation factor in (0, 1]")
+    ap.add_argument("--stop-rule", choices=["prefix", "syndrome"], default=None,
+                    help="--layered: stop rule / meaning of the flag row (default: syndrome with --pn-message, else prefix)")
     ap.add_argument("--as-written", action="store_true", help="decode on the reference's Transform_H table as written (SURVEY F3)")
     args = ap.parse_args()
-    if args.which == "binary" and args.pn_message and (not args.fixed or args.as_written):
+    if args.which == "binary" and args.layered:
+        if args.as_written or not (args.fixed or args.per_frame):
+            ap.error("--layered needs a QC code and --fixed or --per-frame")
+        if args.pn_message and args.per_frame and args.stop_rule == "prefix":
+            ap.error("--pn-message --per-frame needs --stop-rule syndrome (the prefix rule tests for the all-zero word)")
+    elif args.alpha != 1.0 or args.stop_rule is not None:
+        ap.error("--alpha and --stop-rule belong to the binary sweep with --layered")
+    elif args.which == "binary" and args.pn_message and (not args.fixed or args.as_written):
         ap.error("--pn-message needs the binary sweep with --fixed (the decoders' early exit tests for the all-zero word) on a QC code")
     nbd = os.path.join(ROOT, "data", "nb")
     if args.which == "nb":
@@ -74,15 +85,20 @@ def main():
             code = C.BinaryCode.from_table(args.J, args.L, args.Z, wc, wv, C.Transform_H(H, args.J, args.L, args.Z, wc, wv, as_written=True))
         else:
             code = C.BinaryCode.from_blockh(args.matrix, args.J, args.L, args.Z)
+        lay = {}
+        if args.layered:
+            stop = args.stop_rule or ("syndrome" if args.pn_message else "prefix")
+            lay = dict(schedule="layered", alpha=args.alpha, stop_rule=C.STOP_SYNDROME if stop == "syndrome" else C.STOP_PREFIX)
         if rank == 0:
-            print("# %s N=%d K=%d, %s, maxIT=%d, batch=%d x %d GPU(s)%s" % (os.path.basename(args.matrix), code.N, code.K,
+            print("# %s N=%d K=%d, %s%s, maxIT=%d, batch=%d x %d GPU(s)%s" % (os.path.basename(args.matrix), code.N, code.K,
+                  "layered min-sum alpha=%g stop=%s, " % (args.alpha, stop) if args.layered else "",
                   "fixed iterations" if args.fixed else ("per-frame early exit" if args.per_frame else "batch-global early exit"),
-                  args.iters or 50, args.batch, world,
+                  args.iters or (25 if args.layered else 50), args.batch, world,
                   ", random codewords (PN seed %d, K'=%d), syndrome flag" % (args.pn_seed, code.K_info) if args.pn_message else ""))
             print("# SNR      NTF   NEF         FER         BER  AverIT       FER_F      FER_A")
-        sweep(code, args.start, args.stop, args.step, snrtype=1, dist=dist, Num_Frames_OneTime=args.batch, maxIT=args.iters or 50,
+        sweep(code, args.start, args.stop, args.step, snrtype=1, dist=dist, Num_Frames_OneTime=args.batch, maxIT=args.iters or (25 if args.layered else 50),
               exit_mode=C.EXIT_FIXED if args.fixed else (C.EXIT_PER_FRAME if args.per_frame else C.EXIT_BATCH_GLOBAL), max_batches=args.max_batches, displayStep=10 ** 12, device_channel=args.device_channel,
-              PN_Message=1 if args.pn_message else 0, pn_seed=args.pn_seed, log=print if rank == 0 else None)
+              PN_Message=1 if args.pn_message else 0, pn_seed=args.pn_seed, log=print if rank == 0 else None, **lay)
     else:
         from cuda_ldpc_amd import nbldpc as nb
         from cuda_ldpc_amd.nb_simulation import sweep
