@@ -239,12 +239,14 @@ int bldpc_syndrome(const bldpc_code *code, const int *D, int F, int *flag, int *
  *   alpha      normalisation factor in (0, 1]
  *   D          device int32 [N+1][F] (out): hard bits, row N = the flag under stop_rule, in both exit modes
  *   app        optional device float [N][F] (out): S;  iters: device int32 [F] (out), NULL allowed with BLDPC_EXIT_FIXED
- * Refused: codes built from an address table and block rows of weight < 2 (BLDPC_EUNSUPPORTED); max_iter < 1, alpha outside
- * (0, 1] or not finite, an unknown rule or mode, iters == NULL with per-frame exit (BLDPC_EINVAL).  NaN inputs are undefined.
+ * Refused: codes built from an address table, block rows of weight < 2 and block rows of weight > 26 (BLDPC_EUNSUPPORTED; 26
+ * is also the most bldpc_code_create_qc takes, which refuses a heavier matrix with the same code before a code object exists);
+ * max_iter < 1, alpha outside (0, 1] or not finite, length outside [0, N], an unknown rule or mode, iters == NULL with
+ * per-frame exit (BLDPC_EINVAL).  bldpc_decode_layered_host has no upper weight limit.  NaN inputs are undefined.
  * Asynchronous on `stream` in both exit modes; no allocation per call once the code object's scratch has grown (the layered
  * decoder keeps scratch of its own, apart from the flooding decoders').  bldpc_last_kernel names the tier that ran:
  * "k_lay_reg" / "k_lay" (all iterations on-chip: S in LDS, row states in registers / in LDS) or "k_lay_ws" (S and row states
- * in a device workspace: codes whose state exceeds the LDS). */
+ * in a device workspace: codes whose state exceeds the LDS, whose Z exceeds 1024 or whose N is not a multiple of 64). */
 int bldpc_decode_layered(bldpc_code *code, const float *Channel_Out, int F, int max_iter, float alpha, int length, int exit_mode,
                          int stop_rule, int *D, float *app, int *iters, void *stream);
 
