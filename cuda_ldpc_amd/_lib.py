@@ -51,6 +51,10 @@ lib.bldpc_syndrome.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_
 lib.bldpc_decode_layered.argtypes = [c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
 lib.bldpc_decode_layered_host.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_int, c_int, c_int, c_void_p,
                                           c_void_p, c_void_p]
+lib.bldpc_qam_map.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
+lib.bldpc_qam_demap.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_float, c_int, c_int, c_void_p, c_void_p]
+lib.bldpc_qam_map_host.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p]
+lib.bldpc_qam_demap_host.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_float, c_int, c_int, c_void_p]
 lib.bldpc_sigma.restype = ctypes.c_float
 lib.bldpc_sigma.argtypes = [ctypes.c_float, c_int, ctypes.c_float]
 

@@ -11,7 +11,8 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
-from ._lib import check, lib
+from ._lib import LdpcError, check, lib
+from .nbldpc import Get_CONSTELLATION  # noqa: F401  -- the constellation files serve both code families
 
 EXIT_FIXED, EXIT_BATCH_GLOBAL, EXIT_PER_FRAME = 0, 1, 2
 KERNEL_AUTO, KERNEL_TABLE, KERNEL_QC_LDS = 0, 1, 2
@@ -357,6 +358,112 @@ def layered_host(H, J, L, Z, y, max_iter=25, alpha=1.0, length=0, exit_mode=EXIT
     check(lib.bldpc_decode_layered_host(J, L, Z, _np_ptr(H), _np_ptr(y), F, int(max_iter), ctypes.c_float(alpha), int(length), int(exit_mode),
                                         int(stop_rule), _np_ptr(D), None if app is None else _np_ptr(app), _np_ptr(iters)), "layered_host")
     return dict(D=D, app=app, iters=iters)
+
+
+def _qam_bits(q):
+    """log2 q for a constellation size the modem takes (a power of two in 2..256)."""
+    q = int(q)
+    if q < 2 or q > 256 or q & (q - 1):
+        raise ValueError("the constellation must hold a power of two of points in 2..256, not %d" % q)
+    return q.bit_length() - 1
+
+
+def _check_con(constellation, dev=None):
+    """constellation [q, 2] float32: a contiguous CUDA tensor on `dev`, or (dev None) anything numpy reads.  Returns (tensor or array, m)."""
+    if dev is None:
+        con = np.ascontiguousarray(constellation, np.float32)
+        if con.ndim != 2 or con.shape[1] != 2:
+            raise ValueError("constellation must be float32 [q, 2]")
+        return con, _qam_bits(con.shape[0])
+    if not (torch.is_tensor(constellation) and constellation.is_cuda and constellation.device == dev and constellation.dtype == torch.float32
+            and constellation.is_contiguous() and constellation.dim() == 2 and constellation.shape[1] == 2):
+        raise ValueError("constellation must be a contiguous CUDA float32 tensor [q, 2] on %s" % dev)
+    return constellation, _qam_bits(constellation.shape[0])
+
+
+def Modulate_QAM(CodeWord, N, m, F=None, device=None, stream=None):
+    """bldpc_qam_map: CodeWord CUDA int32 [N, F] (frame-fastest) -> constellation indices sym int32 [F, Ns], Ns = ceil(N / m); bit b
+    of sym[f, s] is codeword bit s*m + b, pad bits 0 (include/bldpc.h).  CodeWord=None sends the all-zero word and needs F."""
+    if not 1 <= int(m) <= 8:
+        raise ValueError("m must be in 1..8")
+    if CodeWord is None:
+        if F is None or F <= 0 or N <= 0:
+            raise ValueError("CodeWord=None (the all-zero word) needs positive N and F")
+        device = device or torch.device("cuda", torch.cuda.current_device())
+    else:
+        if not (torch.is_tensor(CodeWord) and CodeWord.dim() == 2 and CodeWord.shape[0] == N and CodeWord.shape[1] > 0):
+            raise ValueError("CodeWord must be [N=%d, F]" % N)
+        F, device = int(CodeWord.shape[1]), CodeWord.device
+        _check_cw(CodeWord, N, F, device)
+    sym = torch.empty((F, (N + m - 1) // m), dtype=torch.int32, device=device)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(device)).cuda_stream)
+    check(lib.bldpc_qam_map(_dev_ptr(CodeWord), N, F, int(m), _dev_ptr(sym), st), "Modulate_QAM")
+    return sym
+
+
+def AWGNChannel_QAM_GPU(seed, sigma, sym, constellation, stream=None):
+    """The per-frame QAM channel of the GF(q) half (nbldpc_awgn_channel_device_qam_frames) on the indices Modulate_QAM made:
+    sym CUDA int32 [F, Ns], constellation CUDA float32 [q, 2] -> rx CUDA float32 [F, Ns, 2].  Four RandomModule draws per symbol;
+    seed (int32[3]) is advanced by 4 * Ns * F draws."""
+    if not (isinstance(seed, np.ndarray) and seed.dtype == np.int32 and seed.size == 3):
+        raise ValueError("seed must be an int32 numpy array of 3")
+    if not (torch.is_tensor(sym) and sym.is_cuda and sym.dtype == torch.int32 and sym.is_contiguous() and sym.dim() == 2 and sym.numel() > 0):
+        raise ValueError("sym must be a contiguous CUDA int32 tensor [F, Ns]")
+    con, _ = _check_con(constellation, sym.device)
+    F, Ns = (int(x) for x in sym.shape)
+    rx = torch.empty((F, Ns, 2), dtype=torch.float32, device=sym.device)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(sym.device)).cuda_stream)
+    rc = lib.nbldpc_awgn_channel_device_qam_frames(_np_ptr(seed), ctypes.c_float(sigma), _dev_ptr(sym), Ns, _dev_ptr(con), int(con.shape[0]), F,
+                                                   _dev_ptr(rx), st)
+    if rc != 0:
+        raise LdpcError("AWGNChannel_QAM_GPU failed (%d): %s" % (rc, lib.nbldpc_last_error().decode(errors="replace")))
+    return rx
+
+
+def Demodulate_QAM(rx, constellation, scale, N, stream=None):
+    """bldpc_qam_demap: max-log soft values of the N codeword bits of every frame.  rx CUDA float32 [F, Ns, 2] with
+    Ns = ceil(N / log2 q), constellation CUDA float32 [q, 2] -> Channel_Out CUDA float32 [N, F] (frame-fastest, positive = bit 0),
+    (m1 - m0) * scale: scale = 1 / (2 sigma^2) for LLRs, 1.0 is as good for the min-sum decoders."""
+    if not (torch.is_tensor(rx) and rx.is_cuda and rx.dtype == torch.float32 and rx.is_contiguous() and rx.dim() == 3 and rx.shape[2] == 2):
+        raise ValueError("rx must be a contiguous CUDA float32 tensor [F, Ns, 2]")
+    con, m = _check_con(constellation, rx.device)
+    F = int(rx.shape[0])
+    if N <= 0 or F <= 0 or rx.shape[1] != (N + m - 1) // m:
+        raise ValueError("rx must hold ceil(N / m) = %d symbols per frame, not %d" % ((N + m - 1) // m, rx.shape[1]))
+    out = torch.empty((N, F), dtype=torch.float32, device=rx.device)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(rx.device)).cuda_stream)
+    check(lib.bldpc_qam_demap(_dev_ptr(rx), _dev_ptr(con), int(con.shape[0]), ctypes.c_float(scale), N, F, _dev_ptr(out), st), "Demodulate_QAM")
+    return out
+
+
+def Modulate_QAM_host(CodeWord, N, m, F=None):
+    """bldpc_qam_map_host: Modulate_QAM on host arrays, no device needed (the statement of the semantics).  -> int32 [F, Ns]."""
+    if not 1 <= int(m) <= 8:
+        raise ValueError("m must be in 1..8")
+    if CodeWord is None:
+        if F is None or F <= 0 or N <= 0:
+            raise ValueError("CodeWord=None (the all-zero word) needs positive N and F")
+        cw = None
+    else:
+        cw = np.ascontiguousarray(CodeWord, np.int32)
+        if cw.ndim != 2 or cw.shape[0] != N or cw.shape[1] <= 0:
+            raise ValueError("CodeWord must be [N=%d, F]" % N)
+        F = cw.shape[1]
+    sym = np.empty((F, (N + m - 1) // m), np.int32)
+    check(lib.bldpc_qam_map_host(None if cw is None else _np_ptr(cw), N, F, int(m), _np_ptr(sym)), "Modulate_QAM_host")
+    return sym
+
+
+def Demodulate_QAM_host(rx, constellation, scale, N):
+    """bldpc_qam_demap_host: Demodulate_QAM on host arrays, no device needed.  rx float32 [F, Ns, 2] -> float32 [N, F]."""
+    con, m = _check_con(constellation)
+    rx = np.ascontiguousarray(rx, np.float32)
+    if N <= 0 or rx.ndim != 3 or rx.shape[0] <= 0 or rx.shape[1] != (N + m - 1) // m or rx.shape[2] != 2:
+        raise ValueError("rx must be float32 [F, ceil(N / m) = %d, 2]" % ((N + m - 1) // m))
+    F = rx.shape[0]
+    out = np.empty((N, F), np.float32)
+    check(lib.bldpc_qam_demap_host(_np_ptr(rx), _np_ptr(con), con.shape[0], ctypes.c_float(scale), N, F, _np_ptr(out)), "Demodulate_QAM_host")
+    return out
 
 
 def Decode_Statistic(code, Channel_Out, counters, max_iter=50, length=0, exit_mode=EXIT_BATCH_GLOBAL, kernel=KERNEL_AUTO, D=None, stream=None):

@@ -37,6 +37,10 @@ def nb_draws_per_frame(N, m):
     return 4 * N * m  # Real and Image part, two draws each (LDPC_Encoder.cpp:57-66)
 
 
+def qam_draws_per_frame(N, m):
+    return 4 * ((N + m - 1) // m)  # a binary codeword over 2^m-QAM: ceil(N/m) symbols, Real and Image part, two draws each
+
+
 def allreduce_counters(counters, dist=None):
     """Sum an int64 counter tensor over all ranks (no-op without a process group). Returns the tensor.
     A caller that passes an initialised process group gets the collective at every world size, 1 included (40 bytes: the

@@ -12,12 +12,15 @@ import torch
 from . import sharding
 from ._lib import check, lib
 from .bldpc import (EXIT_BATCH_GLOBAL, EXIT_FIXED, EXIT_PER_FRAME, KERNEL_AUTO, STOP_PREFIX, STOP_SYNDROME, AWGNChannel_CPU, AWGNChannel_GPU,
-                    Decode_Statistic, LDPC_Decoder_GPU, LDPC_Decoder_Layered_GPU, PN_CodeWords, SimCounters, Syndrome, _dev_ptr, sigma_of)
+                    AWGNChannel_QAM_GPU, Decode_Statistic, Demodulate_QAM, LDPC_Decoder_GPU, LDPC_Decoder_Layered_GPU, Modulate_QAM, PN_CodeWords,
+                    SimCounters, Syndrome, _dev_ptr, sigma_of)
+from .nbldpc import sigma_of as nb_sigma_of
 
 
 def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, exit_mode=EXIT_BATCH_GLOBAL, kernel=KERNEL_AUTO,
                    leastErrorFrames=50, leastTestFrames=10000, displayStep=40960, dist=None, device=None, max_batches=None,
-                   log=print, device_channel=False, PN_Message=0, pn_seed=0, schedule="flooding", alpha=1.0, stop_rule=None):
+                   log=print, device_channel=False, PN_Message=0, pn_seed=0, schedule="flooding", alpha=1.0, stop_rule=None,
+                   n_QAM=2, CONSTELLATION=None):
     """One SNR point (Simulation.cu:12-171).  `seed` (int32[3]) is the AWGN->seed state, advanced in place by the
     WHOLE batch on every rank so that all ranks stay on the reference's single noise stream.
 
@@ -28,7 +31,12 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
 
     schedule="layered" decodes with LDPC_Decoder_Layered_GPU (normalisation factor `alpha`; EXIT_FIXED or EXIT_PER_FRAME, `kernel`
     is not used).  stop_rule defaults to STOP_SYNDROME with PN_Message=1 and to STOP_PREFIX otherwise; with STOP_SYNDROME the flag
-    row already means "valid codeword", so random codewords run with EXIT_PER_FRAME and no separate Syndrome call."""
+    row already means "valid codeword", so random codewords run with EXIT_PER_FRAME and no separate Syndrome call.
+
+    n_QAM != 2 sends the codewords over n_QAM-QAM instead of BPSK: CONSTELLATION (host float32 [n_QAM, 2], Get_CONSTELLATION) labels
+    log2(n_QAM) consecutive codeword bits per point; a batch is encode -> Modulate_QAM -> AWGNChannel_QAM_GPU (four draws per symbol
+    of the same noise stream) -> Demodulate_QAM with scale 1 / (2 sigma^2) -> the chosen decoder, and the caller passes the sigma of
+    that n_QAM (nbldpc.sigma_of).  Needs PN_Message=1 (a QAM channel is not symmetric) and device_channel=True."""
     if PN_Message not in (0, 1):
         raise ValueError("PN_Message must be 0 (all-zero codeword) or 1 (random codewords)")
     if schedule not in ("flooding", "layered"):
@@ -47,12 +55,29 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
             raise ValueError("PN_Message=1 with per-frame exit needs stop_rule=STOP_SYNDROME: STOP_PREFIX tests for the all-zero word")
     elif PN_Message == 1 and exit_mode != EXIT_FIXED:
         raise ValueError("PN_Message=1 needs exit_mode=EXIT_FIXED: the decoders' early exit tests for the all-zero word")
+    qam_m = 0
+    if n_QAM != 2:  # every refusal before anything touches the device
+        if PN_Message != 1:
+            raise ValueError("n_QAM=%r needs PN_Message=1: a QAM channel is not symmetric in the bits, so the all-zero word (always the "
+                             "same constellation point) is not representative of a random codeword" % (n_QAM,))
+        if not device_channel:
+            raise ValueError("n_QAM != 2 needs device_channel=True: there is no host QAM channel on this path")
+        if CONSTELLATION is None:
+            raise ValueError("n_QAM=%r needs CONSTELLATION (float32 [n_QAM, 2], Get_CONSTELLATION)" % (n_QAM,))
+        con = np.ascontiguousarray(CONSTELLATION, np.float32)
+        if not isinstance(n_QAM, (int, np.integer)) or n_QAM < 2 or n_QAM > 256 or n_QAM & (n_QAM - 1) or con.shape != (n_QAM, 2):
+            raise ValueError("CONSTELLATION must be float32 [n_QAM, 2] with n_QAM a power of two in 2..256, not %s for n_QAM=%r"
+                             % (con.shape, n_QAM))
+        qam_m = int(n_QAM).bit_length() - 1
+    elif CONSTELLATION is not None:
+        raise ValueError("CONSTELLATION belongs to n_QAM != 2")
     rank = dist.get_rank() if dist is not None and dist.is_initialized() else 0
     world = dist.get_world_size() if dist is not None and dist.is_initialized() else 1
     device = device or torch.device("cuda", torch.cuda.current_device())
     F = Num_Frames_OneTime
     first, count = sharding.shard_frames(F, world, rank)
-    per_frame = sharding.binary_draws_per_frame(code.N)
+    per_frame = sharding.qam_draws_per_frame(code.N, qam_m) if qam_m else sharding.binary_draws_per_frame(code.N)
+    con_dev = torch.from_numpy(con).to(device) if qam_m else None
     dev_cnt = torch.zeros(5, dtype=torch.int64, device=device)
     D = torch.empty((code.N + 1, max(count, 1)), dtype=torch.int32, device=device)
     length = code.K  # Message_CW 0 (define.cuh:61)
@@ -63,6 +88,9 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
         cw = PN_CodeWords(code, pn_seed, count, first_frame=batches * F + first, device=device) if (PN_Message and count) else None
         if not count:
             yd = None
+        elif qam_m:  # bits -> points -> noisy points -> max-log LLRs, all on the device
+            rx = AWGNChannel_QAM_GPU(my_seed, sigma, Modulate_QAM(cw, code.N, qam_m), con_dev)
+            yd = Demodulate_QAM(rx, con_dev, 1.0 / (2.0 * sigma * sigma), code.N)
         elif device_channel:  # same draws, generated on the GPU (device libm in the Box-Muller transform)
             yd = AWGNChannel_GPU(my_seed, sigma, code.N, count, device=device, CodeWord=cw)
         else:
@@ -115,13 +143,18 @@ def snr_grid(startSNR=0.0, stopSNR=13.0, stepSNR=0.2):
     return pts
 
 
-def sweep(code, startSNR=0.0, stopSNR=13.0, stepSNR=0.2, snrtype=1, seeds=(173, 173, 173), dist=None, log=print, **kw):
-    """main.cu:114-160: returns the list of SimCounters, one per SNR point."""
+def sweep(code, startSNR=0.0, stopSNR=13.0, stepSNR=0.2, snrtype=1, seeds=(173, 173, 173), dist=None, log=print, n_QAM=2, **kw):
+    """main.cu:114-160: returns the list of SimCounters, one per SNR point.  With n_QAM != 2 (pass the constellation itself as
+    CONSTELLATION=...) the sigma of a point is the GF(q) program's, nbldpc_sigma(SNR, snrtype, n_QAM, rate), so that a binary and a
+    GF(q) sweep of the same rate, snrtype and n_QAM run at the same sigma at every SNR value."""
     out = []
+    if n_QAM != 2:
+        kw["n_QAM"] = n_QAM
     for snr in snr_grid(startSNR, stopSNR, stepSNR):
         seed = np.array(seeds, np.int32)  # reset at every point (main.cu:117-119)
         SIM = SimCounters()
         SIM.SNR = snr
-        Simulation_GPU(code, seed, sigma_of(snr, snrtype, code.K / code.N), SIM, dist=dist, log=log, **kw)
+        sigma = nb_sigma_of(snr, code.K / code.N, snrtype, n_QAM) if n_QAM != 2 else sigma_of(snr, snrtype, code.K / code.N)
+        Simulation_GPU(code, seed, sigma, SIM, dist=dist, log=log, **kw)
         out.append(SIM)
     return out

@@ -256,6 +256,53 @@ int bldpc_decode_layered(bldpc_code *code, const float *Channel_Out, int F, int 
 int bldpc_decode_layered_host(int J, int L, int Z, const int *H, const float *Channel_Out, int F, int max_iter, float alpha,
                               int length, int exit_mode, int stop_rule, int *D, float *app, int *iters);
 
+/* -- binary codes over QAM: bit mapper and max-log soft demapper (not in the reference, whose binary channel is BPSK) -- */
+
+/* Bit-interleaved coded modulation without the interleaver: m consecutive codeword bits label one of q = 2^m constellation
+ * points, 1 <= m <= 8.  Semantics:
+ *
+ *   constellation  float [q][2] (Real, Imag), as nbldpc_read_constellation returns it
+ *   Ns = ceil(N / m) symbols per frame.  Bit b (0 <= b < m) of symbol s is codeword bit n = s*m + b and is bit b of the point
+ *   index: idx = sum_b bit[s*m + b] << b (only bit 0 of a CodeWord entry is read, as in bldpc_encode).  This is the order in which
+ *   the GF(q) channels read a symbol's bits (nbldpc_awgn_channel_device[_qam]_frames); the shipped GRAY_*QAM.txt files are Gray in
+ *   these index bits.  Positions n >= N of the last symbol are pad bits: they are sent as 0, the demapper writes nothing for them
+ *   and makes no use of knowing them.  There is NO interleaver: neighbouring codeword bits share a symbol.
+ *
+ *   map:    sym[f][s] = idx, int32 [F][Ns] -- what nbldpc_awgn_channel_device_qam_frames takes as CodeWord_sym with its N := Ns.
+ *           CodeWord == NULL is the all-zero word: every index is 0.
+ *   demap:  max-log, IEEE fp32 without fused multiply-add.  For the received point (x, y) = rx[f][s] and every point p:
+ *             dx = x - cx_p;  dy = y - cy_p;  d_p = dx*dx + dy*dy         (two multiplications, one addition)
+ *           and for every bit b with s*m + b < N:
+ *             m0 = min{d_p : bit b of p is 0};  m1 = min{d_p : bit b of p is 1}
+ *             Channel_Out[(s*m + b)*F + f] = (m1 - m0) * scale             (one subtraction, one multiplication)
+ *           Positive means bit 0, as with the BPSK channel's y = 1 - 2c.  A minimum is a selection, so the order in which the
+ *           points are visited does not change the bits.  NaN inputs are undefined.
+ *   scale   caller-supplied fp32: 1 / (2 sigma^2) gives true (max-log) LLRs; 1.0f serves the min-sum decoders of this library
+ *           as well, which are scale-invariant (every message is a sum or a minimum of inputs, times alpha).
+ *
+ * The three calls of one batch over the QAM channel, on the reference's noise stream:
+ *     bldpc_qam_map(CodeWord, N, F, m, sym, stream);
+ *     nbldpc_awgn_channel_device_qam_frames(seed, sigma, sym, Ns, constellation, q, F, rx, stream);   // include/nbldpc.h: 4 draws per
+ *                                                                             // symbol, advances seed by 4*Ns*F draws
+ *     bldpc_qam_demap(rx, constellation, q, 1.0f / (2 * sigma * sigma), N, F, Channel_Out, stream);
+ * with sigma = nbldpc_sigma(SNR, snrtype, q, rate) (its quirks included), so that a binary and a GF(q) sweep at one SNR value run
+ * at the same sigma.
+ *
+ *   CodeWord     device int32 [N][F] or NULL     sym          device int32 [F][Ns]
+ *   rx           device float [F][Ns][2]         constellation device float [q][2]      Channel_Out  device float [N][F]
+ * Both calls are asynchronous on `stream` and allocate nothing.  BLDPC_EINVAL: a null pointer (but CodeWord), N or F <= 0, m
+ * outside 1..8, q not a power of two in 2..256, scale not finite.
+ * Out of scope: the exact log-sum-exp demapper (its expf / logf differ between device and host libm in the last ulp, which would end
+ * bit-exact testing for a small gain under Gray labelling), bit interleavers, iterative demapping. */
+int bldpc_qam_map(const int *CodeWord, int N, int F, int m, int *sym, void *stream);
+int bldpc_qam_demap(const float *rx, const float *constellation, int q, float scale, int N, int F, float *Channel_Out, void *stream);
+
+/* The same on host pointers, no device needed (and so no stream: they return when done): plain C++ that follows the steps above
+ * literally.  They are the statement of the semantics inside the product, as bldpc_decode_layered_host is for the layered decoder,
+ * and what the kernels are tested against bit for bit.  Same argument checks. */
+int bldpc_qam_map_host(const int *CodeWord, int N, int F, int m, int *sym);
+int bldpc_qam_demap_host(const float *rx, const float *constellation, int q, float scale, int N, int F, float *Channel_Out);
+
 /* sigma of the sweep point (main.cu:120-127): snrtype 0 = Eb/N0 (uses rate), 1 = Es/N0. */
 float bldpc_sigma(float SNR, int snrtype, float rate);
 

@@ -36,7 +36,8 @@ def main():
     ap.add_argument("--fixed", action="store_true", help="fixed iteration count instead of the reference's batch-global early exit")
     ap.add_argument("--per-frame", action="store_true", help="binary: every frame stops on its own flag (the reference rule with Num_Frames_OneTime = 1)")
     ap.add_argument("--qam", type=int, default=2, choices=[2, 64, 256],
-                    help="nb: n_QAM (define.h:25): 2 = BPSK, q = Constellation/GRAY_<q>QAM.txt, one point per GF(q) symbol")
+                    help="n_QAM (define.h:25): 2 = BPSK, q = Constellation/GRAY_<q>QAM.txt; nb: one point per GF(q) symbol; binary: log2 q "
+                         "codeword bits per point, max-log demapper, Eb/N0 as in the nb sweep (needs --pn-message --device-channel)")
     ap.add_argument("--nb-matrix", default="BDS.576.288.GF.64.txt", help="nb: matrix file (under data/nb or a path); q from its header")
     ap.add_argument("--method", type=int, default=0, choices=[0, 1, 2, 3], help="NB decoder_method (define.h:37): 0 EMS, 1 TMM, 2 log-QSPA, 3 layered TMM")
     ap.add_argument("--device-channel", action="store_true", help="generate the AWGN samples on the GPU (same RNG draws, device libm)")
@@ -57,6 +58,9 @@ def main():
         ap.error("--alpha and --stop-rule belong to the binary sweep with --layered")
     elif args.which == "binary" and args.pn_message and (not args.fixed or args.as_written):
         ap.error("--pn-message needs the binary sweep with --fixed (the decoders' early exit tests for the all-zero word) on a QC code")
+    if args.which == "binary" and args.qam != 2 and not (args.pn_message and args.device_channel):
+        ap.error("binary --qam %d needs --pn-message (a QAM channel is not symmetric: the all-zero word is not representative) and "
+                 "--device-channel (there is no host QAM channel on this path)" % args.qam)
     nbd = os.path.join(ROOT, "data", "nb")
     if args.which == "nb":
         mpath = args.nb_matrix if os.path.exists(args.nb_matrix) else os.path.join(nbd, args.nb_matrix)
@@ -89,16 +93,20 @@ def main():
         if args.layered:
             stop = args.stop_rule or ("syndrome" if args.pn_message else "prefix")
             lay = dict(schedule="layered", alpha=args.alpha, stop_rule=C.STOP_SYNDROME if stop == "syndrome" else C.STOP_PREFIX)
+        mod = {}
+        if args.qam != 2:  # the GF(q) half's constellation file and sigma (Eb/N0, n_QAM in the formula): the two sweeps share both
+            mod = dict(n_QAM=args.qam, CONSTELLATION=C.Get_CONSTELLATION(os.path.join(nbd, "Constellation", "GRAY_%dQAM.txt" % args.qam), args.qam))
         if rank == 0:
-            print("# %s N=%d K=%d, %s%s, maxIT=%d, batch=%d x %d GPU(s)%s" % (os.path.basename(args.matrix), code.N, code.K,
+            print("# %s N=%d K=%d, %s%s%s, maxIT=%d, batch=%d x %d GPU(s)%s" % (os.path.basename(args.matrix), code.N, code.K,
+                  "" if args.qam == 2 else "%d-QAM (Gray) %d bits per point, max-log demapper, Eb/N0, " % (args.qam, args.qam.bit_length() - 1),
                   "layered min-sum alpha=%g stop=%s, " % (args.alpha, stop) if args.layered else "",
                   "fixed iterations" if args.fixed else ("per-frame early exit" if args.per_frame else "batch-global early exit"),
                   args.iters or (25 if args.layered else 50), args.batch, world,
                   ", random codewords (PN seed %d, K'=%d), syndrome flag" % (args.pn_seed, code.K_info) if args.pn_message else ""))
             print("# SNR      NTF   NEF         FER         BER  AverIT       FER_F      FER_A")
-        sweep(code, args.start, args.stop, args.step, snrtype=1, dist=dist, Num_Frames_OneTime=args.batch, maxIT=args.iters or (25 if args.layered else 50),
+        sweep(code, args.start, args.stop, args.step, snrtype=1 if args.qam == 2 else 0, dist=dist, Num_Frames_OneTime=args.batch, maxIT=args.iters or (25 if args.layered else 50),
               exit_mode=C.EXIT_FIXED if args.fixed else (C.EXIT_PER_FRAME if args.per_frame else C.EXIT_BATCH_GLOBAL), max_batches=args.max_batches, displayStep=10 ** 12, device_channel=args.device_channel,
-              PN_Message=1 if args.pn_message else 0, pn_seed=args.pn_seed, log=print if rank == 0 else None, **lay)
+              PN_Message=1 if args.pn_message else 0, pn_seed=args.pn_seed, log=print if rank == 0 else None, **lay, **mod)
     else:
         from cuda_ldpc_amd import nbldpc as nb
         from cuda_ldpc_amd.nb_simulation import sweep
