@@ -92,6 +92,23 @@ def sigma_of(SNR, snrtype=1, rate=0.0):
     return float(lib.bldpc_sigma(np.float32(SNR), snrtype, np.float32(rate)))
 
 
+_QC_VARIANT_FIELDS = ("NF", "J", "L", "Z", "WC", "WV", "G", "MINW", "CPT", "regstate", "loc", "has_pf", "U", "threads", "lds_bytes")
+
+
+def qc_variants():
+    """The table of ahead-of-time fused kernel variants (bldpc_qc_variant_info), in selection order: a list of dicts with the
+    fields of include/bldpc.h plus index and tag.  CPT holds NG for the "regstate-halo" entries.  Host only, no device needed."""
+    out = []
+    for i in range(int(lib.bldpc_qc_variant_count())):
+        d = np.zeros(16, np.int32)
+        tag = ctypes.c_char_p()
+        check(lib.bldpc_qc_variant_info(i, _np_ptr(d), ctypes.byref(tag)), "bldpc_qc_variant_info")
+        v = dict(zip(_QC_VARIANT_FIELDS, (int(x) for x in d)))
+        v.update(index=i, tag=tag.value.decode(), has_pf=bool(v["has_pf"]))
+        out.append(v)
+    return out
+
+
 class BinaryCode:
     """Device-resident code object (bldpc_code).  Build with from_blockh / from_shifts / from_table."""
 
@@ -154,6 +171,30 @@ class BinaryCode:
     @property
     def last_kernel(self):
         return lib.bldpc_last_kernel(self._h).decode()
+
+    def qc_info(self):
+        """bldpc_code_qc_info: dict(variant, variant_per_frame, persist_grid, frames_per_wg, force_regroup, no_persist,
+        persist_grid_per_frame) of the fused-kernel plan; the variant indices are -1 where there is no such plan."""
+        d = np.zeros(8, np.int32)
+        check(lib.bldpc_code_qc_info(self._h, _np_ptr(d)), "bldpc_code_qc_info")
+        return dict(variant=int(d[0]), variant_per_frame=int(d[1]), persist_grid=int(d[2]), frames_per_wg=int(d[3]),
+                    force_regroup=bool(d[4]), no_persist=bool(d[5]), persist_grid_per_frame=int(d[6]))
+
+    @property
+    def qc_variant(self):
+        """Index into qc_variants() of the fused kernel variant this code runs on (-1: the table kernels serve it)."""
+        return self.qc_info()["variant"]
+
+    @property
+    def qc_variant_per_frame(self):
+        """Index of the nested plan that serves the per-frame passes (-1: the plan of qc_variant serves them itself)."""
+        return self.qc_info()["variant_per_frame"]
+
+    @property
+    def persist_grid(self):
+        """Workgroups of the persistent per-frame kernel of the plan that serves the per-frame passes (0: it has none)."""
+        q = self.qc_info()
+        return q["persist_grid_per_frame"] if q["variant_per_frame"] >= 0 else q["persist_grid"]
 
     def set_profiling(self, enable=True):
         check(lib.bldpc_set_profiling(self._h, 1 if enable else 0), "bldpc_set_profiling")

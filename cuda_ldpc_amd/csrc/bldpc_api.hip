@@ -247,6 +247,41 @@ extern "C" int bldpc_code_dims(const bldpc_code *c, int dims[8])
 
 extern "C" const char *bldpc_last_kernel(const bldpc_code *c) { return c ? c->last_kernel : "none"; }
 
+extern "C" int bldpc_qc_variant_count(void)
+{
+    int n = 0;
+    (void)qc_variants(&n);
+    return n;
+}
+
+extern "C" int bldpc_qc_variant_info(int index, int info[16], const char **tag)
+{
+    int n = 0;
+    const QcVariant *vars = qc_variants(&n);
+    if (!info || index < 0 || index >= n) return fail(BLDPC_EINVAL, "bldpc_qc_variant_info: index %d outside [0,%d) or null info", index, n);
+    const QcVariant &v = vars[index];
+    const int out[16] = {v.NF, v.J, v.L, v.Z, v.WC, v.WV, v.G, v.MINW, v.CPT, v.regstate, v.loc, v.fn_pf ? 1 : 0, v.U, v.threads, v.lds_bytes, 0};
+    std::copy(out, out + 16, info);
+    if (tag) *tag = v.tag;
+    return BLDPC_OK;
+}
+
+extern "C" int bldpc_code_qc_info(const bldpc_code *c, int info[8])
+{
+    if (!c || !info) return fail(BLDPC_EINVAL, "bldpc_code_qc_info: null argument");
+    const bool on = c->has_qc && c->qc.frames_per_wg > 0;
+    const QcPlan *pf = on ? c->qc.pf : nullptr;
+    info[0] = on ? c->qc.variant : -1;
+    info[1] = pf ? pf->variant : -1;
+    info[2] = on ? c->qc.persist_grid : 0;
+    info[3] = on ? c->qc.frames_per_wg : 0;
+    info[4] = on && c->qc.force_regroup ? 1 : 0;
+    info[5] = on && c->qc.no_persist ? 1 : 0;
+    info[6] = pf ? pf->persist_grid : 0;
+    info[7] = 0;
+    return BLDPC_OK;
+}
+
 extern "C" int bldpc_set_profiling(bldpc_code *c, int enable)
 {
     if (!c) return fail(BLDPC_EINVAL, "bldpc_set_profiling: null code");

@@ -319,6 +319,34 @@ int bldpc_kernel_ms_mean(bldpc_code *code, float *mean_ms, int *launches);
 /* Name of the kernel variant the last bldpc_decode / bldpc_decode_layered on this code used (static string). */
 const char *bldpc_last_kernel(const bldpc_code *code);
 
+/* -- the table of fused (QC_LDS) kernel variants, read-only ---------------------------------------------------------- */
+
+/* The fused kernels are instantiated ahead of time, one table entry ("variant") per geometry; a code object takes the first
+ * entry that accepts its matrix (BLDPC_QC_VARIANT=<index> in the environment, read when the code is created, pins one).
+ * These calls only report; they select nothing.  Host only: no device is touched.
+ *   bldpc_qc_variant_count   entries in the table
+ *   bldpc_qc_variant_info    info[16] of entry `index` (0 <= index < count, else BLDPC_EINVAL):
+ *     [0] NF frames per lane  [1] J  [2] L  [3] Z   (J = L = 0: any; L = 0: any)
+ *     [4] WC heaviest block row taken  [5] WV heaviest block column taken (31: no limit of the entry's own)
+ *     [6] G thread groups  [7] MINW lightest block row taken (checked by the register-state entries only)
+ *     [8] CPT block columns per thread group at most (compressed entries) or NG, the wrapped blocks per (row, tile) at most
+ *         (register-state entries with halos); 0 elsewhere
+ *     [9] regstate: 0, 1 = check states in registers, 2 = the same with halo columns
+ *     [10] loc: 0, 1 = half-row kernel with local edges, 2 = row kernel with local edges
+ *     [11] 1 when the entry has a persistent per-frame kernel  [12] U lanes per thread group (compressed entries, else 0)
+ *     [13] threads per workgroup  [14] LDS bytes (0: computed per code)  [15] 0
+ *     *tag (when not NULL): the entry's tag as it appears in bldpc_last_kernel ("row", "halfrow", "compressed", ...), static. */
+int bldpc_qc_variant_count(void);
+int bldpc_qc_variant_info(int index, int info[16], const char **tag);
+
+/* What the fused-kernel plan of a code object is, info[8]:
+ *   [0] variant index of the plan, -1: none (the table kernels serve the code)
+ *   [1] variant index of the nested plan that serves the per-frame passes, -1: none (the plan itself serves them)
+ *   [2] persist_grid: workgroups of the plan's persistent kernel (0: it has none)  [3] frames per workgroup
+ *   [4] 1 when built under BLDPC_REGROUP  [5] 1 when built under BLDPC_NO_PERSIST
+ *   [6] persist_grid of the nested plan (0: none)  [7] 0 */
+int bldpc_code_qc_info(const bldpc_code *code, int info[8]);
+
 const char *bldpc_last_error(void);
 
 #ifdef __cplusplus

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from conftest import DATA, GOLDEN
+from qc_variant_cases import random_block_matrix
 
 pytestmark = pytest.mark.gpu
 
@@ -618,19 +619,7 @@ def test_bench_plain_run_dumps_outputs(C, tmp_path):
 def test_other_lifting_sizes_random_matrices(C, orc, tmp_path, Z, J, L):
     """Random block matrices with lifting sizes the reference's matrix set does not contain: the generic compressed-state
     kernel is picked (these shapes have no ahead-of-time messages-in-LDS variant) and agrees with the oracle and the table kernels."""
-    rng = np.random.default_rng(Z + J)
-    H = rng.integers(0, Z, size=(J, L)).astype(np.int32)
-    H[rng.random((J, L)) < 0.45] = -1
-    for l in range(L):  # every column keeps at least two blocks, every row at least three
-        rows = rng.permutation(J)[:2]
-        for r in rows:
-            if H[r, l] < 0:
-                H[r, l] = rng.integers(0, Z)
-    for j in range(J):
-        cols = rng.permutation(L)[:3]
-        for c in cols:
-            if H[j, c] < 0:
-                H[j, c] = rng.integers(0, Z)
+    H = random_block_matrix(Z, J, L)  # every column keeps at least two blocks, every row at least three
     path = str(tmp_path / "H.txt")
     with open(path, "w") as f:
         for j in range(J):
