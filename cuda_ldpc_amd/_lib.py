@@ -29,6 +29,7 @@ lib.bldpc_last_kernel.argtypes = [c_void_p]
 lib.bldpc_qc_variant_count.argtypes = []
 lib.bldpc_qc_variant_info.argtypes = [c_int, c_void_p, ctypes.POINTER(c_char_p)]
 lib.bldpc_code_qc_info.argtypes = [c_void_p, c_void_p]
+lib.bldpc_qc_plan_host.argtypes = [c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]
 lib.bldpc_read_blockh.argtypes = [c_char_p, c_int, c_int, c_void_p, c_void_p, c_void_p]
 lib.bldpc_transform_h.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int]
 lib.bldpc_code_create_qc.argtypes = [c_int, c_int, c_int, c_void_p, ctypes.POINTER(c_void_p)]

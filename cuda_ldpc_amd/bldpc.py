@@ -5,6 +5,7 @@ compile-time macros of define.cuh (J, L, Z, Num_Frames_OneTime, maxIT, msgLen)
 become run-time arguments.  Everything computes through the C ABI of
 include/bldpc.h on the GPU; tensors are torch CUDA(HIP) tensors.
 """
+import collections
 import ctypes
 from dataclasses import dataclass, field
 
@@ -107,6 +108,21 @@ def qc_variants():
         v.update(index=i, tag=tag.value.decode(), has_pf=bool(v["has_pf"]))
         out.append(v)
     return out
+
+
+QcPlanHost = collections.namedtuple("QcPlanHost", "variant variant_per_frame lds_bytes lc WVS frames_per_wg info digest")
+
+
+def qc_plan_host(H, Z, pin=-1, no_local=False, no_halo=False, local_per_frame=False):
+    """bldpc_qc_plan_host: the fused-kernel plan a code object of the block matrix H [J, L] would get (pin, no_local, no_halo,
+    local_per_frame: as BLDPC_QC_VARIANT, BLDPC_NO_LOCAL, BLDPC_NO_HALO, BLDPC_LOCAL_PER_FRAME), with the FNV-1a digests of its
+    tables.  Host only, no device needed.  info: int32 [8], digest: uint64 [8] as in include/bldpc.h."""
+    H = np.ascontiguousarray(H, np.int32)
+    J, L = H.shape
+    info, digest = np.zeros(8, np.int32), np.zeros(8, np.uint64)
+    flags = (1 if no_local else 0) | (2 if no_halo else 0) | (4 if local_per_frame else 0)
+    check(lib.bldpc_qc_plan_host(J, L, int(Z), _np_ptr(H), int(pin), flags, _np_ptr(info), _np_ptr(digest)), "bldpc_qc_plan_host")
+    return QcPlanHost(*(int(x) for x in info[:6]), info, digest)
 
 
 class BinaryCode:

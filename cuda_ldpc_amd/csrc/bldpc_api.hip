@@ -109,12 +109,7 @@ extern "C" int bldpc_transform_h(const int *H, int J, int L, int Z, const int *w
     return BLDPC_OK;
 }
 
-static int upload(void **dst, const void *src, size_t bytes)
-{
-    CLDPC_HIP(hipMalloc(dst, bytes), BLDPC_ENOMEM);
-    CLDPC_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice), BLDPC_EHIP);
-    return BLDPC_OK;
-}
+static_assert(BLDPC_OK == 0 && BLDPC_ENOMEM == kUploadEnomem && BLDPC_EHIP == kUploadEhip, "cldpc::upload returns this ABI's codes");
 
 // Shared tail of the two constructors: validate the table, level-schedule the
 // variable nodes, upload.
@@ -190,7 +185,7 @@ extern "C" int bldpc_code_create_qc(int J, int L, int Z, const int *H, bldpc_cod
     if (!r) r = finish_code(c, addr.data());
     if (!r) {
         c->has_qc = true;
-        r = qc_plan_build(&c->qc, J, L, Z, c->H.data());
+        r = qc_plan_build(&c->qc, J, L, Z, c->H.data(), qc_switches_from_env());
     }
     if (r) { bldpc_code_destroy(c); return r; }
     *out = c;
@@ -279,6 +274,49 @@ extern "C" int bldpc_code_qc_info(const bldpc_code *c, int info[8])
     info[5] = on && c->qc.no_persist ? 1 : 0;
     info[6] = pf ? pf->persist_grid : 0;
     info[7] = 0;
+    return BLDPC_OK;
+}
+
+static unsigned long long fnv1a(const void *p, size_t n)
+{
+    unsigned long long h = 1469598103934665603ull;
+    for (size_t i = 0; i < n; i++) h = (h ^ static_cast<const unsigned char *>(p)[i]) * 1099511628211ull;
+    return h;
+}
+
+static void table_digests(const QcTables &t, unsigned long long d[7])
+{
+    const auto bytes = t.bytes();
+    for (size_t i = 0; i < bytes.size(); i++) d[i] = bytes[i].n ? fnv1a(bytes[i].p, bytes[i].n) : 0;
+}
+
+extern "C" int bldpc_qc_plan_host(int J, int L, int Z, const int *H, int pin, int flags, int info[8], unsigned long long digest[8])
+{
+    if (!H || !info || !digest || J <= 0 || L <= 0 || Z <= 0) return fail(BLDPC_EINVAL, "bldpc_qc_plan_host: bad argument");
+    for (int i = 0; i < J * L; i++)
+        if (H[i] != -1 && (H[i] < 0 || H[i] >= Z)) return fail(BLDPC_EINVAL, "shift %d outside [0,%d)", H[i], Z);
+    QcSwitches sw;
+    sw.pin = pin < 0 ? -1 : pin;
+    sw.no_local = flags & 1; sw.no_halo = flags & 2; sw.local_per_frame = flags & 4;
+    QcTables t, pf;
+    qc_tables_build(J, L, Z, H, sw, false, t);
+    std::fill(info, info + 8, 0);
+    std::fill(digest, digest + 8, 0ull);
+    info[0] = info[1] = -1;
+    if (t.variant < 0) return BLDPC_OK;
+    int n = 0;
+    const QcVariant &v = qc_variants(&n)[t.variant];
+    info[0] = t.variant; info[2] = t.lds_bytes; info[3] = t.lc; info[4] = t.WVS; info[5] = v.NF;
+    table_digests(t, digest);
+    if (qc_wants_nested(v, sw, false)) {
+        qc_tables_build(J, L, Z, H, sw, true, pf);
+        if (qc_nested_fits(v, pf.variant)) {
+            unsigned long long nd[7];
+            table_digests(pf, nd);
+            info[1] = pf.variant;
+            digest[7] = fnv1a(nd, sizeof(nd));
+        }
+    }
     return BLDPC_OK;
 }
 

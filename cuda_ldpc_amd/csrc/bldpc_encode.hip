@@ -319,13 +319,6 @@ void cldpc::enc_state_free(EncState *s)
     delete s;
 }
 
-static int upload(void **dst, const void *src, size_t bytes)
-{
-    CLDPC_HIP(hipMalloc(dst, std::max<size_t>(bytes, 4)), BLDPC_ENOMEM);
-    if (bytes) CLDPC_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice), BLDPC_EHIP);
-    return BLDPC_OK;
-}
-
 static int state_of(const bldpc_code *code, const char *who, CodeView &v, EncState *&s)
 {
     if (!code) return fail(BLDPC_EINVAL, "%s: null code", who);

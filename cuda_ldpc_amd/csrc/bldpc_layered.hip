@@ -192,13 +192,6 @@ void cldpc::lay_plan_free(LayPlan *p)
 
 namespace {
 
-int upload(void **dst, const void *src, size_t bytes)
-{
-    CLDPC_HIP(hipMalloc(dst, bytes), BLDPC_ENOMEM);
-    CLDPC_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice), BLDPC_EHIP);
-    return BLDPC_OK;
-}
-
 using LayKernel = void (*)(LayArgs);
 
 LayKernel lay_kernel(int regj)

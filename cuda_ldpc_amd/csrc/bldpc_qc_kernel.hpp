@@ -33,12 +33,11 @@
 // read a slot that always holds +inf (neutral for min1/min2/sign) and write into
 // the row's own padding blocks; columns lighter than WV read a slot that always
 // holds +0.0f (adding +0.0f to a sum that is never -0.0f is exact).
+//
+// This header holds the kernels and the table of their ahead-of-time instantiations (qc_variants); the host side -- which entry a code
+// runs on, the tables the kernels read, their upload, the launches and the exit rules -- is bldpc_qc_plan.hpp, included at the bottom.
 #pragma once
-#include <algorithm>
-#include <cstdlib>
-#include <string>
 #include <utility>
-#include <vector>
 
 #include "../../include/bldpc.h"
 #include "bldpc_math.hpp"
@@ -593,9 +592,13 @@ __global__ __launch_bounds__(256) void k_iters_max(const int *iters, int F, int 
 
 // ---------------------------------------------------------------------------------------------
 using QcKernel = void (*)(QcArgs);
-struct QcVariant { int NF, J, L, Z, WC, WV, G, MINW, threads, lds_bytes; QcKernel fn, fn_hist; const char *tag; int U, CPT, regstate; QcKernel fn_pf = nullptr; int loc = 0; };
-// fn_pf: persistent kernel for the per-frame exit (k_qc2p), or null; loc: half-row kernel with local edges (QcGeom2<..., true>)
-// tag "compressed" (U != 0): J = L = 0 (any), WC = row slots, lds_bytes computed per code; tag "regstate": L = 0 (any)
+// What the host builds for an entry: block lists for the row and half-row kernels (with or without local edges, see loc), meta words for
+// the compressed-state kernel, row slots for the register-state kernels, halo slot tables on top for the hardware-addressed one.
+enum class QcKind { ROW, HALFROW, COMPRESSED, REGSTATE, REGSTATE_HALO };
+struct QcVariant { int NF, J, L, Z, WC, WV, G, MINW, threads, lds_bytes; QcKernel fn, fn_hist; const char *tag; QcKind kind; int U, CPT, regstate; QcKernel fn_pf = nullptr; int loc = 0; };
+// fn_pf: persistent kernel for the per-frame exit (k_qc2p), or null; loc: local edges, 1 = half-row kernel (QcGeom2<..., true>), 2 = row kernel
+// COMPRESSED: J = L = 0 (any), WC = row slots; the kinds without block lists: lds_bytes computed per code (qc_lds_bytes).  Host code
+// branches on kind and loc alone; tag, U and regstate are what bldpc_qc_variant_info and the plan's name report.
 
 // Ahead-of-time variants: one per block-matrix geometry of the reference's matrix set whose message
 // state fits one CU's LDS (shifts are run-time data, so every code of the same J x L x Z shape and
@@ -614,15 +617,15 @@ inline const QcVariant *qc_variants(int *count)
 #define X(NF, J, L, Z, WC, WV, G, MINW)                                                                  \
     {NF, J, L, Z, WC, WV, G, MINW, QcGeom<NF, J, L, Z, WC, WV, G, MINW>::TPB,                              \
      QcGeom<NF, J, L, Z, WC, WV, G, MINW>::lds_bytes, k_qc<QcGeom<NF, J, L, Z, WC, WV, G, MINW>, false>,    \
-     k_qc<QcGeom<NF, J, L, Z, WC, WV, G, MINW>, true>, "row", 0, 0, 0, k_qcp<QcGeom<NF, J, L, Z, WC, WV, G, MINW>, true>},
+     k_qc<QcGeom<NF, J, L, Z, WC, WV, G, MINW>, true>, "row", QcKind::ROW, 0, 0, 0, k_qcp<QcGeom<NF, J, L, Z, WC, WV, G, MINW>, true>},
 #define X2(NF, J, L, Z, WC, WV, GJ, MINW)                                                                 \
     {NF, J, L, Z, WC, WV, GJ, MINW, QcGeom2<NF, J, L, Z, WC, WV, GJ, MINW>::TPB,                            \
      QcGeom2<NF, J, L, Z, WC, WV, GJ, MINW>::lds_bytes, k_qc2<QcGeom2<NF, J, L, Z, WC, WV, GJ, MINW>, false>, \
-     k_qc2<QcGeom2<NF, J, L, Z, WC, WV, GJ, MINW>, true>, "halfrow", 0, 0, 0, k_qc2p<QcGeom2<NF, J, L, Z, WC, WV, GJ, MINW>, true>},
+     k_qc2<QcGeom2<NF, J, L, Z, WC, WV, GJ, MINW>, true>, "halfrow", QcKind::HALFROW, 0, 0, 0, k_qc2p<QcGeom2<NF, J, L, Z, WC, WV, GJ, MINW>, true>},
 #define X1L(NF, J, L, Z, WC, WV, G, MINW)                                                                      \
     {NF, J, L, Z, WC, WV, G, MINW, QcGeom<NF, J, L, Z, WC, WV, G, MINW, true>::TPB,                                \
      QcGeom<NF, J, L, Z, WC, WV, G, MINW, true>::lds_bytes, k_qc<QcGeom<NF, J, L, Z, WC, WV, G, MINW, true>, false>,  \
-     k_qc<QcGeom<NF, J, L, Z, WC, WV, G, MINW, true>, true>, "row-local", 0, 0, 0, QC1L_PF(NF, J, L, Z, WC, WV, G, MINW), 2},
+     k_qc<QcGeom<NF, J, L, Z, WC, WV, G, MINW, true>, true>, "row-local", QcKind::ROW, 0, 0, 0, QC1L_PF(NF, J, L, Z, WC, WV, G, MINW), 2},
 #ifdef QC_LOCAL_PER_FRAME_ROW /* experiment: the per-frame exit of the ROW kernel on its local-edge form too (persistent form instantiated) */
 #define QC1L_PF(NF, J, L, Z, WC, WV, G, MINW) k_qcp<QcGeom<NF, J, L, Z, WC, WV, G, MINW, true>, true>
 #else
@@ -631,17 +634,17 @@ inline const QcVariant *qc_variants(int *count)
 #define X2L(NF, J, L, Z, WC, WV, GJ, MINW)                                                                      \
     {NF, J, L, Z, WC, WV, GJ, MINW, QcGeom2<NF, J, L, Z, WC, WV, GJ, MINW, true>::TPB,                              \
      QcGeom2<NF, J, L, Z, WC, WV, GJ, MINW, true>::lds_bytes, k_qc2<QcGeom2<NF, J, L, Z, WC, WV, GJ, MINW, true>, false>, \
-     k_qc2<QcGeom2<NF, J, L, Z, WC, WV, GJ, MINW, true>, true>, "halfrow-local", 0, 0, 0,                            \
+     k_qc2<QcGeom2<NF, J, L, Z, WC, WV, GJ, MINW, true>, true>, "halfrow-local", QcKind::HALFROW, 0, 0, 0,                            \
      k_qc2p<QcGeom2<NF, J, L, Z, WC, WV, GJ, MINW, true>, true>, 1},
 #define XC(Z, U, G, CPT, WCS)                                                                              \
     {1, 0, 0, Z, WCS, 31, G, 0, QccGeom<Z, U, G, CPT, WCS>::TPB, 0, k_qcc<QccGeom<Z, U, G, CPT, WCS>, false>,   \
-     k_qcc<QccGeom<Z, U, G, CPT, WCS>, true>, "compressed", U, CPT, 0, k_qcc<QccGeom<Z, U, G, CPT, WCS>, true, true>},
+     k_qcc<QccGeom<Z, U, G, CPT, WCS>, true>, "compressed", QcKind::COMPRESSED, U, CPT, 0, k_qcc<QccGeom<Z, U, G, CPT, WCS>, true, true>},
 #define XR(J, L, Z, TPB, WCS, MINW, YB)                                                                     \
     {1, J, L, Z, WCS, 31, 0, MINW, TPB, 0, k_qcr<QcrGeom<J, L, Z, TPB, WCS, MINW, YB>, false>,               \
-     k_qcr<QcrGeom<J, L, Z, TPB, WCS, MINW, YB>, true>, "regstate", 0, 0, 1, k_qcr<QcrGeom<J, L, Z, TPB, WCS, MINW, YB>, true, true>},
+     k_qcr<QcrGeom<J, L, Z, TPB, WCS, MINW, YB>, true>, "regstate", QcKind::REGSTATE, 0, 0, 1, k_qcr<QcrGeom<J, L, Z, TPB, WCS, MINW, YB>, true, true>},
 #define XR2(J, L, Z, TPB, WCS, YB, NG) /* CPT carries NG here */                                              \
     {1, J, L, Z, WCS, 31, 0, 2, TPB, 0, k_qcr2<Qcr2Geom<J, L, Z, TPB, WCS, YB, NG>, false>,                    \
-     k_qcr2<Qcr2Geom<J, L, Z, TPB, WCS, YB, NG>, true>, "regstate-halo", 0, NG, 2, k_qcr2<Qcr2Geom<J, L, Z, TPB, WCS, YB, NG>, true, true>},
+     k_qcr2<Qcr2Geom<J, L, Z, TPB, WCS, YB, NG>, true>, "regstate-halo", QcKind::REGSTATE_HALO, 0, NG, 2, k_qcr2<Qcr2Geom<J, L, Z, TPB, WCS, YB, NG>, true, true>},
     static const QcVariant v[] = {
         X2L(2, 4, 24, 96, 20, 4, 4, 6) /* J4_L24_Z96 (BASELINE config 2) with local edges: taken when every row is full and the matching exists */
         X2(2, 4, 24, 96, 20, 4, 4, 6) /* J4_L24_Z96 (BASELINE config 2): 768 thr, 80 KB, 2 WG/CU, 6 waves/SIMD */
@@ -691,537 +694,6 @@ static unsigned long long *g_qc_stamps = nullptr;
 static int g_qc_stagger = 0;
 #endif
 
-struct QcPlan {
-    int J = 0, L = 0, Z = 0, nnz = 0, Wc = 0, Wv = 0;
-    int variant = -1;
-    int frames_per_wg = 0; // 0 = unavailable
-    QcCnEdge *d_cn = nullptr;
-    unsigned short *d_rowptr = nullptr;
-    QcVnEdge *d_vn = nullptr;
-    unsigned char *d_wv = nullptr;
-    unsigned *d_cn_meta = nullptr, *d_vn_meta = nullptr; // compressed-state kernel
-    v4i32 *d_lane = nullptr; // half-row kernel: per-thread LDS addresses (qc2_lane_table)
-    int WVS = 0, lds_bytes = 0, lc = 0;
-    char name[96] = "qc_lds(unavailable)";
-    mutable int ran_to_max = 0; // BATCH_GLOBAL: the previous batch did not stop before max_iter (a performance hint, never a result)
-    int persist_grid = 0; // k_qc2p: workgroups that fill the chip once (a multiple of 8)
-    // experiment / test switches, read ONCE when the plan is built (never per decode call):
-    bool no_persist = false;    // BLDPC_NO_PERSIST: one workgroup per frame group even where the persistent form exists
-    bool force_regroup = false; // BLDPC_REGROUP: k_regroup_y in front of the row / half-row kernels instead of reading in place
-                                // (BLDPC_NO_LOCAL, also read there: the half-row kernel without local edges)
-    // A ROW-kernel plan with local edges carries the plain plan of the same code for the per-frame exit: its flag-tracking
-    // instantiation keeps the branching variable-node phase (one loop per place code would be 210 KB there) and the plain kernel is the
-    // faster one for frames that leave after 3 ... 10 iterations (J32_L64_Z64 per-frame 24.5 against 23.4 M codewords/s).  The HALF-ROW
-    // kernel serves the per-frame exit with its local-edge form (persistent, k_qc2p<LOC>): 49 / 66 / 71 M against 44 / 59 / 66 M
-    // codewords/s at 3.0 / 3.6 / 4.2 dB (it was the other way round, 40 / 53 / 59 M, before the block-row choice left the loop).
-    QcPlan *pf = nullptr;
-};
-
-// bldpc_decode_statistic: per-frame error counts wanted from the pass that unpacks the hard bits (single-launch modes only).
-// Per CALL state (it used to live in the plan, where a concurrent decode on another host thread could pick it up).
-struct QcStat {
-    int *errs = nullptr; // device int32 [F], all zero on entry
-    int length = 0;
-    bool done = false;   // set when the unpack pass has accumulated into errs
-};
-
-inline void qc_plan_release(QcPlan *q)
-{
-    if (q->d_cn) (void)hipFree(q->d_cn);
-    if (q->d_rowptr) (void)hipFree(q->d_rowptr);
-    if (q->d_vn) (void)hipFree(q->d_vn);
-    if (q->d_wv) (void)hipFree(q->d_wv);
-    if (q->d_cn_meta) (void)hipFree(q->d_cn_meta);
-    if (q->d_vn_meta) (void)hipFree(q->d_vn_meta);
-    if (q->d_lane) (void)hipFree(q->d_lane);
-    q->d_cn_meta = nullptr; q->d_vn_meta = nullptr; q->d_lane = nullptr;
-    q->d_cn = nullptr; q->d_rowptr = nullptr; q->d_vn = nullptr; q->d_wv = nullptr;
-    q->frames_per_wg = 0;
-    if (q->pf) {
-        qc_plan_release(q->pf);
-        delete q->pf;
-        q->pf = nullptr;
-    }
-}
-
-// The half-row kernel's per-thread table (see qc2_lane_words) from the block lists as uploaded: what every thread's prologue used to
-// gather from cn_edges / vn_edges itself, two dependent global look-ups in front of its channel loads.  Laid out [word][thread] so that
-// a wave's load of one int4 word is 1 KB contiguous.  False if an address falls outside the kernel's LDS or input (cannot happen).
-inline bool qc2_lane_table(const QcVariant &v, const std::vector<unsigned short> &rowptr, const std::vector<QcCnEdge> &cn,
-                           const std::vector<QcVnEdge> &vn, const std::vector<unsigned char> &wvb, std::vector<int> &tab)
-{
-    const bool loc = v.loc == 1;
-    const int Z = v.Z, WC = v.WC, WV = v.WV, GJ = v.G, L = v.L, TPB = v.threads, MSG = v.NF * 4;
-    const int ZB = Z / 32, WCH = WC / 2, NCG = 2 * GJ, RPT = v.J / GJ, CPT = L / NCG, NV = loc ? CPT : 0, WVR = loc ? WV - 1 : WV;
-    const int Sslot = v.J * WC * Z, zero_slot = Sslot + L * Z, inf_slot = zero_slot + 1;
-    const int LW = qc2_lane_words(v.J, L, WC, WV, GJ, loc);
-    tab.assign((size_t)LW * 4 * TPB, 0);
-    bool ok = true;
-    for (int tid = 0; tid < TPB; tid++) {
-        const int wave = tid >> 6, lane = tid & 63, h = lane >> 5;
-        const int jq = wave / ZB, t = (wave - jq * ZB) * 32 + (lane & 31), cg = jq * 2 + h;
-        std::vector<int> w(LW * 4, 0), cl(CPT, 0);
-        for (int rr = 0; rr < RPT; rr++) {
-            const int e0 = rowptr[jq + rr * GJ], wr = rowptr[jq + rr * GJ + 1] - e0;
-            for (int i = 0; i < WCH; i++) {
-                int slot = inf_slot;
-                if (h * WCH + i < wr) {
-                    const QcCnEdge ed = cn[e0 + h * WCH + i];
-                    const int c = (t + ed.shift) % Z;
-                    slot = Sslot + ed.col * Z + c;
-                    if (loc && i < CPT) { // local edge i: this thread is also the variable (col, c), column i of its column group
-                        w[i] = ed.col * Z + c;
-                        cl[i] = c;
-                    }
-                }
-                w[NV + rr * WCH + i] = slot * MSG;
-            }
-        }
-        for (int cc = 0; cc < CPT; cc++) {
-            const int l = cg + cc * NCG;
-            for (int k = 0; k < WVR; k++) {
-                int slot = zero_slot;
-                if (loc) { // the column's blocks in the other block rows (the own row jq is the local edge), ascending
-                    const QcVnEdge ed = vn[(size_t)l * WV + k + (k >= jq ? 1 : 0)];
-                    if (ed.e != 0xffffu) slot = ed.e * Z + (cl[cc] - ed.shift + Z) % Z;
-                } else if (k < wvb[l]) {
-                    const QcVnEdge ed = vn[(size_t)l * WV + k];
-                    slot = ed.e * Z + (t - ed.shift + Z) % Z;
-                }
-                w[NV + RPT * WCH + cc * WVR + k] = slot * MSG;
-            }
-        }
-        for (int k = 0; k < LW * 4; k++) {
-            const bool var = k < NV, addr = k >= NV && k < NV + RPT * WCH + CPT * WVR;
-            ok = ok && (!var || (w[k] >= 0 && w[k] < L * Z)) && (!addr || (w[k] >= 0 && w[k] < v.lds_bytes - MSG + 1));
-            tab[((size_t)(k / 4) * TPB + tid) * 4 + k % 4] = w[k];
-        }
-    }
-    return ok;
-}
-
-// Pick the first variant whose geometry matches the code, upload its block lists.  Leaves
-// frames_per_wg == 0 (not an error) when none does.  BLDPC_QC_VARIANT=<index> pins one (experiments).
-inline int qc_plan_build(QcPlan *q, int J, int L, int Z, const int *H, bool plain = false)
-{
-    q->J = J; q->L = L; q->Z = Z;
-    std::vector<QcCnEdge> cn;
-    std::vector<unsigned short> rowptr(J + 1, 0);
-    std::vector<int> wv(L, 0);
-    int Wc = 0, Wcmin = 1 << 30;
-    if (Z > 65535 || L > 65535) return BLDPC_OK;
-    for (int j = 0; j < J; j++) {
-        for (int l = 0; l < L; l++)
-            if (H[j * L + l] != -1) {
-                cn.push_back({(unsigned short)l, (unsigned short)H[j * L + l]});
-                wv[l]++;
-            }
-        if (cn.size() > 65535) return BLDPC_OK;
-        rowptr[j + 1] = (unsigned short)cn.size();
-        Wc = std::max(Wc, (int)(rowptr[j + 1] - rowptr[j]));
-        Wcmin = std::min(Wcmin, (int)(rowptr[j + 1] - rowptr[j]));
-    }
-    const int nnz = (int)cn.size();
-    const int Wv = *std::max_element(wv.begin(), wv.end());
-    q->nnz = nnz; q->Wc = Wc; q->Wv = Wv;
-    int nvar = 0;
-    const QcVariant *vars = qc_variants(&nvar);
-    const char *pin = getenv("BLDPC_QC_VARIANT");
-    const bool no_halo = getenv("BLDPC_NO_HALO") != nullptr; // tests: k_qcr on a code k_qcr2 takes
-    q->no_persist = getenv("BLDPC_NO_PERSIST") != nullptr;
-    q->force_regroup = getenv("BLDPC_REGROUP") != nullptr;
-    const bool no_local = plain || getenv("BLDPC_NO_LOCAL") != nullptr;
-    std::vector<int> owner; // half-row kernel with local edges: the block row every column is handed to
-    // k_qcr2 gives per-lane addresses to two slots per (block row, tile): no more than two of a row's blocks may wrap past Z in
-    // the same tile of 64 circulant positions (shifts taken relative to the register-resident column, as the kernel sees them)
-    auto qcr2_fits = [&](int ng) -> bool {
-        int lc = -1;
-        for (int l = 0; l < L && lc < 0; l++)
-            if (wv[l] == J) lc = l;
-        if (lc < 0 || Z % 64 != 0) return false;
-        for (int j = 0; j < J; j++) {
-            int rot = 0;
-            for (int e = rowptr[j]; e < rowptr[j + 1]; e++)
-                if (cn[e].col == lc) rot = cn[e].shift;
-            for (int t = 0; t < Z / 64; t++) {
-                int nw = 0;
-                for (int e = rowptr[j]; e < rowptr[j + 1]; e++)
-                    if (cn[e].col != lc && (64 * t + (cn[e].shift - rot + Z) % Z) % Z > Z - 64) nw++;
-                if (nw > ng) return false;
-            }
-        }
-        return true;
-    };
-    for (int vi = 0; vi < nvar && q->variant < 0; vi++) {
-        const QcVariant &v = vars[vi];
-        if (pin && atoi(pin) != vi) continue;
-        if (v.regstate) { // register-state kernel
-            if (v.regstate == 2 && (!qcr2_fits(v.CPT) || no_halo)) continue; // three blocks of one row wrap in the same tile: k_qcr takes the code (env: tests)
-            const size_t lds = v.regstate == 2 ? (size_t)L * (Z + 64) * 4 + 272 : (size_t)L * Z * 4 + 16;
-            if (v.J != J || v.L != L || v.Z != Z || v.WC < Wc || v.MINW > Wcmin || L > 255 || Z > 2047 || lds > kLdsBytes) continue;
-            q->lds_bytes = (int)lds;
-        } else if (v.U) { // compressed-state kernel: geometry-generic
-            const size_t lds = (size_t)(J + 1) * Z * 12 + (size_t)(L + 1) * Z * 4 + 16;
-            if (v.Z != Z || (L + v.G - 1) / v.G > v.CPT || v.WC < Wc || Wv > 28 || J > 62 || L > 254 || Z > 2047 || lds > kLdsBytes) continue;
-            q->lds_bytes = (int)lds;
-        } else {
-            if (v.J != J || v.L != L || v.Z != Z || v.WC < Wc || v.WV < Wv) continue;
-            if ((size_t)v.lds_bytes > kLdsBytes) continue;
-            if (v.loc == 1 && (no_local || Wcmin != v.WC || L % (2 * J) != 0 || !qc2_local_assign(J, L, rowptr, cn, owner))) continue; // every row full, every column placed
-            if (v.loc == 2 && (no_local || Z % 64 != 0 || *std::min_element(wv.begin(), wv.end()) != v.WV || Wcmin < L / J ||
-                               !qc2_local_assign(J, L, rowptr, cn, owner))) continue; // every column full, every column placed
-            q->lds_bytes = v.lds_bytes;
-        }
-        q->variant = vi;
-    }
-    if (q->variant < 0) return BLDPC_OK;
-    const QcVariant &v = vars[q->variant];
-    if (v.regstate) { // row slots with first-edge-of-column marks
-        // the register-resident column LC: one that meets every block row (prefer the heaviest traffic saved = any such);
-        // every block row is rotated until its LC block has shift 0, and lists that block first
-        int lc = -1;
-        for (int l = 0; l < L && lc < 0; l++)
-            if (wv[l] == J) lc = l;
-        bool ok = lc >= 0;
-        for (int l = 0; l < L; l++) ok = ok && wv[l] > 0; // an unconnected column would keep a stale S
-        if (!ok) { q->variant = -1; return BLDPC_OK; }
-        std::vector<unsigned> cm((size_t)J * v.WC, qcr_cn_meta(0, 0, 0, 1));
-        std::vector<int> seen(L, 0);
-        for (int j = 0; j < J; j++) {
-            int rot = 0;
-            for (int e = rowptr[j]; e < rowptr[j + 1]; e++)
-                if (cn[e].col == lc) rot = cn[e].shift;
-            int pos = 1;
-            for (int e = rowptr[j]; e < rowptr[j + 1]; e++) {
-                const int l = cn[e].col;
-                seen[l]++;
-                cm[(size_t)j * v.WC + (l == lc ? 0 : pos++)] = qcr_cn_meta(l, (cn[e].shift - rot + Z) % Z, seen[l] == 1, 0);
-            }
-        }
-        q->lc = lc;
-        if (v.regstate == 2) { // k_qcr2: per (block row, tile, slot) the byte offset of the wave's 64 rotated positions, and the flags
-            const int NT = Z / 64, ZH = Z + 64, WCS = v.WC;
-            const unsigned inf_base = (unsigned)(L * ZH * 4); // 64 words of +inf: what a padding slot addresses
-            std::vector<unsigned> ta((size_t)J * NT * WCS, inf_base), tx((size_t)J * NT * WCS, inf_base);
-            bool fits = true;
-            for (int j = 0; j < J && fits; j++)
-                for (int t = 0; t < NT && fits; t++) {
-                    // slots of this (block row, tile): the blocks whose 64 positions wrap past Z go last (the last NG slots take
-                    // per-lane addresses in phase 2), the others first, padding in between (plain + wrapped <= WCS - 1: no overlap)
-                    std::vector<std::pair<int, int>> plain, wrapped; // (column, rb)
-                    for (int p = 1; p < WCS; p++) {
-                        const unsigned m = cm[(size_t)j * WCS + p];
-                        if ((m >> 21) & 1u) continue;
-                        const int col = (int)(m & 255u), rb = (64 * t + (int)((m >> 8) & 2047u)) % Z;
-                        (rb > Z - 64 ? wrapped : plain).push_back({col, rb});
-                    }
-                    if ((int)wrapped.size() > v.CPT) { fits = false; break; }
-                    unsigned *a1 = &ta[((size_t)j * NT + t) * WCS], *a2 = &tx[((size_t)j * NT + t) * WCS];
-                    int slot = 1;
-                    for (auto &b : plain) {
-                        a1[slot] = a2[slot] = (unsigned)((b.first * ZH + b.second) * 4);
-                        slot++;
-                    }
-                    for (int g = 0; g < v.CPT; g++) // the per-lane slots, whatever they hold: offset | first wrapped lane << 18 (64: no lane wraps)
-                        a2[WCS - 1 - g] = (a2[WCS - 1 - g] & 0x3ffffu) | (64u << 18);
-                    for (size_t k = 0; k < wrapped.size(); k++) {
-                        const int gs = WCS - 1 - (int)k;
-                        a1[gs] = (unsigned)((wrapped[k].first * ZH + wrapped[k].second) * 4);
-                        a2[gs] = a1[gs] | ((unsigned)(Z - wrapped[k].second) << 18); // lanes from Z - rb on wrap
-                    }
-                }
-            if (!fits) { q->variant = -1; return BLDPC_OK; } // (the selection loop has checked: cannot happen)
-            if (L * ZH * 4 + 272 >= (1 << 18)) { q->variant = -1; return BLDPC_OK; } // offsets are 18-bit fields
-            CLDPC_HIP(hipMalloc((void **)&q->d_vn_meta, tx.size() * sizeof(unsigned)), BLDPC_ENOMEM); // one table for both phases (ta = tx without the lane tags)
-            CLDPC_HIP(hipMemcpy(q->d_vn_meta, tx.data(), tx.size() * sizeof(unsigned), hipMemcpyHostToDevice), BLDPC_EHIP);
-        } else {
-            CLDPC_HIP(hipMalloc((void **)&q->d_cn_meta, cm.size() * sizeof(unsigned)), BLDPC_ENOMEM);
-            CLDPC_HIP(hipMemcpy(q->d_cn_meta, cm.data(), cm.size() * sizeof(unsigned), hipMemcpyHostToDevice), BLDPC_EHIP);
-        }
-    }
-    if (v.U) { // meta tables of the compressed-state kernel
-        const int WVS = (Wv + 1) / 2 * 2; // column edge lists padded to whole rounds of 2 with entries of the zero state (row J)
-        q->WVS = WVS;
-        std::vector<unsigned> cm((size_t)J * v.WC + J, qcc_cn_meta(L, 0)), vm((size_t)L * WVS, qcc_vn_meta(J, 0, 0));
-        std::vector<int> fillc(L, 0);
-        for (int j = 0; j < J; j++) {
-            for (int e = rowptr[j]; e < rowptr[j + 1]; e++) {
-                const int pos = e - rowptr[j], l = cn[e].col;
-                cm[(size_t)j * v.WC + pos] = qcc_cn_meta(l, cn[e].shift);
-                vm[(size_t)l * WVS + fillc[l]++] = qcc_vn_meta(j, pos, cn[e].shift); // ascending j = the reference's edge order
-            }
-            cm[(size_t)J * v.WC + j] = (unsigned)(rowptr[j + 1] - rowptr[j]); // row weights behind the slots
-        }
-        CLDPC_HIP(hipMalloc((void **)&q->d_cn_meta, cm.size() * sizeof(unsigned)), BLDPC_ENOMEM);
-        CLDPC_HIP(hipMalloc((void **)&q->d_vn_meta, vm.size() * sizeof(unsigned)), BLDPC_ENOMEM);
-        CLDPC_HIP(hipMemcpy(q->d_cn_meta, cm.data(), cm.size() * sizeof(unsigned), hipMemcpyHostToDevice), BLDPC_EHIP);
-        CLDPC_HIP(hipMemcpy(q->d_vn_meta, vm.data(), vm.size() * sizeof(unsigned), hipMemcpyHostToDevice), BLDPC_EHIP);
-    }
-    const bool generic = v.U || v.regstate;
-    const int vnw = generic ? 1 : v.WV;
-    // Row variant with wave-uniform rows (Z whole waves) and several rows per thread: the kernel runs ONE body for all of a
-    // thread's rows, sized for the heaviest of them, so that their loads are in flight together.  Which check rows a thread owns is
-    // free (a row is only a name for a set of R slots): hand every thread group rows of equal weight where the weights allow it --
-    // "virtual" row i + rr*G = the (i*RPT + rr)-th row in descending weight order.  The ORDER of a column's edges stays the
-    // reference's, ascending real block row: only the slot a block's messages live in changes.
-    std::vector<int> virt_of(J);
-    for (int j = 0; j < J; j++) virt_of[j] = j;
-    if (!generic && std::string(v.tag).compare(0, 3, "row") == 0 && Z % 64 == 0 && J / v.G >= 2) {
-        const int G = v.G, RPT = J / G;
-        std::vector<int> order(J);
-        for (int j = 0; j < J; j++) order[j] = j;
-        std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return rowptr[x + 1] - rowptr[x] > rowptr[y + 1] - rowptr[y]; });
-        if (v.loc == 2) { // local edges: the rows of a thread group in lexicographic order of their local blocks' (sorted) places, see qc_kcode_sorted
-            auto place = [&](int l) { int o = 0; for (int j2 = 0; j2 < owner[l]; j2++) o += (H[j2 * L + l] != -1) ? 1 : 0; return o; };
-            auto tuple_of = [&](int j) { std::vector<int> t; for (int l = 0; l < L; l++) if (owner[l] == j) t.push_back(place(l)); std::sort(t.begin(), t.end()); return t; };
-            for (int k0 = 0; k0 + RPT <= J; k0 += RPT)
-                std::stable_sort(order.begin() + k0, order.begin() + k0 + RPT, [&](int x, int y) { return tuple_of(x) < tuple_of(y); });
-        }
-        for (int k = 0; k < J; k++) virt_of[order[k]] = (k / RPT) + (k % RPT) * G;
-        std::vector<int> real_of(J);
-        for (int j = 0; j < J; j++) real_of[virt_of[j]] = j;
-        std::vector<QcCnEdge> cn2;
-        std::vector<unsigned short> rowptr2(J + 1, 0);
-        for (int vj = 0; vj < J; vj++) {
-            const int j = real_of[vj];
-            for (int e = rowptr[j]; e < rowptr[j + 1]; e++) cn2.push_back(cn[e]);
-            rowptr2[vj + 1] = (unsigned short)cn2.size();
-        }
-        cn = cn2;
-        rowptr = rowptr2;
-    }
-    std::vector<int> virt_col(L);
-    for (int l = 0; l < L; l++) virt_col[l] = l;
-    if (v.loc == 2) {
-        // Row kernel: virtual row vj = g + rr*G lists its NLR local blocks first (the order of a row's slots is free); the column of
-        // local block i is the thread group's virtual column g + (rr*NLR + i)*G.
-        const int NLR = L / J, G = v.G;
-        std::vector<int> real_of(J);
-        for (int j = 0; j < J; j++) real_of[virt_of[j]] = j;
-        for (int vj = 0; vj < J; vj++) {
-            std::vector<QcCnEdge> loc, oth;
-            for (int e = rowptr[vj]; e < rowptr[vj + 1]; e++) (owner[cn[e].col] == real_of[vj] ? loc : oth).push_back(cn[e]);
-            auto place = [&](int l) { int o = 0; for (int j2 = 0; j2 < owner[l]; j2++) o += (H[j2 * L + l] != -1) ? 1 : 0; return o; };
-            std::stable_sort(loc.begin(), loc.end(), [&](const QcCnEdge &x, const QcCnEdge &y) { return place(x.col) < place(y.col); }); // by place in the column's order
-            for (int i = 0; i < NLR; i++) {
-                cn[rowptr[vj] + i] = loc[i];
-                virt_col[loc[i].col] = (vj % G) + ((vj / G) * NLR + i) * G;
-            }
-            for (size_t i = 0; i < oth.size(); i++) cn[rowptr[vj] + NLR + i] = oth[i];
-        }
-    }
-    if (v.loc == 1) {
-        // Half-row (j, h) lists its CPT local blocks first, then its share of the row's other blocks (the order of a row's slots is
-        // free: min1 / min2 / sign product are symmetric, a duplicated minimum gives min1 == min2); the column of local block cc is the
-        // thread group's virtual column (2j + h) + cc * 2J.
-        const int CPT = L / (2 * J), WCH = v.WC / 2;
-        std::vector<QcCnEdge> cn2(cn.size());
-        for (int j = 0; j < J; j++) {
-            std::vector<QcCnEdge> loc, oth;
-            for (int e = rowptr[j]; e < rowptr[j + 1]; e++) (owner[cn[e].col] == j ? loc : oth).push_back(cn[e]);
-            for (int h = 0; h < 2; h++) {
-                QcCnEdge *dst = &cn2[rowptr[j] + h * WCH];
-                for (int cc = 0; cc < CPT; cc++) {
-                    dst[cc] = loc[h * CPT + cc];
-                    virt_col[loc[h * CPT + cc].col] = (2 * j + h) + cc * 2 * J;
-                }
-                for (int i = CPT; i < WCH; i++) dst[i] = oth[h * (WCH - CPT) + (i - CPT)];
-            }
-        }
-        cn = cn2;
-    }
-    std::vector<QcVnEdge> vn((size_t)L * vnw, v.loc == 1 ? QcVnEdge{0xffff, 0} : QcVnEdge{0, 0});
-    std::vector<int> fill(L, 0), fill_nl(L, 0), kloc(L, 0);
-    for (int j = 0; j < J; j++) { // ascending REAL block row = the reference's edge order
-        const int vj = virt_of[j];
-        for (int e = rowptr[vj]; e < rowptr[vj + 1]; e++) {
-            const int l = cn[e].col;
-            // .e = padded block index (virtual row)*WC + position
-            if (v.loc == 2) { // the column's other blocks in ascending real block row; kloc = where its local block stands among them
-                if (owner[l] == j) kloc[virt_col[l]] = fill[l];
-                else vn[(size_t)virt_col[l] * v.WV + fill_nl[l]++] = {(unsigned short)(vj * v.WC + (e - rowptr[vj])), cn[e].shift};
-                fill[l]++;
-            } else if (v.loc == 1) vn[(size_t)virt_col[l] * v.WV + j] = {(unsigned short)(j * v.WC + (e - rowptr[j])), cn[e].shift}; // slot k = block row k
-            else if (!generic) vn[(size_t)l * v.WV + fill[l]++] = {(unsigned short)(vj * v.WC + (e - rowptr[vj])), cn[e].shift};
-        }
-    }
-    std::vector<unsigned char> wvb(L);
-    for (int l = 0; l < L; l++) wvb[l] = (unsigned char)(v.loc == 2 ? kloc[l] : wv[l]); // row kernel with local edges: per VIRTUAL column, the place of its local block
-    if (!generic && std::string(v.tag).compare(0, 7, "halfrow") == 0) {
-        std::vector<int> tab;
-        if (!qc2_lane_table(v, rowptr, cn, vn, wvb, tab)) { q->variant = -1; return BLDPC_OK; }
-        CLDPC_HIP(hipMalloc((void **)&q->d_lane, tab.size() * sizeof(int)), BLDPC_ENOMEM);
-        CLDPC_HIP(hipMemcpy(q->d_lane, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice), BLDPC_EHIP);
-    }
-    CLDPC_HIP(hipMalloc((void **)&q->d_cn, cn.size() * sizeof(QcCnEdge)), BLDPC_ENOMEM);
-    CLDPC_HIP(hipMalloc((void **)&q->d_rowptr, rowptr.size() * sizeof(unsigned short)), BLDPC_ENOMEM);
-    CLDPC_HIP(hipMalloc((void **)&q->d_vn, vn.size() * sizeof(QcVnEdge)), BLDPC_ENOMEM);
-    CLDPC_HIP(hipMalloc((void **)&q->d_wv, wvb.size()), BLDPC_ENOMEM);
-    CLDPC_HIP(hipMemcpy(q->d_cn, cn.data(), cn.size() * sizeof(QcCnEdge), hipMemcpyHostToDevice), BLDPC_EHIP);
-    CLDPC_HIP(hipMemcpy(q->d_rowptr, rowptr.data(), rowptr.size() * sizeof(unsigned short), hipMemcpyHostToDevice), BLDPC_EHIP);
-    CLDPC_HIP(hipMemcpy(q->d_vn, vn.data(), vn.size() * sizeof(QcVnEdge), hipMemcpyHostToDevice), BLDPC_EHIP);
-    CLDPC_HIP(hipMemcpy(q->d_wv, wvb.data(), wvb.size(), hipMemcpyHostToDevice), BLDPC_EHIP);
-    CLDPC_HIP(hipFuncSetAttribute((const void *)v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, generic ? (int)kLdsBytes : v.lds_bytes), BLDPC_EHIP);
-    CLDPC_HIP(hipFuncSetAttribute((const void *)v.fn_hist, hipFuncAttributeMaxDynamicSharedMemorySize, generic ? (int)kLdsBytes : v.lds_bytes), BLDPC_EHIP);
-    if (v.fn_pf) {
-        CLDPC_HIP(hipFuncSetAttribute((const void *)v.fn_pf, hipFuncAttributeMaxDynamicSharedMemorySize, generic ? (int)kLdsBytes : v.lds_bytes), BLDPC_EHIP);
-        int occ = 0, dev = 0, ncu = 0;
-        CLDPC_HIP(hipGetDevice(&dev), BLDPC_EHIP);
-        CLDPC_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev), BLDPC_EHIP);
-        CLDPC_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)v.fn_pf, v.threads, (size_t)q->lds_bytes), BLDPC_EHIP);
-        q->persist_grid = std::max(8, ncu * std::max(1, occ) / 8 * 8);
-    }
-    q->frames_per_wg = v.NF;
-    if (v.loc == 2 && !plain && !getenv("BLDPC_LOCAL_PER_FRAME")) { // the per-frame exit's plan of the ROW kernel (see QcPlan::pf); without it the local-edge kernels serve that mode too
-        q->pf = new QcPlan();
-        const int rp = qc_plan_build(q->pf, J, L, Z, H, true);
-        if (rp || q->pf->frames_per_wg != v.NF || qc_variants(&nvar)[q->pf->variant].loc) {
-            qc_plan_release(q->pf);
-            delete q->pf;
-            q->pf = nullptr;
-            if (rp) return rp;
-        }
-    }
-    snprintf(q->name, sizeof(q->name), "qc_lds_%s<nf%d,J%d,L%d,Z%d,wc%d,wv%d,g%d,w%d>t%d_lds%d", v.tag, v.NF, J, L, v.Z, v.WC, generic ? Wv : v.WV,
-             v.G, v.MINW, v.threads, q->lds_bytes);
-    return BLDPC_OK;
-}
-
-inline bool qc_reads_in_place(const QcPlan *q)
-{
-    int nvar = 0;
-    const QcVariant &v = qc_variants(&nvar)[q->variant];
-    return v.NF == 2 && !v.U && !v.regstate; // the row and half-row kernels
-}
-
-inline int qc_regroup(const QcPlan *q, const float *y, float *yg, int F, hipStream_t st)
-{
-    int nvar = 0;
-    const QcVariant &v = qc_variants(&nvar)[q->variant];
-    const int N = q->L * q->Z;
-    const dim3 grid((unsigned)((F + 63) / 64), (unsigned)((N + 63) / 64));
-    if (v.NF == 2) hipLaunchKernelGGL(k_regroup_y<2>, grid, dim3(256), 0, st, y, yg, N, F);
-    else hipLaunchKernelGGL(k_regroup_y<1>, grid, dim3(256), 0, st, y, yg, N, F);
-    CLDPC_HIP(hipGetLastError(), BLDPC_EHIP);
-    return BLDPC_OK;
-}
-
-// y here is the regrouped buffer produced by qc_regroup.
-inline int qc_launch(const QcPlan *q, const float *y, int F, int max_iter, int length, int *D, float *app,
-                     unsigned long long *hist, unsigned *bits, hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr,
-                     int *iters = nullptr, bool expand = true, int *work = nullptr, QcStat *stat = nullptr, bool y_in_place = false)
-{
-    int nvar = 0;
-    const QcVariant &v = qc_variants(&nvar)[q->variant];
-    QcArgs a;
-    a.y = y; a.y_raw = y_in_place ? y : nullptr; a.D = D; a.bits = bits; a.app = app; a.hist = hist;
-    a.per_frame = (iters && hist) ? 1 : 0; a.iters = iters; // per-frame exit lives in the flag-tracking instantiation
-    a.cn_edges = q->d_cn; a.rowptr = q->d_rowptr; a.vn_edges = q->d_vn; a.wv = q->d_wv; a.lane = q->d_lane;
-    a.F = F;
-    a.nWG = (F + q->frames_per_wg - 1) / q->frames_per_wg;
-    a.max_iter = max_iter; a.length = length;
-    a.cn_meta = q->d_cn_meta; a.vn_meta = q->d_vn_meta; a.J = q->J; a.L = q->L; a.WVS = q->WVS; a.lc = q->lc;
-#ifdef QC_STAMPS
-    a.stamps = g_qc_stamps; a.stagger = g_qc_stagger;
-#endif
-    unsigned grid = (unsigned)((a.nWG + 7) / 8 * 8);
-    QcKernel fn = hist ? v.fn_hist : v.fn;
-    if (a.per_frame && v.fn_pf && work && q->persist_grid > 0 && grid > (unsigned)q->persist_grid && !q->no_persist) {
-        // per-frame exit on the half-row kernel: persistent workgroups, one frame-pair counter per XCD (k_qc2p)
-        CLDPC_HIP(hipMemsetAsync(work, 0, 8 * sizeof(int), st), BLDPC_EHIP);
-        a.work = work;
-        fn = v.fn_pf;
-        grid = (unsigned)q->persist_grid;
-    }
-    if (ev0) (void)hipEventRecord(ev0, st);
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(v.threads), q->lds_bytes, st, a);
-    if (ev1) (void)hipEventRecord(ev1, st);
-    const int NW = q->L * q->Z / 32;
-    if (expand) {
-        hipLaunchKernelGGL(k_expand_bits, dim3((unsigned)((F + 1023) / 1024), (unsigned)NW), dim3(256), 0, st, bits, D, F, NW, stat ? stat->errs : nullptr,
-                           stat ? stat->length : 0);
-        if (stat && stat->errs) stat->done = true;
-    }
-    CLDPC_HIP(hipGetLastError(), BLDPC_EHIP);
-    return BLDPC_OK;
-}
-
-// hist_ws: device uint64[F] workspace; and_ws: device uint64; bits: device uint32 [F][N/32] workspace;
-// yg: device float [ceil(F/NF)*NF][N] workspace for the regrouped channel values.
-inline int qc_decode(const QcPlan *q, const float *y, int F, int max_iter, int length, int exit_mode, int *D, float *app,
-                     unsigned long long *flag_hist, unsigned long long *hist_ws, unsigned long long *and_ws, unsigned *bits,
-                     float *yg, int *itera, int *iters, int *iters_ws, hipStream_t st, hipEvent_t ev0 = nullptr,
-                     hipEvent_t ev1 = nullptr, QcStat *stat = nullptr, const char **used = nullptr)
-{
-    const QcPlan *qf = q->pf ? q->pf : q; // the plan of the per-frame passes
-    if (used) *used = (exit_mode == BLDPC_EXIT_PER_FRAME) ? qf->name : q->name;
-    // k_qc / k_qc2 carry two frames per lane: with F even (and the frame-fastest rows 8-byte aligned) a lane's pair of channel
-    // values is 8 contiguous bytes of the reference's own layout and the kernels read it in place -- every 64-byte sector is
-    // shared by the 4 workgroups of 8 neighbouring frames, which the XCD-aware block order puts on one L2 -- instead of paying a
-    // separate pass that reads and writes the whole input (0.24 ms of a 5.9 ms step at config 2).
-    const bool in_place = qc_reads_in_place(q) && (F % 2 == 0) && ((uintptr_t)y % 8 == 0) && !q->force_regroup;
-    if (!in_place) {
-        int rr = qc_regroup(q, y, yg, F, st);
-        if (rr) return rr;
-        y = yg;
-    }
-    if (exit_mode == BLDPC_EXIT_FIXED) {
-        *itera = max_iter;
-        return qc_launch(q, y, F, max_iter, length, D, app, flag_hist, bits, st, ev0, ev1, nullptr, true, nullptr, stat, in_place);
-    }
-    if (exit_mode == BLDPC_EXIT_PER_FRAME) { // every workgroup leaves when its own frames have stopped; nothing to wait for
-        *itera = max_iter;
-        return qc_launch(qf, y, F, max_iter, length, D, app, flag_hist ? flag_hist : hist_ws, bits, st, ev0, ev1, iters, true, (int *)and_ws, stat, in_place);
-    }
-    // Reference rule (LDPC_Decoder.cu:150-153): stop after the first iteration at which ALL frames are flagged.  No
-    // workgroup can know that iteration while it runs, so it is found first and the batch then decoded with exactly that
-    // many iterations:
-    //   pass 1  per-frame exit (cheap: every workgroup leaves when its own frames are flagged) -> m = the latest
-    //           first-flag iteration of any frame (max_iter for a frame that never flags).  The batch cannot stop before m.
-    //   pass 2  `run` = m iterations with the flag history on: if every frame is flagged at some iteration <= run (usually
-    //           exactly at m) that is the stop iteration -- replayed if it is not `run` itself.  Otherwise a frame has lost
-    //           its flag again: double `run` and repeat; `run` = max_iter ends the search.
-    if (max_iter > 64) return fail(BLDPC_EUNSUPPORTED, "QC_LDS with BATCH_GLOBAL exit supports max_iter <= 64 (got %d)", max_iter);
-    unsigned long long *hist = flag_hist ? flag_hist : hist_ws;
-    // A batch that holds a frame which never passes costs the per-frame pass for nothing (its answer is max_iter); sweeps
-    // stay in that regime for many batches in a row, so after such a batch the full run comes first.
-    auto all_flagged = [&](int iters_run, unsigned long long *all) -> int { // AND of the histories, first iters_run bits
-        CLDPC_HIP(hipMemsetAsync(and_ws, 0xFF, sizeof(unsigned long long), st), BLDPC_EHIP);
-        hipLaunchKernelGGL(k_hist_and, dim3(std::min((F + 255) / 256, 1024)), dim3(256), 0, st, hist, F, and_ws);
-        CLDPC_HIP(hipMemcpyAsync(all, and_ws, sizeof(*all), hipMemcpyDeviceToHost, st), BLDPC_EHIP);
-        CLDPC_HIP(hipStreamSynchronize(st), BLDPC_EHIP);
-        if (iters_run < 64) *all &= ((1ull << iters_run) - 1);
-        return BLDPC_OK;
-    };
-    int r;
-    int run = max_iter;
-    if (!q->ran_to_max) {
-        r = qc_launch(qf, y, F, max_iter, length, D, nullptr, hist, bits, st, nullptr, nullptr, iters_ws, /*expand=*/false, (int *)and_ws, nullptr, in_place);
-        if (r) return r;
-        int m = 0;
-        CLDPC_HIP(hipMemsetAsync(and_ws, 0, sizeof(unsigned long long), st), BLDPC_EHIP);
-        hipLaunchKernelGGL(k_iters_max, dim3(std::min((F + 255) / 256, 1024)), dim3(256), 0, st, iters_ws, F, (int *)and_ws);
-        CLDPC_HIP(hipMemcpyAsync(&m, and_ws, sizeof(int), hipMemcpyDeviceToHost, st), BLDPC_EHIP);
-        CLDPC_HIP(hipStreamSynchronize(st), BLDPC_EHIP);
-        if (m < 1 || m > max_iter) return fail(BLDPC_EHIP, "per-frame pass returned iteration count %d", m);
-        run = m;
-    }
-    for (;; run = std::min(max_iter, std::max(run + 4, 2 * run))) {
-        if ((r = qc_launch(q, y, F, run, length, D, app, hist, bits, st, ev0, ev1, nullptr, true, nullptr, nullptr, in_place))) return r;
-        unsigned long long all = 0; // bit it-1: every frame flagged after iteration it
-        if ((r = all_flagged(run, &all))) return r;
-        if (all) {
-            const int stop = __builtin_ctzll(all) + 1;
-            *itera = stop;
-            q->ran_to_max = (stop == max_iter);
-            return stop < run ? qc_launch(q, y, F, stop, length, D, app, flag_hist, bits, st, ev0, ev1, nullptr, true, nullptr, nullptr, in_place) : BLDPC_OK;
-        }
-        if (run == max_iter) {
-            *itera = max_iter;
-            q->ran_to_max = 1;
-            return BLDPC_OK;
-        }
-    }
-}
-
 } // namespace cldpc
+
+#include "bldpc_qc_plan.hpp" // the host side: plan, tables, launch, decode

@@ -31,6 +31,16 @@ inline int fail(int code, const char *fmt, ...)
             return cldpc::fail((errcode), "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
+// A device copy of a host table: at least 4 bytes are allocated, nothing is copied when bytes == 0.  Returns 0, -2 (out of device
+// memory) or -3 (HIP error): BLDPC_ENOMEM / BLDPC_EHIP and NBLDPC_ENOMEM / NBLDPC_EHIP (asserted in the two *_api.hip units).
+constexpr int kUploadEnomem = -2, kUploadEhip = -3;
+inline int upload(void **dst, const void *src, size_t bytes)
+{
+    CLDPC_HIP(hipMalloc(dst, bytes < 4 ? 4 : bytes), kUploadEnomem);
+    if (bytes) CLDPC_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice), kUploadEhip);
+    return 0;
+}
+
 // Grow-only device buffer owned by a code object (no per-call hipMalloc, unlike
 // the reference's LDPC_Decoder.cu:38-65).
 struct DevBuf {

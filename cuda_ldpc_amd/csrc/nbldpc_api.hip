@@ -24,6 +24,8 @@
 
 using namespace cldpc;
 
+static_assert(NBLDPC_OK == 0 && NBLDPC_ENOMEM == kUploadEnomem && NBLDPC_EHIP == kUploadEhip, "cldpc::upload (nbldpc_encode.hip) returns this ABI's codes");
+
 struct nbldpc_code {
     int N = 0, M = 0, q = 0, m = 0, dv = 0, dc = 0;
     int *d_vn_w = nullptr, *d_vn_thr = nullptr, *d_vn_gf = nullptr;

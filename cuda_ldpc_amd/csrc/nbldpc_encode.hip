@@ -339,13 +339,6 @@ void cldpc::nb_enc_state_free(NbEncState *s)
     delete s;
 }
 
-static int upload(void **dst, const void *src, size_t bytes)
-{
-    CLDPC_HIP(hipMalloc(dst, std::max<size_t>(bytes, 4)), NBLDPC_ENOMEM);
-    if (bytes) CLDPC_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice), NBLDPC_EHIP);
-    return NBLDPC_OK;
-}
-
 static int ensure_generator(nbldpc_code *code, const char *who, NbCodeView &v, NbEncState *&s)
 {
     if (!code) return fail(NBLDPC_EINVAL, "%s: null code", who);

@@ -347,6 +347,17 @@ int bldpc_qc_variant_info(int index, int info[16], const char **tag);
  *   [6] persist_grid of the nested plan (0: none)  [7] 0 */
 int bldpc_code_qc_info(const bldpc_code *code, int info[8]);
 
+/* The plan bldpc_code_create_qc would make for the block matrix H [J][L] (shifts, -1 = zero block), without a device: the table
+ * entry and the tables its kernel reads, as digests.  pin: a variant index as in BLDPC_QC_VARIANT, -1 = none.  flags: bit 0
+ * BLDPC_NO_LOCAL, bit 1 BLDPC_NO_HALO, bit 2 BLDPC_LOCAL_PER_FRAME (the other switches change no table).
+ *   info[8]    [0] variant, -1: none  [1] variant of the nested per-frame plan, -1: none  [2] LDS bytes  [3] lc, the block column the
+ *              register-state kernels keep in registers  [4] WVS, padded column list length of the compressed-state kernel
+ *              [5] frames per workgroup  [6] [7] 0
+ *   digest[8]  [0..6] 64-bit FNV-1a (offset basis 1469598103934665603, prime 1099511628211) of the bytes handed to the device as
+ *              cn, rowptr, vn, wv, cn_meta, vn_meta, lane; 0 for a table that is not uploaded
+ *              [7] FNV-1a of the nested plan's seven digests (56 bytes, as stored), 0: no nested plan */
+int bldpc_qc_plan_host(int J, int L, int Z, const int *H, int pin, int flags, int info[8], unsigned long long digest[8]);
+
 const char *bldpc_last_error(void);
 
 #ifdef __cplusplus

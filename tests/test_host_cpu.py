@@ -204,6 +204,36 @@ def test_explicit_stack_walk_equals_the_recursion(tmp_path):
     assert out.startswith("OK "), out
 
 
+def test_plan_tables_under_host_sanitizers(C, tmp_path):
+    """The tables of the fused binary kernels (qc_tables_build, csrc/bldpc_qc_plan.hpp: no HIP call in it) built by a stand-alone
+    program under AddressSanitizer and UBSan, for every case of the variant case table that uses a shipped matrix -- with its
+    NO_LOCAL / NO_HALO switch or its pin -- and checked there: block lists, column lists with and without local edges, the
+    half-row lane table inside LDS, the compressed meta words, the halo slots (tests/cpp/qc_plan_host_test.hip)."""
+    import shutil
+    import subprocess
+    import qc_variant_cases as Q
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not available")
+    args, names = [], set()
+    for c in Q.build_cases(C.qc_variants()):
+        if c.matrix[0] != "shipped":
+            continue
+        path, _, J, L, Z = Q.matrix(c.matrix)
+        flags = (1 if "BLDPC_NO_LOCAL" in c.env else 0) | (2 if "BLDPC_NO_HALO" in c.env else 0)
+        args += [path, J, L, Z, c.env.get("BLDPC_QC_VARIANT", -1), flags]
+        names.add(c.matrix[1])
+    assert names == {"J4_L24_Z96", "J8_L24_Z96", "J12_L24_Z96", "J6_L24_Z96", "J32_L64_Z64", "J4_L24_Z256", "PON_LDPC", "J4_L24_Z512",
+                     "J15_L30_Z1280", "J10_L60_Z160", "J48_L60_Z160"}
+    exe = str(tmp_path / "qc_plan_host")
+    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cpp", "qc_plan_host_test.hip")
+    subprocess.check_call([hipcc, "-O1", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off", "-Xarch_host", "-fsanitize=address,undefined",
+                           "-Xarch_host", "-fno-sanitize-recover=undefined", src, "-o", exe], cwd=str(tmp_path))
+    r = subprocess.run([exe] + [str(a) for a in args], timeout=120, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    out = r.stdout.decode()
+    assert r.returncode == 0 and out.strip() == "OK %d" % (len(args) // 6), out
+
+
 def test_local_edge_matching_is_valid(tmp_path):
     """The fused row / half-row kernels keep one block per column out of LDS ("local edges"): the host hands every block column to
     one block row containing it, L / J per row (qc2_local_assign, csrc/bldpc_qc_assign.hpp -- no HIP in that header).  On 1 400 random

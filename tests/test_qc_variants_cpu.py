@@ -79,11 +79,18 @@ def _accepts(v, H, J, L, Z, env):
     return True
 
 
-def test_every_case_fits_its_variant(variants, cases):
+def _plan_host(C, c):
+    """qc_plan_host for the case's matrix under the case's pin and switches."""
+    return C.qc_plan_host(Q.matrix(c.matrix)[1], Q.matrix(c.matrix)[4], pin=int(c.env.get("BLDPC_QC_VARIANT", -1)),
+                          no_local="BLDPC_NO_LOCAL" in c.env, no_halo="BLDPC_NO_HALO" in c.env)
+
+
+def test_every_case_fits_its_variant(C, variants, cases):
     for c in cases:
         _, H, J, L, Z = Q.matrix(c.matrix)
         v = variants[c.variant]
         assert _accepts(v, H, J, L, Z, c.env), (c.id, v)
+        assert _plan_host(C, c).variant == c.variant, c.id  # the real selection, the local-edge matching included
         if v["tag"] == "compressed":
             assert -(-L // v["G"]) <= v["CPT"], c.id  # the CPT bound
         earlier = [u["index"] for u in variants[:c.variant] if _accepts(u, H, J, L, Z, c.env)]
@@ -91,6 +98,41 @@ def test_every_case_fits_its_variant(variants, cases):
             assert earlier, "%s is pinned, but nothing stands in front of variant %d: use the product path" % (c.id, c.variant)
         else:
             assert not earlier, "%s: variants %s take the matrix before %d" % (c.id, earlier, c.variant)
+
+
+def _fnv1a(data):
+    h = 1469598103934665603
+    for x in data:
+        h = ((h ^ x) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
+    return h
+
+
+def test_plan_tables_equal_the_parent_commit(C, cases):
+    """tests/golden/qc_plan_digests.json holds, per case, what qc_plan_build handed to the device BEFORE it was split into stages (its
+    hipMalloc / hipMemcpy redirected to host stand-ins, the bytes behind the plan's pointers hashed): the table entry, the LDS
+    size and every table of the staged build are those, byte for byte."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "qc_plan_digests.json")) as f:
+        want = json.load(f)
+    assert sorted(want) == sorted(c.id for c in cases)
+    for c in cases:
+        w = want[c.id]
+        H = np.ascontiguousarray(Q.matrix(c.matrix)[1], np.int32)
+        assert "%016x" % _fnv1a(H.tobytes()) == w["h"], "%s: numpy has generated another matrix than the fixture was made from" % c.id
+        got = _plan_host(C, c)
+        assert got.info.tolist() == w["info"], c.id
+        assert ["%016x" % int(x) for x in got.digest] == w["digest"], c.id
+
+
+def test_plan_host_refuses_bad_arguments(C):
+    H = Q.matrix(("shipped", "J4_L24_Z96"))[1]
+    with pytest.raises(C._lib.LdpcError):
+        C.qc_plan_host(H, 0)
+    with pytest.raises(C._lib.LdpcError):
+        C.qc_plan_host(H, 64)  # shifts of a Z = 96 matrix
+    none = C.qc_plan_host(H, 96, pin=10 ** 6)  # a pin that names no entry: no plan, not an error
+    assert none.info.tolist() == [-1, -1, 0, 0, 0, 0, 0, 0] and not none.digest.any()
 
 
 def test_reachable_by_pin_only(variants, cases):

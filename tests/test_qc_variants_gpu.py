@@ -111,6 +111,18 @@ def _cols(w, N, F0, F):
     return w["D"].reshape(N + 1, F0)[:, :F], w["app"].reshape(N, F0)[:, :F], w["flag_hist"][:F]
 
 
+def test_code_objects_land_where_the_host_view_says(C, monkeypatch):
+    """No kernel runs here: for every case, the code object created under the case's environment reports the variant and the
+    nested per-frame variant that qc_plan_host computes, without a device, for the same matrix and switches."""
+    for case in CASES:
+        code = _make(C, monkeypatch, case.matrix, case.env)
+        _, H, _, _, Z = Q.matrix(case.matrix)
+        host = C.qc_plan_host(H, Z, pin=int(case.env.get("BLDPC_QC_VARIANT", -1)), no_local="BLDPC_NO_LOCAL" in case.env,
+                              no_halo="BLDPC_NO_HALO" in case.env)
+        assert (code.qc_variant, code.qc_variant_per_frame) == (host.variant, host.variant_per_frame), case.id
+        assert code.frames_per_wg == host.frames_per_wg, case.id
+
+
 @pytest.mark.parametrize("case", CASES, ids=IDS)
 def test_fixed_iterations(C, orc, monkeypatch, case):
     """fn and fn_hist at 1, 2 and 7 iterations, F = 1, 5 and 6 (odd batches take the regrouped input, even ones of the two-frame

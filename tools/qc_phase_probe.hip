@@ -24,7 +24,7 @@ int main(int argc, char **argv)
         if (fscanf(fp, "%d", &h) != 1) return 1;
     fclose(fp);
     QcPlan q;
-    if (qc_plan_build(&q, J, L, Z, H.data()) || !q.frames_per_wg) { printf("no plan: %s\n", err_buf()); return 1; }
+    if (qc_plan_build(&q, J, L, Z, H.data(), qc_switches_from_env()) || !q.frames_per_wg) { printf("no plan: %s\n", err_buf()); return 1; }
     printf("kernel %s, F = %d, stagger %d\n", q.name, F, g_qc_stagger);
     const int N = L * Z, nWG = F / 2;
     std::vector<float> y((size_t)N * F);
