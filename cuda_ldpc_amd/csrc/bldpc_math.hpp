@@ -6,6 +6,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#define BLDPC_SELECT_FN __device__ __forceinline__
+#include "bldpc_select.hpp"
 
 namespace cldpc {
 
@@ -37,37 +39,25 @@ struct CnAcc {
     __device__ __forceinline__ uint32_t key() const { return __builtin_amdgcn_bitop3_b32(f2u(m1), f2u(m2), sgn & 0x80000000u, 0x96); } // a ^ b ^ c in one full-rate instruction
 };
 
+// The device policy of bldpc_select.hpp's network: v_min_f32 / v_max_f32 / v_min3_f32 / v_med3_f32.
+struct SelF32 {
+    static __device__ __forceinline__ float min(float a, float b) { return __builtin_fminf(a, b); }
+    static __device__ __forceinline__ float max(float a, float b) { return __builtin_fmaxf(a, b); }
+    static __device__ __forceinline__ float min3(float a, float b, float c) { return __builtin_fminf(__builtin_fminf(a, b), c); }
+    static __device__ __forceinline__ float med3(float a, float b, float c) { return __builtin_amdgcn_fmed3f(a, b, c); }
+};
+
 // The two smallest magnitudes (with multiplicity) and the XOR of the sign bits of N values at once: what N calls of
-// CnAcc::add leave in (m1, m2, sgn), with 3-input instructions -- min3 / med3 of a triple, then
-// (m1, m2) <- (min(m1, lo), min3(max(m1, lo), m2, mid)): 5 instructions per 3 values instead of 6 (14 instead of 20 for the
-// ten edges of half a J4_L24_Z96 row; min / max / med3 all issue every 4.2 cycles per SIMD, profiles/r02_micro_rates.txt).
-// Selection only, no arithmetic: the same bits whatever the order.
+// CnAcc::add leave in (m1, m2, sgn).  The magnitudes go through the selection network of bldpc_select.hpp (3-input instructions:
+// 12 instead of 20 for the ten edges of half a J4_L24_Z96 row, 7 instead of 14 for a 7-edge row of J32_L64_Z64; min / max / min3 /
+// med3 all issue every 4.2 cycles per SIMD, profiles/r02_micro_rates.txt).  Selection only, no arithmetic: the same bits whatever the order.
 template <int N, int STRIDE> __device__ __forceinline__ void cn_two_smallest(const float *q, float &m1, float &m2, uint32_t &sgn)
 {
     static_assert(N >= 2, "a check row half has at least two edges");
-    auto A = [&](int i) { return __builtin_fabsf(q[i * STRIDE]); };
-    int i = 0;
-    if (N >= 3) {
-        m1 = __builtin_fminf(__builtin_fminf(A(0), A(1)), A(2));
-        m2 = __builtin_amdgcn_fmed3f(A(0), A(1), A(2));
-        i = 3;
-    } else {
-        m1 = __builtin_fminf(A(0), A(1));
-        m2 = __builtin_fmaxf(A(0), A(1));
-        i = 2;
-    }
+    float mag[N];
 #pragma unroll
-    for (; i + 3 <= N; i += 3) {
-        const float lo = __builtin_fminf(__builtin_fminf(A(i), A(i + 1)), A(i + 2));
-        const float mid = __builtin_amdgcn_fmed3f(A(i), A(i + 1), A(i + 2));
-        m2 = __builtin_fminf(__builtin_fminf(__builtin_fmaxf(m1, lo), m2), mid);
-        m1 = __builtin_fminf(m1, lo);
-    }
-#pragma unroll
-    for (; i < N; i++) {
-        m2 = __builtin_amdgcn_fmed3f(m1, m2, A(i));
-        m1 = __builtin_fminf(m1, A(i));
-    }
+    for (int i = 0; i < N; i++) mag[i] = __builtin_fabsf(q[i * STRIDE]);
+    two_smallest<SelF32, N, float>(mag, m1, m2);
     // the sign product two values at a time: v_bitop3_b32 (any 3-input bit function; 0x96 = a ^ b ^ c) issues at the full rate on
     // gfx950, unlike v_or3 / v_and_or / v_bfi (tools/micro_rates.hip -> profiles/r03_micro_rates_bitop3.txt: 2.4 against 4.2 SIMD-cycles):
     // 5 instructions instead of 10 for ten edges -- J4_L24_Z96 12.67 -> 13.03 M codewords/s, J32_L64_Z64 6.34 -> 6.53 M

@@ -99,7 +99,15 @@ template <typename GM, bool HIST> __global__ __launch_bounds__(GM::TPB, GM::MINW
 
     // VN phase (LDPC_Decoder.cu:188-210): S = ((0+R_0)+...+R_{w-1})+y, published aligned.  0 + R_0 is a real addition:
     // R_0 may be -0.0f (magnitude 0, sign -1) and (+0) + (-0) = +0 is what the reference computes.
-    auto vn_phase = [&](bool (&bad)[NF]) {
+    // ZS (compile time) = the sum starts at 0; without it it starts at R_0, one v_pk_add_f32 per column less.  The two forms differ
+    // only where EVERY addend is -0.0f, y included: the reference's sum is +0.0f there, the short one -0.0f.  Then this variable's R
+    // is -0.0f on every edge, so the check-node phase's Q = S - R is +0.0f both ways, and S < 0 is false both ways; a column with an
+    // absent block row adds the +0.0f slot and never gets there.  What does read the sign of a zero S is emit (app and its bits).
+    // So the short form is for sums that only the next check-node phase reads: the iteration loop of the HIST == false
+    // instantiations, where emit runs after the FINAL variable-node phase only, and that one (vn_any) keeps the 0.  With HIST,
+    // retire emits S from inside the loop (per-frame exit, k_qc2p) and every phase keeps it.  vn_first is exact as it stands.
+    auto vn_phase = [&](auto ZS, bool (&bad)[NF]) {
+        constexpr bool zs = decltype(ZS)::value;
         constexpr int CB = (CPT * WV <= 12) ? CPT : 1; // columns with reads in flight together
         static_for<CPT / CB>([&](auto C0) {
             constexpr int c0 = decltype(C0)::value * CB;
@@ -110,9 +118,10 @@ template <typename GM, bool HIST> __global__ __launch_bounds__(GM::TPB, GM::MINW
                 for (int k = 0; k < WV; k++) R[ci][k] = lds_ld2(raddr[c0 + ci][k]);
             static_for<CB>([&](auto CI) {
                 constexpr int ci = decltype(CI)::value, cc = c0 + ci;
-                v2f32 S = v2f32{0.0f, 0.0f};
+                v2f32 S = R[ci][0];
+                if constexpr (zs) S = v2f32{0.0f, 0.0f} + S;
 #pragma unroll
-                for (int k = 0; k < WV; k++) S = S + R[ci][k];
+                for (int k = 1; k < WV; k++) S = S + R[ci][k];
                 S = S + yreg[cc];
                 lds_st2_imm<cc * NCG * Z * MSG>(sbase, S);
                 if (HIST) {
@@ -128,8 +137,9 @@ template <typename GM, bool HIST> __global__ __launch_bounds__(GM::TPB, GM::MINW
     // LOC: the same sum with the own block row's R from the register that holds it (slot jj), S kept for the check-node phase
     v2f32 Sloc[LOC ? CPT : 1];
     const int jqs = __builtin_amdgcn_readfirstlane(jq);
-    auto vn_phase_loc = [&](auto JJ, bool (&bad)[NF]) {
+    auto vn_phase_loc = [&](auto JJ, auto ZS, bool (&bad)[NF]) {
         constexpr int jj = decltype(JJ)::value;
+        constexpr bool zs = decltype(ZS)::value;
         v2f32 R[CPT][WV - 1];
 #pragma unroll
         for (int cc = 0; cc < CPT; cc++)
@@ -140,8 +150,11 @@ template <typename GM, bool HIST> __global__ __launch_bounds__(GM::TPB, GM::MINW
             v2f32 S = v2f32{0.0f, 0.0f};
             static_for<WV>([&](auto K) {
                 constexpr int k = decltype(K)::value;
-                if constexpr (k == jj) S = S + Rr[0][cc];
-                else S = S + R[cc][k - (k > jj ? 1 : 0)];
+                v2f32 Rk;
+                if constexpr (k == jj) Rk = Rr[0][cc];
+                else Rk = R[cc][k - (k > jj ? 1 : 0)];
+                if constexpr (k == 0 && !zs) S = Rk;
+                else S = S + Rk;
             });
             S = S + yreg[cc];
             Sloc[LOC ? cc : 0] = S;
@@ -178,8 +191,8 @@ template <typename GM, bool HIST> __global__ __launch_bounds__(GM::TPB, GM::MINW
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     };
     auto vn_any = [&](bool (&bad)[NF]) {
-        if constexpr (LOC) static_for<GM::J>([&](auto JJ) { if (jqs == decltype(JJ)::value) vn_phase_loc(JJ, bad); });
-        else vn_phase(bad);
+        if constexpr (LOC) static_for<GM::J>([&](auto JJ) { if (jqs == decltype(JJ)::value) vn_phase_loc(JJ, std::true_type{}, bad); });
+        else vn_phase(std::true_type{}, bad);
     };
     auto flags_publish = [&](const bool (&bad)[NF], int it) { // two sets of flag words by iteration parity, see k_qc
 #pragma unroll
@@ -262,8 +275,8 @@ template <typename GM, bool HIST> __global__ __launch_bounds__(GM::TPB, GM::MINW
         for (int v = 0; v < NF; v++) bad[v] = false;
         __builtin_amdgcn_s_setprio(QC_PRIO_VN);
         if constexpr (first) vn_first(bad);
-        else if constexpr (LOC) vn_phase_loc(JJ, bad);
-        else vn_phase(bad);
+        else if constexpr (LOC) vn_phase_loc(JJ, std::bool_constant<HIST>{}, bad); // the loop's sums: from 0 only where emit may read them
+        else vn_phase(std::bool_constant<HIST>{}, bad);
         if (HIST) flags_publish(bad, it);
         __syncthreads();
         __builtin_amdgcn_s_setprio(QC_PRIO_CN);
