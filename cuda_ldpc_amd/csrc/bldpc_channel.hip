@@ -11,37 +11,11 @@
 
 #include "../../include/bldpc.h"
 #include "common.hpp"
+#include "common_lcg.hpp"
+
+using namespace cldpc::lcg; // RandomModule (LDPC_Encoder.cu:45-56), its constants, powmod and the jump
 
 namespace {
-inline float random_module(int *seed) // LDPC_Encoder.cu:45-56
-{
-    seed[0] = (seed[0] * 249) % 61967;
-    seed[1] = (seed[1] * 251) % 63443;
-    seed[2] = (seed[2] * 252) % 63599;
-    float t = ((float)seed[0] / 61967.0f) + ((float)seed[1] / 63443.0f) + ((float)seed[2] / 63599.0f);
-    t -= (int)t;
-    return t;
-}
-} // namespace
-
-namespace {
-constexpr unsigned kA[3] = {249u, 251u, 252u}, kM[3] = {61967u, 63443u, 63599u}; // LDPC_Encoder.cu:48-50
-
-// a^k mod m for the three LCG moduli.  They are prime (61967, 63443, 63599), so a^(m-1) = 1 and the exponent reduces to
-// k mod (m-1) < 2^16; operands stay below 2^16, so every product fits 32 bits: at most 16 squarings of 32-bit arithmetic
-// per jump instead of up to 40 of 64-bit arithmetic.
-__host__ __device__ inline unsigned powmod(unsigned a, unsigned long long k, unsigned m)
-{
-    unsigned e = (unsigned)(k % (unsigned long long)(m - 1));
-    unsigned r = 1, b = a % m;
-    while (e) {
-        if (e & 1) r = (r * b) % m;
-        b = (b * b) % m;
-        e >>= 1;
-    }
-    return r;
-}
-
 // frames [f0, f1) of the serial loop (LDPC_Encoder.cu:30-38: frame outer, bit inner), seed = the stream state before frame f0
 void awgn_frames(int *seed, float sigma, float *out, const int *cw, int N, int F, int f0, int f1)
 {
@@ -64,8 +38,7 @@ void awgn_frames(int *seed, float sigma, float *out, const int *cw, int N, int F
 extern "C" int bldpc_awgn_channel_host(int seed[3], float sigma, float *out, const int *cw, int N, int F)
 {
     if (!seed || !out || N <= 0 || F <= 0) return cldpc::fail(BLDPC_EINVAL, "bldpc_awgn_channel_host: bad argument");
-    bool jumpable = true; // the jump needs canonical states; any other int triple takes the serial loop as the reference would
-    for (int i = 0; i < 3; i++) jumpable = jumpable && seed[i] >= 0 && (unsigned)seed[i] < kM[i];
+    const bool jumpable = seed_in_range(seed); // the jump needs canonical states; any other int triple takes the serial loop as the reference would
     const unsigned hw = std::thread::hardware_concurrency();
     const int T = (int)std::min<long long>({(long long)(hw ? hw : 1), 16LL, (long long)F / 16, (long long)((size_t)N * F / 65536)});
     if (!jumpable || T < 2) {
@@ -73,21 +46,17 @@ extern "C" int bldpc_awgn_channel_host(int seed[3], float sigma, float *out, con
         return BLDPC_OK;
     }
     const int s0[3] = {seed[0], seed[1], seed[2]};
-    auto jumped = [&](int f, int *s) {
-        const unsigned long long k = 2ull * (unsigned long long)N * f;
-        for (int i = 0; i < 3; i++) s[i] = (int)(((unsigned long long)s0[i] * powmod(kA[i], k, kM[i])) % kM[i]);
-    };
     std::vector<std::thread> th;
     for (int t = 0; t < T; t++) {
         const int f0 = (int)((long long)F * t / T), f1 = (int)((long long)F * (t + 1) / T);
         th.emplace_back([=]() {
-            int s[3];
-            jumped(f0, s);
+            int s[3] = {s0[0], s0[1], s0[2]};
+            jump(s, 2ull * (unsigned long long)N * f0);
             awgn_frames(s, sigma, out, cw, N, F, f0, f1);
         });
     }
     for (auto &x : th) x.join();
-    jumped(F, seed);
+    jump(seed, 2ull * (unsigned long long)N * F);
     return BLDPC_OK;
 }
 
@@ -102,22 +71,10 @@ __global__ __launch_bounds__(256) void k_awgn(unsigned s0, unsigned s1, unsigned
     if (f >= F) return;
     const unsigned long long k = 2ull * ((unsigned long long)f * N + n0);
     unsigned s[3] = {s0, s1, s2};
-#pragma unroll
-    for (int i = 0; i < 3; i++) s[i] = (unsigned)(((unsigned long long)s[i] * powmod(kA[i], k, kM[i])) % kM[i]);
+    jump(s, k);
     const double two_pi = 2 * 3.1415926;
     for (int n = n0; n < min(N, n0 + kRun); n++) {
-        float u[2];
-#pragma unroll
-        for (int d = 0; d < 2; d++) {
-#pragma unroll
-            for (int i = 0; i < 3; i++) s[i] = (s[i] * kA[i]) % kM[i];
-            // x / m for an integer 0 <= x < m, m an odd prime below 2^16: the correctly rounded float quotient equals the double
-            // product x * (1/m) rounded to float (x/m is at least 2^-40 away, relatively, from every float rounding boundary;
-            // all 3 x 63 599 cases checked in tests/test_host_cpu.py) -- three conversions and a multiply instead of a division
-            float t = (float)((double)(int)s[0] * (1.0 / 61967.0)) + (float)((double)(int)s[1] * (1.0 / 63443.0)) + (float)((double)(int)s[2] * (1.0 / 63599.0));
-            t -= (int)t;
-            u[d] = t;
-        }
+        const float u[2] = {uniform(s), uniform(s)};
         const float amp = sqrtf(-2.0f * logf(1.0f - u[0]));
         const int c = cw ? cw[(size_t)n * F + f] : 0;
         out[(size_t)n * F + f] = (float)((double)sigma * sin(two_pi * (double)u[1]) * (double)amp + 1.0 - (double)(2 * c));
@@ -128,13 +85,12 @@ __global__ __launch_bounds__(256) void k_awgn(unsigned s0, unsigned s1, unsigned
 extern "C" int bldpc_awgn_channel_device(int seed[3], float sigma, float *out, const int *cw, int N, int F, void *stream)
 {
     if (!seed || !out || N <= 0 || F <= 0) return cldpc::fail(BLDPC_EINVAL, "bldpc_awgn_channel_device: bad argument");
-    for (int i = 0; i < 3; i++)
-        if (seed[i] < 0 || (unsigned)seed[i] >= kM[i]) return cldpc::fail(BLDPC_EINVAL, "seed[%d]=%d outside [0,%u)", i, seed[i], kM[i]);
+    int i = 0;
+    if (!seed_in_range(seed, &i)) return cldpc::fail(BLDPC_EINVAL, "seed[%d]=%d outside [0,%u)", i, seed[i], kM[i]);
     hipLaunchKernelGGL(k_awgn, dim3((unsigned)((F + 255) / 256), (unsigned)((N + kRun - 1) / kRun)), dim3(256), 0, (hipStream_t)stream,
                        (unsigned)seed[0], (unsigned)seed[1], (unsigned)seed[2], sigma, out, cw, N, F);
     CLDPC_HIP(hipGetLastError(), BLDPC_EHIP);
-    const unsigned long long draws = 2ull * (unsigned long long)N * F;
-    for (int i = 0; i < 3; i++) seed[i] = (int)(((unsigned long long)seed[i] * powmod(kA[i], draws, kM[i])) % kM[i]);
+    jump(seed, 2ull * (unsigned long long)N * F);
     return BLDPC_OK;
 }
 

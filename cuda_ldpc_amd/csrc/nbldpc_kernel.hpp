@@ -687,57 +687,4 @@ template <int Q, int DVM, int NT> __global__ __launch_bounds__(NT) void k_nb_ems
     } // next frame
 }
 
-// Demodulate, BPSK branch (LDPC_Decoder.cpp:139-157): one thread per (frame, symbol, element).
-__global__ __launch_bounds__(256) void k_nb_demod_bpsk(const float *rx, float sigma, int B, int N, int q, int m, float *Lch)
-{
-    const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const size_t total = (size_t)B * N * (q - 1);
-    if (id >= total) return;
-    const int k = (int)(id % (q - 1)) + 1;
-    const size_t bs = id / (q - 1); // b*N + s
-    const float *r = rx + bs * m;
-    const float s2 = sigma * sigma;
-    float acc = 0.0f;
-    for (int b = 0; b < m; b++)
-        if ((k & (1 << b)) != 0) acc += (float)(-2) * r[b] / s2;
-    Lch[id] = acc;
-}
-
-// Demodulate, n_QAM != 2 branch (LDPC_Decoder.cpp:160-169): one received point per code symbol, float arithmetic in the
-// reference's order.  rx [B][N][2] (Real, Image), con [q][2].
-__global__ __launch_bounds__(256) void k_nb_demod_qam(const float *rx, const float *con, float sigma, int B, int N, int q, float *Lch)
-{
-    const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const size_t total = (size_t)B * N * (q - 1);
-    if (id >= total) return;
-    const int k = (int)(id % (q - 1)) + 1;
-    const size_t bs = id / (q - 1); // b*N + s
-    const float yr = rx[2 * bs], yi = rx[2 * bs + 1];
-    const float c0r = con[0], c0i = con[1], ckr = con[2 * k], cki = con[2 * k + 1];
-    Lch[id] = ((2 * yr - c0r - ckr) * (ckr - c0r) + (2 * yi - c0i - cki) * (cki - c0i)) / (2 * sigma * sigma);
-}
-
-// Statistic (Simulation.cpp:256-279): one thread per frame.  Frame f is compared with cw + f * cw_stride (0: one word for all frames).
-__global__ __launch_bounds__(256) void k_nb_statistic(const int *out, const int *iters, const int *ok, const int *cw, int cw_stride, int B, int N,
-                                                      long long *counters)
-{
-    const int f = blockIdx.x * 256 + threadIdx.x;
-    long long v[4] = {0, 0, 0, 0};
-    if (f < B) {
-        int err = 0;
-        const int *w = cw + (size_t)f * cw_stride;
-        for (int i = 0; i < N; i++) err += (out[(size_t)f * N + i] != w[i]) ? 1 : 0;
-        v[0] = err != 0;
-        v[1] = err;
-        v[2] = iters[f];
-        v[3] = ok[f];
-    }
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-        long long x = v[c];
-        for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-        if ((threadIdx.x & 63) == 0 && x) atomicAdd((unsigned long long *)&counters[c], (unsigned long long)x);
-    }
-}
-
 } // namespace cldpc

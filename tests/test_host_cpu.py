@@ -334,3 +334,96 @@ def test_nb_reference_signature_shim_host_side(nbm, orc, tmp_path):
     assert [int(x) for x in st[:8]] == [0, 0, 0, 1, 4, 2, 4, 2 + 3 + 4 + 5]  # returns 1 when >= 2 error frames and >= 3 frames
     assert abs(float(st[8]) - 0.5) < 1e-7 and abs(float(st[9]) - 4 / 4 / 96) < 1e-9 and abs(float(st[10]) - 14 / 4) < 1e-6  # "BER" = symbol errors / frames / N (sic)
 
+
+
+NB_PLAN_CASES = [  # (case id in tests/golden/nb_plan_digests.json, matrix, field, switches of tests/cpp/nb_plan_host_test.hip)
+    ("BDS.576.288.GF.64.txt", "BDS.576.288.GF.64.txt", 64, 0),                   # fused, k_nb_ems2 offered, trellis decoders offered
+    ("LDPC_N576_K288_GF64_d1_exp.txt", "LDPC_N576_K288_GF64_d1_exp.txt", 64, 0), # zero coefficients
+    ("LDPC_N96_K48_GF256_d1_exp.txt", "LDPC_N96_K48_GF256_d1_exp.txt", 256, 0),  # wide
+    ("LDPC_N576_K480_GF256_exp.txt", "LDPC_N576_K480_GF256_exp.txt", 256, 0),    # heavy rows: workspace kernel
+    ("Tanner_74_9_Z128_GF16.txt", "Tanner_74_9_Z128_GF16.txt", 16, 0),           # row weight 21: workspace kernel
+    ("BDS.576.288.GF.64.txt+NBLDPC_FORCE_HBM", "BDS.576.288.GF.64.txt", 64, 1),
+]
+
+
+def test_nb_plan_tables_equal_the_parent_commit_under_host_sanitizers(tmp_path):
+    """What nbldpc_code_create hands to the device (nb_tables_build, csrc/nbldpc_plan.hpp: no HIP call in it), built by a stand-alone
+    program under AddressSanitizer and UBSan for the five shipped GF(q) matrices and the forced workspace path, checked there (cross
+    indices mutually inverse and in range, trellis tables: tests/cpp/nb_plan_host_test.hip) and compared with
+    tests/golden/nb_plan_digests.json: the host decisions and the FNV-1a 64 digest of every upload, in order, as nbldpc_code_create
+    made them BEFORE it was split into stages (its hipMalloc / hipMemcpy pair replaced by a hash of the bytes).  Exact: integer tables."""
+    import json
+    import shutil
+    import subprocess
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not available")
+    here = os.path.dirname(os.path.abspath(__file__))
+    with open(os.path.join(here, "golden", "nb_plan_digests.json")) as f:
+        want = json.load(f)
+    assert sorted(want) == sorted(c[0] for c in NB_PLAN_CASES)
+    exe = str(tmp_path / "nb_plan_host")
+    subprocess.check_call([hipcc, "-O1", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off", "-Xarch_host", "-fsanitize=address,undefined",
+                           "-Xarch_host", "-fno-sanitize-recover=undefined", os.path.join(here, "cpp", "nb_plan_host_test.hip"), "-o", exe],
+                          cwd=str(tmp_path))
+    args = []
+    for cid, matrix, q, flags in NB_PLAN_CASES:
+        args += [cid, os.path.join(NB, matrix), os.path.join(NB, "GF", "Arith.Table.GF.%d.txt" % q), str(flags)]
+    r = subprocess.run([exe] + args, timeout=120, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    lines = r.stdout.decode().strip().split("\n")
+    assert r.returncode == 0 and lines[-1] == "OK %d" % len(NB_PLAN_CASES), r.stdout.decode()
+    keys = ("m", "hbm", "lds_bytes", "zero_coeff", "levels", "tmm_ok", "pipe_lds")
+    for (cid, _, _, _), line in zip(NB_PLAN_CASES, lines):
+        tok = line.split()
+        assert tok[0] == cid
+        got = dict(zip(keys, (int(x) for x in tok[1:8])), digest=tok[8:])
+        assert got == want[cid], cid
+
+
+def nb_create_error_cases():
+    """Malformed variants of a 4-variable, 2-check code over GF(4) (VN 0, 1 on CN 0; VN 2, 3 on CN 1): name -> nbldpc_code_create
+    arguments.  Every one is refused before the first HIP call."""
+    base = dict(N=4, M=2, q=4, dv=1, dc=2, vn_w=[1, 1, 1, 1], vn_cn=[0, 0, 1, 1], vn_gf=[1, 2, 3, 1], cn_w=[2, 2], cn_vn=[0, 1, 2, 3],
+                cn_gf=[1, 2, 3, 1], mul=[0, 0, 0, 0, 0, 1, 2, 3, 0, 2, 3, 1, 0, 3, 1, 2])
+
+    def variant(**kw):
+        c = {k: (list(v) if isinstance(v, list) else v) for k, v in base.items()}
+        for k, v in kw.items():
+            if isinstance(v, tuple):
+                c[k][v[0]] = v[1]
+            else:
+                c[k] = v
+        return c
+    return {
+        "vn_names_cn_that_does_not_list_it": variant(vn_cn=(0, 1)),
+        "coefficient_differs_between_views": variant(cn_gf=(0, 3)),
+        "row_of_weight_1": variant(vn_w=(1, 0), cn_w=(0, 1)),
+        "multiply_table_entry_ge_q": variant(mul=(5, 4)),
+        "dv_9": variant(dv=9, vn_cn=[0] * 36, vn_gf=[1] * 36),
+        "q_512": variant(q=512),
+        "q_48": variant(q=48),
+        "check_index_out_of_range": variant(vn_cn=(0, 2)),
+    }
+
+
+def nb_create_error(lib, c):
+    arr = {k: np.ascontiguousarray(c[k], np.uint32 if k == "mul" else np.int32) for k in ("vn_w", "vn_cn", "vn_gf", "cn_w", "cn_vn", "cn_gf", "mul")}
+    h = ctypes.c_void_p()
+    rc = lib.nbldpc_code_create(c["N"], c["M"], c["q"], c["dv"], c["dc"], *[arr[k].ctypes.data_as(ctypes.c_void_p) for k in
+                                ("vn_w", "vn_cn", "vn_gf", "cn_w", "cn_vn", "cn_gf", "mul")], ctypes.byref(h))
+    return [rc, lib.nbldpc_last_error().decode()]
+
+
+def test_nb_code_create_errors_equal_the_parent_commit(nbm):
+    """tests/golden/nb_create_errors.json holds (code, nbldpc_last_error()) of nbldpc_code_create for each malformed input, recorded
+    BEFORE the function was split into stages: codes, texts and the order of the checks are unchanged.  No device: all return before
+    the first HIP call."""
+    import json
+    from cuda_ldpc_amd._lib import lib
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "nb_create_errors.json")) as f:
+        want = json.load(f)
+    cases = nb_create_error_cases()
+    assert sorted(want) == sorted(cases) and len(cases) == 8
+    for name, c in cases.items():
+        assert nb_create_error(lib, c) == want[name], name
+        assert want[name][0] < 0
