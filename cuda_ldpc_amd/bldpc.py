@@ -337,7 +337,7 @@ def Syndrome(code, D, into_flag_row=True, stream=None):
 
 
 def LDPC_Decoder_GPU(code, Channel_Out, max_iter=50, length=0, exit_mode=EXIT_BATCH_GLOBAL, kernel=KERNEL_AUTO,
-                     D=None, want_app=False, want_flag_hist=False, stream=None):
+                     D=None, want_app=False, want_flag_hist=False, stream=None, alpha=None):
     """LDPC_Decoder_GPU (LDPC_Decoder.cu:23-164).
 
     Channel_Out: CUDA float32 tensor [N, F] (frame-fastest, as the reference).
@@ -345,6 +345,9 @@ def LDPC_Decoder_GPU(code, Channel_Out, max_iter=50, length=0, exit_mode=EXIT_BA
 
     exit_mode=EXIT_PER_FRAME (bldpc_decode_per_frame): every frame stops on its own flag, as the reference does with a
     batch of one frame; the result then carries iters=int32 [F] on the device (iterations per frame) and iteraTime is None.
+
+    alpha=None is the reference's un-normalised min-sum.  A number in (0, 1] runs the normalised kernels (bldpc_decode_normalised:
+    every check message times alpha, 1.0 included): EXIT_FIXED (iteraTime = max_iter) or EXIT_PER_FRAME, no flag history.
     """
     if not (Channel_Out.is_cuda and Channel_Out.dtype == torch.float32 and Channel_Out.is_contiguous()):
         raise ValueError("Channel_Out must be a contiguous CUDA float32 tensor")
@@ -356,10 +359,19 @@ def LDPC_Decoder_GPU(code, Channel_Out, max_iter=50, length=0, exit_mode=EXIT_BA
         D = torch.empty((code.N + 1, F), dtype=torch.int32, device=dev)
     else:
         _check_D(D, code.N, F, dev)
+    if alpha is not None and (exit_mode == EXIT_BATCH_GLOBAL or want_flag_hist):
+        raise ValueError("alpha (normalised min-sum) takes EXIT_FIXED or EXIT_PER_FRAME and returns no flag history")
     app = torch.empty((code.N, F), dtype=torch.float32, device=dev) if want_app else None
     hist = torch.zeros(F, dtype=torch.int64, device=dev) if want_flag_hist else None
     it = ctypes.c_int(0)
     st = ctypes.c_void_p((stream or torch.cuda.current_stream(dev)).cuda_stream)
+    if alpha is not None:
+        iters = torch.empty(F, dtype=torch.int32, device=dev) if exit_mode == EXIT_PER_FRAME else None
+        check(lib.bldpc_decode_normalised(code._h, _dev_ptr(Channel_Out), F, int(max_iter), ctypes.c_float(alpha), int(length), int(exit_mode),
+                                          int(kernel), _dev_ptr(D), _dev_ptr(app), _dev_ptr(iters), st), "LDPC_Decoder_GPU")
+        if iters is not None:
+            return dict(D=D, iteraTime=None, app=app, flag_hist=None, iters=iters)
+        return dict(D=D, iteraTime=int(max_iter), app=app, flag_hist=None)
     if exit_mode == EXIT_PER_FRAME:
         if want_flag_hist:
             raise ValueError("flag history is not returned with per-frame exit (iters holds each frame's stop iteration)")
@@ -414,6 +426,26 @@ def layered_host(H, J, L, Z, y, max_iter=25, alpha=1.0, length=0, exit_mode=EXIT
     iters = np.zeros(F, np.int32)
     check(lib.bldpc_decode_layered_host(J, L, Z, _np_ptr(H), _np_ptr(y), F, int(max_iter), ctypes.c_float(alpha), int(length), int(exit_mode),
                                         int(stop_rule), _np_ptr(D), None if app is None else _np_ptr(app), _np_ptr(iters)), "layered_host")
+    return dict(D=D, app=app, iters=iters)
+
+
+def normalised_host(H, J, L, Z, y, max_iter=50, alpha=1.0, length=0, exit_mode=EXIT_FIXED, want_app=True):
+    """bldpc_decode_normalised_host: the flooding decoder with normalised min-sum on the host (no device), the statement of its
+    semantics.  y: float32 [N, F] host array (frame-fastest).  Returns dict(D=int32 [N+1, F], app=float32 [N, F] or None,
+    iters=int32 [F]: iterations run by each frame)."""
+    H = np.ascontiguousarray(H, np.int32)
+    if H.size != J * L:
+        raise ValueError("H must hold J*L shifts")
+    y = np.ascontiguousarray(y, np.float32)
+    N = L * Z
+    if y.ndim != 2 or y.shape[0] != N or y.shape[1] <= 0:
+        raise ValueError("y must be [N=%d, F]" % N)
+    F = y.shape[1]
+    D = np.zeros((N + 1, F), np.int32)
+    app = np.zeros((N, F), np.float32) if want_app else None
+    iters = np.zeros(F, np.int32)
+    check(lib.bldpc_decode_normalised_host(J, L, Z, _np_ptr(H), _np_ptr(y), F, int(max_iter), ctypes.c_float(alpha), int(length), int(exit_mode),
+                                           _np_ptr(D), None if app is None else _np_ptr(app), _np_ptr(iters)), "normalised_host")
     return dict(D=D, app=app, iters=iters)
 
 

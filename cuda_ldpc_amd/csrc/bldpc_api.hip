@@ -14,6 +14,7 @@
 
 #include "bldpc_encode.hpp"
 #include "bldpc_layered.hpp"
+#include "bldpc_norm.hpp"
 #include "bldpc_qc_kernel.hpp"
 #include "bldpc_table_kernels.hpp"
 #include "common.hpp"
@@ -31,6 +32,7 @@ struct bldpc_code {
     int *h_cnt = nullptr; // pinned
     QcPlan qc;            // fused LDS kernel description (frames_per_wg == 0: unavailable)
     const char *last_kernel = "none";
+    char norm_name[112] = ""; // the plain path's name of the tier with "_norm" appended (bldpc_decode_normalised)
     bool profiling = false;
     // profiling: a ring of event pairs, one pair per decode call, so that a bench can average the dominant kernel over ALL of its
     // timed steps without synchronising after each (bldpc_kernel_ms_mean); ev0/ev1 point at the pair of the call in progress
@@ -361,19 +363,21 @@ extern "C" int bldpc_last_kernel_ms(bldpc_code *c, float *ms)
 // ---------------------------------------------------------------------------
 template <int VEC>
 static int run_table(bldpc_code *c, const float *y, int F, int max_iter, int length, int exit_mode, int *D, float *app,
-                     unsigned long long *flag_hist, int *itera, int *iters, hipStream_t st)
+                     unsigned long long *flag_hist, int *itera, int *iters, hipStream_t st, float alpha)
 {
     const bool early = exit_mode != BLDPC_EXIT_FIXED; // the host watches the flags: stop when every frame is flagged / has stopped
     TableArgs a;
     a.rq = (float *)c->rq.p; a.y = y; a.addr = c->d_addr; a.node_list = c->d_node_list;
     a.wv_blk = c->d_wv_blk; a.wc_blk = c->d_wc_blk;
     a.F = F; a.Z = c->Z; a.Wv = c->Wv; a.Wc = c->Wc; a.length = length;
+    a.alpha = alpha; // > 0: the normalised check-node kernel (alpha == 1.0f included)
     a.iters = (exit_mode == BLDPC_EXIT_PER_FRAME) ? iters : nullptr;
     if (a.iters) CLDPC_HIP(hipMemsetAsync(iters, 0, (size_t)F * sizeof(int), st), BLDPC_EHIP);
     int *bad = (int *)c->bad.p, *cnt = (int *)c->cnt.p;
     const dim3 blk(256);
     const unsigned gx = (unsigned)((F + VEC * 256 - 1) / (VEC * 256));
     const bool per_iter_flags = early || flag_hist;
+    void (*const cn)(TableArgs, int) = alpha > 0.0f ? k_table_cn<VEC, true> : k_table_cn<VEC, false>;
     CLDPC_HIP(hipMemsetAsync(c->rq.p, 0, (size_t)c->M * c->Wc * F * sizeof(float), st), BLDPC_EHIP); // LDPC_Decoder.cu:82
     CLDPC_HIP(hipMemsetAsync(bad, 0, (size_t)F * sizeof(int), st), BLDPC_EHIP);
     if (flag_hist) CLDPC_HIP(hipMemsetAsync(flag_hist, 0, (size_t)F * sizeof(unsigned long long), st), BLDPC_EHIP);
@@ -391,7 +395,7 @@ static int run_table(bldpc_code *c, const float *y, int F, int max_iter, int len
             hipLaunchKernelGGL(k_table_vn<VEC>, dim3(gx, (unsigned)std::min(cntn, 65535)), blk, 0, st, a, n0, cntn);
         }
         if (!last || exit_mode == BLDPC_EXIT_BATCH_GLOBAL) // the CN pass after the final VN pass is unobservable (the reference runs it)
-            hipLaunchKernelGGL(k_table_cn<VEC>, dim3(gx, (unsigned)std::min(c->M, 65535)), blk, 0, st, a, c->M);
+            hipLaunchKernelGGL(cn, dim3(gx, (unsigned)std::min(c->M, 65535)), blk, 0, st, a, c->M);
         if (per_iter_flags || last) {
             const bool need_cnt = early;
             if (need_cnt) CLDPC_HIP(hipMemsetAsync(cnt, 0, sizeof(int), st), BLDPC_EHIP);
@@ -410,8 +414,9 @@ static int run_table(bldpc_code *c, const float *y, int F, int max_iter, int len
 }
 
 static int decode_impl(bldpc_code *c, const float *y, int F, int max_iter, int length, int exit_mode, int kernel, int *D, float *app,
-                       unsigned long long *flag_hist, int *itera, int *iters, void *stream, QcStat *stat = nullptr)
+                       unsigned long long *flag_hist, int *itera, int *iters, void *stream, QcStat *stat = nullptr, float alpha = 0.0f)
 {
+    // alpha > 0: bldpc_decode_normalised -- the NORM instantiation of whatever kernel the plain call would run, on the same plan and scratch
     if (!c || !y || !D || !itera) return fail(BLDPC_EINVAL, "bldpc_decode: null argument");
     if (F <= 0 || max_iter <= 0) return fail(BLDPC_EINVAL, "bldpc_decode: F=%d max_iter=%d must be positive", F, max_iter);
     if (length == 0) length = c->K;
@@ -429,11 +434,29 @@ static int decode_impl(bldpc_code *c, const float *y, int F, int max_iter, int l
     // from the histories) and a requested flag_hist need max_iter <= 64 there.  The reference takes any maxIT, and so do the
     // table kernels: AUTO goes to them; only an explicit QC_LDS request is refused.
     const bool needs_hist = exit_mode == BLDPC_EXIT_BATCH_GLOBAL || flag_hist != nullptr;
-    if (kernel == BLDPC_KERNEL_AUTO) kernel = (qc_ok && !(needs_hist && max_iter > 64)) ? BLDPC_KERNEL_QC_LDS : BLDPC_KERNEL_TABLE;
+    QcNorm norm;
+    bool norm_ok = true; // the entry has the normalised kernel this exit mode needs
+    if (alpha > 0.0f && qc_ok && kernel != BLDPC_KERNEL_TABLE) {
+        int nvar = 0;
+        const QcVariant *vars = qc_variants(&nvar);
+        const QcPlan *qf = c->qc.pf ? c->qc.pf : &c->qc; // the plan of the per-frame passes, as in qc_decode
+        QcNormKernels k, kf;
+        auto max_lds = [&](const QcPlan *q) { return qc_kind_lists(vars[q->variant].kind) ? vars[q->variant].lds_bytes : (int)kLdsBytes; };
+        int r = qc_norm_kernels(c->qc.variant, max_lds(&c->qc), &k);
+        if (!r) r = qc_norm_kernels(qf->variant, max_lds(qf), &kf);
+        if (r) return r;
+        norm.fn = k.fn; norm.fn_pf = kf.fn_pf; norm.alpha = alpha;
+        norm_ok = exit_mode == BLDPC_EXIT_PER_FRAME ? norm.fn_pf != nullptr : norm.fn != nullptr;
+    }
+    if (kernel == BLDPC_KERNEL_AUTO)
+        kernel = (qc_ok && norm_ok && !(needs_hist && max_iter > 64)) ? BLDPC_KERNEL_QC_LDS : BLDPC_KERNEL_TABLE;
     if (kernel == BLDPC_KERNEL_QC_LDS) {
         if (!qc_ok)
             return fail(BLDPC_EUNSUPPORTED, "QC_LDS kernel unavailable for this code (%s)",
                         c->has_qc ? "message state exceeds LDS" : "built from an address table");
+        if (!norm_ok)
+            return fail(BLDPC_EUNSUPPORTED, "this code's QC_LDS entry has no normalised kernel for this exit mode; BLDPC_KERNEL_AUTO or "
+                        "BLDPC_KERNEL_TABLE run the normalised table kernels");
         if (needs_hist && max_iter > 64)
             return fail(BLDPC_EUNSUPPORTED, "QC_LDS with a flag history (BATCH_GLOBAL exit or flag_hist) supports max_iter <= 64 (got %d); "
                         "BLDPC_KERNEL_AUTO or BLDPC_KERNEL_TABLE take any max_iter", max_iter);
@@ -445,7 +468,11 @@ static int decode_impl(bldpc_code *c, const float *y, int F, int max_iter, int l
         const char *used = c->qc.name;
         int r = qc_decode(&c->qc, y, F, max_iter, length, exit_mode, D, app, flag_hist, (unsigned long long *)c->bad.p,
                           (unsigned long long *)c->cnt.p, (unsigned *)c->bits.p, (float *)c->yg.p, itera, iters, (int *)c->itw.p, st,
-                          c->profiling ? c->ev0 : nullptr, c->profiling ? c->ev1 : nullptr, stat, &used);
+                          c->profiling ? c->ev0 : nullptr, c->profiling ? c->ev1 : nullptr, stat, &used, alpha > 0.0f ? &norm : nullptr);
+        if (alpha > 0.0f) {
+            snprintf(c->norm_name, sizeof(c->norm_name), "%s_norm", used);
+            used = c->norm_name;
+        }
         c->last_kernel = used;
         return r;
     }
@@ -457,11 +484,11 @@ static int decode_impl(bldpc_code *c, const float *y, int F, int max_iter, int l
     if (c->profiling) CLDPC_HIP(hipEventRecord(c->ev0, st), BLDPC_EHIP);
     int r;
     if (F % 4 == 0 && a16) {
-        c->last_kernel = "table_vec4";
-        r = run_table<4>(c, y, F, max_iter, length, exit_mode, D, app, flag_hist, itera, iters, st);
+        c->last_kernel = alpha > 0.0f ? "table_vec4_norm" : "table_vec4";
+        r = run_table<4>(c, y, F, max_iter, length, exit_mode, D, app, flag_hist, itera, iters, st, alpha);
     } else {
-        c->last_kernel = "table_vec1";
-        r = run_table<1>(c, y, F, max_iter, length, exit_mode, D, app, flag_hist, itera, iters, st);
+        c->last_kernel = alpha > 0.0f ? "table_vec1_norm" : "table_vec1";
+        r = run_table<1>(c, y, F, max_iter, length, exit_mode, D, app, flag_hist, itera, iters, st, alpha);
     }
     if (c->profiling) CLDPC_HIP(hipEventRecord(c->ev1, st), BLDPC_EHIP);
     return r;
@@ -481,6 +508,20 @@ extern "C" int bldpc_decode_per_frame(bldpc_code *c, const float *y, int F, int 
     if (!iters) return fail(BLDPC_EINVAL, "bldpc_decode_per_frame: null iters");
     int unused = 0;
     return decode_impl(c, y, F, max_iter, length, BLDPC_EXIT_PER_FRAME, kernel, D, app, nullptr, &unused, iters, stream);
+}
+
+extern "C" int bldpc_decode_normalised(bldpc_code *c, const float *y, int F, int max_iter, float alpha, int length, int exit_mode, int kernel,
+                                       int *D, float *app, int *iters, void *stream)
+{
+    const char *who = "bldpc_decode_normalised";
+    if (!(alpha > 0.0f && alpha <= 1.0f)) return fail(BLDPC_EINVAL, "%s: alpha=%g outside (0, 1]", who, (double)alpha);
+    if (exit_mode == BLDPC_EXIT_BATCH_GLOBAL)
+        return fail(BLDPC_EINVAL, "%s: BLDPC_EXIT_BATCH_GLOBAL is not offered; use BLDPC_EXIT_FIXED or BLDPC_EXIT_PER_FRAME", who);
+    if (exit_mode != BLDPC_EXIT_FIXED && exit_mode != BLDPC_EXIT_PER_FRAME) return fail(BLDPC_EINVAL, "%s: unknown exit_mode %d", who, exit_mode);
+    if (exit_mode == BLDPC_EXIT_PER_FRAME && !iters) return fail(BLDPC_EINVAL, "%s: per-frame exit needs iters", who);
+    int unused = 0;
+    return decode_impl(c, y, F, max_iter, length, exit_mode, kernel, D, app, nullptr, &unused, exit_mode == BLDPC_EXIT_PER_FRAME ? iters : nullptr,
+                       stream, nullptr, alpha);
 }
 
 static int statistic_impl(const bldpc_code *cc, const int *D, const int *cw, int F, int length, int itera, const int *iters,

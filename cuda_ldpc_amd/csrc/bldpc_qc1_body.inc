@@ -1,6 +1,7 @@
 // bldpc_qc1_body.inc -- the body of the row kernel, expanded twice by bldpc_qc_kernel.hpp (see bldpc_qc2_body.inc):
 //   QC1_NAME k_qc, QC1_PERSIST 0: one workgroup per frame group; QC1_NAME k_qcp, QC1_PERSIST 1: persistent, per-frame exit.
-template <typename GM, bool HIST> __global__ __launch_bounds__(GM::TPB, GM::MINW) void QC1_NAME(QcArgs a)
+// NORM: normalised min-sum, every check message scaled by a.alpha behind the select of cn_out (see bldpc_qc2_body.inc)
+template <typename GM, bool HIST, bool NORM = false> __global__ __launch_bounds__(GM::TPB, GM::MINW) void QC1_NAME(QcArgs a)
 {
     constexpr int NF = GM::NF, L = GM::L, Z = GM::Z, WC = GM::WC, WV = GM::WV, G = GM::G;
     constexpr int RPT = GM::RPT, CPT = GM::CPT, MSG = GM::MSG;
@@ -340,6 +341,7 @@ template <typename GM, bool HIST> __global__ __launch_bounds__(GM::TPB, GM::MINW
                 MT Rn;
 #pragma unroll
                 for (int v = 0; v < NF; v++) msg_set<NF>(Rn, v, cn_out(msg_get<NF>(Rr[rr][pp], v), m2[v], key[v]));
+                if constexpr (NORM) Rn = Rn * a.alpha;
                 Rr[rr][pp] = Rn;
                 if constexpr (!(LOC && pp < NLR)) lds_stm_imm<NF, (rr * G * WC + pp) * Z * MSG>(rbase, Rn); // a local edge's R has no reader but this thread
             });

@@ -4,7 +4,9 @@
 //       dispatched one workgroup per pair the CUs end far apart (as the GF(q) kernels did, DESIGN 6): the grid fills the chip once
 //       and a workgroup takes pair after pair of its XCD from a counter; tables and rotated addresses are set up once.
 // GM::LOC selects the local-edge form (QcGeom2), in both expansions.
-template <typename GM, bool HIST> __global__ __launch_bounds__(GM::TPB, GM::MINW) void QC2_NAME(QcArgs a)
+// NORM: normalised min-sum (bldpc_decode_normalised).  The clamp-XOR select of cn_out maps (m1, m2) to (m2, m1) and cannot map them to
+// (alpha m2, alpha m1), so its result is scaled: fl(alpha * (+-m)) has the bits of +-fl(alpha * m), one v_pk_mul_f32 per edge and frame pair.
+template <typename GM, bool HIST, bool NORM = false> __global__ __launch_bounds__(GM::TPB, GM::MINW) void QC2_NAME(QcArgs a)
 {
     constexpr int NF = GM::NF, L = GM::L, Z = GM::Z, WC = GM::WC, WV = GM::WV, GJ = GM::GJ, ZB = GM::ZB, WCH = GM::WCH;
     constexpr int RPT = GM::RPT, CPT = GM::CPT, NCG = GM::NCG, MSG = GM::MSG;
@@ -345,6 +347,7 @@ template <typename GM, bool HIST> __global__ __launch_bounds__(GM::TPB, GM::MINW
                 v2f32 Rn;
                 Rn.x = cn_out(Rr[rr][i].x, m2f[0], key[0]);
                 Rn.y = cn_out(Rr[rr][i].y, m2f[1], key[1]);
+                if constexpr (NORM) Rn = Rn * a.alpha;
                 Rr[rr][i] = Rn;
                 if constexpr (!(LOC && i < NL)) lds_st2_imm<(r_ * GJ * WC + i) * Z * MSG>(rbase, Rn); // a local edge's R has no reader but this thread
             });

@@ -93,6 +93,7 @@ struct QcArgs {
     unsigned long long *stamps; // tools/qc_phase_probe.hip only: [nWG][QC_STAMPS] s_memtime stamps of wave 0
     int stagger;                // tools only: cycles of s_sleep for workgroups with an odd TG_ID before the loop
 #endif
+    float alpha = 1.0f;         // NORM instantiations only: the normalisation factor (bldpc_decode_normalised); the others never read it
 };
 
 template <int NF> struct Msg;
@@ -333,6 +334,7 @@ template <int NF> __global__ __launch_bounds__(256) void k_regroup_y(const float
     }
 }
 
+#ifndef BLDPC_QC_KERNELS_ONLY /* plain (non-template) kernels: defined once, in bldpc_api.hip */
 // Unpack the hard bits into the reference's D layout (int32 [N][F], frame-fastest): one thread per
 // (word w, 4 frames); reads 4 words, writes 32 rows of int4 -- stores coalesce along the frame dimension.
 // errs != nullptr: the message-bit errors of Statistic against the all-zero codeword (Simulation.cu:249-257) are counted here, from
@@ -368,12 +370,14 @@ __global__ __launch_bounds__(256) void k_expand_bits(const unsigned *bits, int *
     }
 }
 
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // Compressed-state kernel, see bldpc_qcc_kernel.hpp.  LDS: mm float2[M] | w2 uint[M] | S float[(L+1)*Z] | flag.
 // PERSIST (per-frame exit only): the grid fills the chip once and a workgroup takes frame after frame of its XCD from the counter
 // a.work[xcd], as k_qc2p / k_qcr2<PERSIST> do (frames leave after 1 ... max_iter iterations: one workgroup per frame leaves the CUs far apart)
-template <typename GM, bool HIST, bool PERSIST = false> __global__ __launch_bounds__(GM::TPB) void k_qcc(QcArgs a)
+// NORM: normalised min-sum, the two magnitudes scaled once per row where the state is written (every rebuild of R then has the scaled bits)
+template <typename GM, bool HIST, bool PERSIST = false, bool NORM = false> __global__ __launch_bounds__(GM::TPB) void k_qcc(QcArgs a)
 {
     constexpr int Z = GM::Z, U = GM::U, G = GM::G, CPT = GM::CPT, WCS = GM::WCS;
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -527,7 +531,7 @@ template <typename GM, bool HIST, bool PERSIST = false> __global__ __launch_boun
             // R_p = Sign[25]*Sign[p] * magnitude: output sign bit p = parity of all signs XOR sign p
             if (__builtin_popcount(signs) & 1) signs ^= (1u << w) - 1u;
             if (lane_on) {
-                const float nm[2] = {m1, m2};
+                const float nm[2] = {NORM ? a.alpha * m1 : m1, NORM ? a.alpha * m2 : m2};
                 lds_st<2>(lds, sidx * 8, nm);
                 const float nw[1] = {u2f(signs | ((unsigned)idx << 27))};
                 lds_st<1>(lds, off_w2 + sidx * 4, nw);
@@ -572,6 +576,7 @@ template <typename GM, bool HIST, bool PERSIST = false> __global__ __launch_boun
 #include "bldpc_qcr_kernel.hpp" // k_qcr: check states in registers, S in LDS (long blocks)
 #include "bldpc_qcr2_kernel.hpp" // k_qcr2: the same with hardware-addressed (M0 + lane) LDS accesses
 
+#ifndef BLDPC_QC_KERNELS_ONLY
 // AND of all frames' flag histories -> first iteration at which every frame's flag is set.
 __global__ __launch_bounds__(256) void k_hist_and(const unsigned long long *hist, int F, unsigned long long *out)
 {
@@ -589,6 +594,8 @@ __global__ __launch_bounds__(256) void k_iters_max(const int *iters, int F, int 
     for (int off = 32; off > 0; off >>= 1) x = max(x, __shfl_down(x, off, 64));
     if ((threadIdx.x & 63) == 0) atomicMax(out, x);
 }
+
+#endif
 
 // ---------------------------------------------------------------------------------------------
 using QcKernel = void (*)(QcArgs);
@@ -612,6 +619,41 @@ struct QcVariant { int NF, J, L, Z, WC, WV, G, MINW, threads, lds_bytes; QcKerne
     X(2,   6, 24,  96, 15, 4,  6, 2) /* J6_L24_Z96                                              */ \
     X(1,   4, 24, 256, 20, 4,  4, 4) /* J4_L24_Z256 (one frame per lane)                        */
 
+// Every entry of the table, in selection order, as a list of X-macro calls: qc_variants() below expands it into the plain kernels of
+// each entry, bldpc_norm.hip into the normalised ones of the same index.
+#define QC_VARIANT_LIST \
+        X2L(2, 4, 24, 96, 20, 4, 4, 6) /* J4_L24_Z96 (BASELINE config 2) with local edges: taken when every row is full and the matching exists */ \
+        X2(2, 4, 24, 96, 20, 4, 4, 6) /* J4_L24_Z96 (BASELINE config 2): 768 thr, 80 KB, 2 WG/CU, 6 waves/SIMD */ \
+        X2(2, 8, 24, 96, 10, 6, 4, 6) /* J8_L24_Z96: 768 thr, 80 KB, 2 WG/CU                                     */ \
+        X2(2, 12, 24, 96, 8, 6, 4, 3) /* J12_L24_Z96 (rows padded 7 -> 8): 768 thr, 92 KB                        */ \
+        X2(2, 6, 24, 96, 16, 4, 3, 3) /* J6_L24_Z96 (rows padded 15 -> 16): 576 thr, 92 KB                       */ \
+        X1L(2, 32, 64, 64, 7, 3, 16, 4) /* J32_L64_Z64 (BASELINE config 3) with local edges: every column of weight WV, the matching exists */ \
+        QC_VARIANTS(X) \
+        /* check states in registers, S in LDS (bldpc_qcr_kernel.hpp), several workgroups per CU */ \
+        XR(12, 69, 256, 256, 23, 22, 3) /* PON_LDPC J12_L69_Z256 (the reference's default, define.cuh:20-22): 69 KB, 2 WG/CU */ \
+        XR2(4, 24, 512, 512, 20, 8, 5)   /* J4_L24_Z512: 55 KB, 2 WG/CU; at most 5 wrapped blocks per (row, tile) */ \
+        XR(4, 24, 512, 512, 20, 20, 8)  /* J4_L24_Z512: 48 KB, 3 WG/CU                                                      */ \
+        /* compressed check state (bldpc_qcc_kernel.hpp): any J, L with ceil(L/G) <= CPT and row weight <= WCS */ \
+        XC(256, 256, 4, 18, 24) /* PON_LDPC J12_L69_Z256 (the reference's default, define.cuh:20-22)       */ \
+        XC(160, 192, 5, 12, 24) /* the Z = 160 family, J10 ... J48, L60                                   */ \
+        XC(512, 512, 2, 12, 24) /* J4_L24_Z512                                                            */ \
+        /* lifting sizes outside the reference's matrix set (its users swap matrices by editing define.cuh): the same \
+         * generic kernel, any J <= 62 and L <= CPT*G whose states fit LDS; everything else runs on the table kernels */ \
+        XC(64, 64, 16, 8, 24)   /* Z =  64: L <= 128 */ \
+        XC(96, 128, 8, 12, 24)  /* Z =  96: L <=  96 */ \
+        XC(128, 128, 8, 12, 24) /* Z = 128: L <=  96 */ \
+        XC(192, 192, 5, 16, 24) /* Z = 192: L <=  80 */ \
+        XC(320, 320, 3, 24, 24) /* Z = 320: L <=  72 */ \
+        XC(384, 384, 2, 32, 24) /* Z = 384: L <=  64 */ \
+        XC(640, 640, 1, 40, 24) /* Z = 640: L <=  40 */ \
+        XC(1024, 1024, 1, 32, 24) /* Z = 1024: L <= 32 */ \
+        /* check states in registers, S with halos in LDS, hardware-addressed accesses (bldpc_qcr2_kernel.hpp) */ \
+        XR2(15, 30, 1280, 768, 8, 10, 2) /* J15_L30_Z1280 (BASELINE config 4): 157.5 KB; at most 2 wrapped blocks per (row, tile) */ \
+        XR2(15, 30, 1280, 768, 8, 10, 3) /* the same shape with other shifts: at most 3 */ \
+        /* check states in registers, S in LDS (bldpc_qcr_kernel.hpp): long blocks with 4 N <= LDS */ \
+        XR(15, 30, 1280, 768, 8, 7, 10) /* J15_L30_Z1280 (BASELINE config 4): 12 waves, 8 of them cover 2 tiles of Z (5 tiles per SIMD) */
+
+#ifndef BLDPC_QC_KERNELS_ONLY /* bldpc_norm.hip takes the kernels and the list above, not the plain table and the host side */
 inline const QcVariant *qc_variants(int *count)
 {
 #define X(NF, J, L, Z, WC, WV, G, MINW)                                                                  \
@@ -646,36 +688,7 @@ inline const QcVariant *qc_variants(int *count)
     {1, J, L, Z, WCS, 31, 0, 2, TPB, 0, k_qcr2<Qcr2Geom<J, L, Z, TPB, WCS, YB, NG>, false>,                    \
      k_qcr2<Qcr2Geom<J, L, Z, TPB, WCS, YB, NG>, true>, "regstate-halo", QcKind::REGSTATE_HALO, 0, NG, 2, k_qcr2<Qcr2Geom<J, L, Z, TPB, WCS, YB, NG>, true, true>},
     static const QcVariant v[] = {
-        X2L(2, 4, 24, 96, 20, 4, 4, 6) /* J4_L24_Z96 (BASELINE config 2) with local edges: taken when every row is full and the matching exists */
-        X2(2, 4, 24, 96, 20, 4, 4, 6) /* J4_L24_Z96 (BASELINE config 2): 768 thr, 80 KB, 2 WG/CU, 6 waves/SIMD */
-        X2(2, 8, 24, 96, 10, 6, 4, 6) /* J8_L24_Z96: 768 thr, 80 KB, 2 WG/CU                                     */
-        X2(2, 12, 24, 96, 8, 6, 4, 3) /* J12_L24_Z96 (rows padded 7 -> 8): 768 thr, 92 KB                        */
-        X2(2, 6, 24, 96, 16, 4, 3, 3) /* J6_L24_Z96 (rows padded 15 -> 16): 576 thr, 92 KB                       */
-        X1L(2, 32, 64, 64, 7, 3, 16, 4) /* J32_L64_Z64 (BASELINE config 3) with local edges: every column of weight WV, the matching exists */
-        QC_VARIANTS(X)
-        /* check states in registers, S in LDS (bldpc_qcr_kernel.hpp), several workgroups per CU */
-        XR(12, 69, 256, 256, 23, 22, 3) /* PON_LDPC J12_L69_Z256 (the reference's default, define.cuh:20-22): 69 KB, 2 WG/CU */
-        XR2(4, 24, 512, 512, 20, 8, 5)   /* J4_L24_Z512: 55 KB, 2 WG/CU; at most 5 wrapped blocks per (row, tile) */
-        XR(4, 24, 512, 512, 20, 20, 8)  /* J4_L24_Z512: 48 KB, 3 WG/CU                                                      */
-        /* compressed check state (bldpc_qcc_kernel.hpp): any J, L with ceil(L/G) <= CPT and row weight <= WCS */
-        XC(256, 256, 4, 18, 24) /* PON_LDPC J12_L69_Z256 (the reference's default, define.cuh:20-22)       */
-        XC(160, 192, 5, 12, 24) /* the Z = 160 family, J10 ... J48, L60                                   */
-        XC(512, 512, 2, 12, 24) /* J4_L24_Z512                                                            */
-        /* lifting sizes outside the reference's matrix set (its users swap matrices by editing define.cuh): the same
-         * generic kernel, any J <= 62 and L <= CPT*G whose states fit LDS; everything else runs on the table kernels */
-        XC(64, 64, 16, 8, 24)   /* Z =  64: L <= 128 */
-        XC(96, 128, 8, 12, 24)  /* Z =  96: L <=  96 */
-        XC(128, 128, 8, 12, 24) /* Z = 128: L <=  96 */
-        XC(192, 192, 5, 16, 24) /* Z = 192: L <=  80 */
-        XC(320, 320, 3, 24, 24) /* Z = 320: L <=  72 */
-        XC(384, 384, 2, 32, 24) /* Z = 384: L <=  64 */
-        XC(640, 640, 1, 40, 24) /* Z = 640: L <=  40 */
-        XC(1024, 1024, 1, 32, 24) /* Z = 1024: L <= 32 */
-        /* check states in registers, S with halos in LDS, hardware-addressed accesses (bldpc_qcr2_kernel.hpp) */
-        XR2(15, 30, 1280, 768, 8, 10, 2) /* J15_L30_Z1280 (BASELINE config 4): 157.5 KB; at most 2 wrapped blocks per (row, tile) */
-        XR2(15, 30, 1280, 768, 8, 10, 3) /* the same shape with other shifts: at most 3 */
-        /* check states in registers, S in LDS (bldpc_qcr_kernel.hpp): long blocks with 4 N <= LDS */
-        XR(15, 30, 1280, 768, 8, 7, 10) /* J15_L30_Z1280 (BASELINE config 4): 12 waves, 8 of them cover 2 tiles of Z (5 tiles per SIMD) */
+        QC_VARIANT_LIST
     };
 #undef X
 #undef X2
@@ -693,7 +706,10 @@ constexpr size_t kLdsBytes = 160 * 1024;
 static unsigned long long *g_qc_stamps = nullptr;
 static int g_qc_stagger = 0;
 #endif
+#endif // BLDPC_QC_KERNELS_ONLY
 
 } // namespace cldpc
 
+#ifndef BLDPC_QC_KERNELS_ONLY
 #include "bldpc_qc_plan.hpp" // the host side: plan, tables, launch, decode
+#endif

@@ -593,10 +593,19 @@ inline int qc_regroup(const QcPlan *q, const float *y, float *yg, int F, hipStre
     return BLDPC_OK;
 }
 
+// bldpc_decode_normalised: the same plan, tables and launch with the NORM instantiation of the plan's kernel (bldpc_norm.hip).
+// fn: the kernel of the plan's own entry (fixed iterations); fn_pf: the PERSISTENT per-frame kernel of the entry that serves the
+// per-frame passes (the nested plan's where there is one).  The caller checks that the one the exit mode needs is not null.
+struct QcNorm {
+    QcKernel fn = nullptr, fn_pf = nullptr;
+    float alpha = 1.0f;
+};
+
 // y here is the regrouped buffer produced by qc_regroup.
 inline int qc_launch(const QcPlan *q, const float *y, int F, int max_iter, int length, int *D, float *app,
                      unsigned long long *hist, unsigned *bits, hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr,
-                     int *iters = nullptr, bool expand = true, int *work = nullptr, QcStat *stat = nullptr, bool y_in_place = false)
+                     int *iters = nullptr, bool expand = true, int *work = nullptr, QcStat *stat = nullptr, bool y_in_place = false,
+                     const QcNorm *norm = nullptr)
 {
     int nvar = 0;
     const QcVariant &v = qc_variants(&nvar)[q->variant];
@@ -620,6 +629,16 @@ inline int qc_launch(const QcPlan *q, const float *y, int F, int max_iter, int l
         fn = v.fn_pf;
         grid = (unsigned)q->persist_grid;
     }
+    if (norm) {
+        a.alpha = norm->alpha;
+        fn = norm->fn;
+        if (a.per_frame) { // the persistent form at every batch size: it takes any grid that is a multiple of 8
+            CLDPC_HIP(hipMemsetAsync(work, 0, 8 * sizeof(int), st), BLDPC_EHIP);
+            a.work = work;
+            fn = norm->fn_pf;
+            if (q->persist_grid > 0 && !q->no_persist) grid = std::min(grid, (unsigned)q->persist_grid);
+        }
+    }
     if (ev0) (void)hipEventRecord(ev0, st);
     hipLaunchKernelGGL(fn, dim3(grid), dim3(v.threads), q->lds_bytes, st, a);
     if (ev1) (void)hipEventRecord(ev1, st);
@@ -638,7 +657,7 @@ inline int qc_launch(const QcPlan *q, const float *y, int F, int max_iter, int l
 inline int qc_decode(const QcPlan *q, const float *y, int F, int max_iter, int length, int exit_mode, int *D, float *app,
                      unsigned long long *flag_hist, unsigned long long *hist_ws, unsigned long long *and_ws, unsigned *bits,
                      float *yg, int *itera, int *iters, int *iters_ws, hipStream_t st, hipEvent_t ev0 = nullptr,
-                     hipEvent_t ev1 = nullptr, QcStat *stat = nullptr, const char **used = nullptr)
+                     hipEvent_t ev1 = nullptr, QcStat *stat = nullptr, const char **used = nullptr, const QcNorm *norm = nullptr)
 {
     const QcPlan *qf = q->pf ? q->pf : q; // the plan of the per-frame passes
     if (used) *used = (exit_mode == BLDPC_EXIT_PER_FRAME) ? qf->name : q->name;
@@ -654,11 +673,11 @@ inline int qc_decode(const QcPlan *q, const float *y, int F, int max_iter, int l
     }
     if (exit_mode == BLDPC_EXIT_FIXED) {
         *itera = max_iter;
-        return qc_launch(q, y, F, max_iter, length, D, app, flag_hist, bits, st, ev0, ev1, nullptr, true, nullptr, stat, in_place);
+        return qc_launch(q, y, F, max_iter, length, D, app, flag_hist, bits, st, ev0, ev1, nullptr, true, nullptr, stat, in_place, norm);
     }
     if (exit_mode == BLDPC_EXIT_PER_FRAME) { // every workgroup leaves when its own frames have stopped; nothing to wait for
         *itera = max_iter;
-        return qc_launch(qf, y, F, max_iter, length, D, app, flag_hist ? flag_hist : hist_ws, bits, st, ev0, ev1, iters, true, (int *)and_ws, stat, in_place);
+        return qc_launch(qf, y, F, max_iter, length, D, app, flag_hist ? flag_hist : hist_ws, bits, st, ev0, ev1, iters, true, (int *)and_ws, stat, in_place, norm);
     }
     // Reference rule (LDPC_Decoder.cu:150-153): stop after the first iteration at which ALL frames are flagged.  No
     // workgroup can know that iteration while it runs, so it is found first and the batch then decoded with exactly that
@@ -668,6 +687,7 @@ inline int qc_decode(const QcPlan *q, const float *y, int F, int max_iter, int l
     //   pass 2  `run` = m iterations with the flag history on: if every frame is flagged at some iteration <= run (usually
     //           exactly at m) that is the stop iteration -- replayed if it is not `run` itself.  Otherwise a frame has lost
     //           its flag again: double `run` and repeat; `run` = max_iter ends the search.
+    if (norm) return fail(BLDPC_EINVAL, "the normalised kernels take the fixed and the per-frame exit");
     if (max_iter > 64) return fail(BLDPC_EUNSUPPORTED, "QC_LDS with BATCH_GLOBAL exit supports max_iter <= 64 (got %d)", max_iter);
     unsigned long long *hist = flag_hist ? flag_hist : hist_ws;
     // A batch that holds a frame which never passes costs the per-frame pass for nothing (its answer is max_iter); sweeps

@@ -50,7 +50,7 @@ template <int J_, int L_, int Z_, int TPB_, int WCS_, int YB_, int NG_> struct Q
 };
 
 
-template <typename GM, bool HIST, int NZ>
+template <typename GM, bool HIST, int NZ, bool NORM>
 __device__ __forceinline__ void qcr2_iterations(const QcArgs &a, char *lds, int *lds_flag, const __amdgpu_buffer_rsrc_t yrs, float (&S0)[GM::ZR],
                                                 unsigned long long &hist, int &stop)
 {
@@ -144,7 +144,7 @@ __device__ __forceinline__ void qcr2_iterations(const QcArgs &a, char *lds, int 
                 const int idx = WCS - 1 - (int)__builtin_ctz(lower | (1u << (WCS - 1)));
                 // R_p = Sign[25]*Sign[p] * magnitude: output sign bit p = parity of all signs XOR sign p
                 if (__builtin_popcount(signs) & 1) signs ^= (1u << WCS) - 1u;
-                m1[j][z] = n1; m2[j][z] = n2;
+                m1[j][z] = NORM ? a.alpha * n1 : n1; m2[j][z] = NORM ? a.alpha * n2 : n2; // NORM: R = +-fl(alpha * min), scaled once per state
                 w2[j][z] = signs | ((unsigned)idx << 27);
                 asm volatile("" : "+v"(m1[j][z]), "+v"(m2[j][z]), "+v"(w2[j][z])); // the state is complete here (see k_qcr)
             }
@@ -277,7 +277,7 @@ __device__ __forceinline__ void qcr2_iterations(const QcArgs &a, char *lds, int 
 // LDS: S float[L][Z + 64] | 64 x +inf | flags.
 // PERSIST (per-frame exit only): the grid fills the chip once and a workgroup takes frame after frame of its XCD from the counter
 // a.work[xcd] -- frames leave after 1 ... max_iter iterations, and one workgroup per frame leaves the CUs far apart (see k_qc2p)
-template <typename GM, bool HIST, bool PERSIST = false> __global__ __launch_bounds__(GM::TPB) void k_qcr2(QcArgs a)
+template <typename GM, bool HIST, bool PERSIST = false, bool NORM = false> __global__ __launch_bounds__(GM::TPB) void k_qcr2(QcArgs a)
 {
     constexpr int Z = GM::Z, TPB = GM::TPB, ZR = GM::ZR, N = GM::L * Z;
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -330,8 +330,8 @@ template <typename GM, bool HIST, bool PERSIST = false> __global__ __launch_boun
     }
 
     if (stop) {
-    } else if (GM::RAGGED && !zlast) qcr2_iterations<GM, HIST, (GM::RAGGED ? ZR - 1 : ZR)>(a, lds, lds_flag, yrs, S0, hist, stop);
-    else qcr2_iterations<GM, HIST, ZR>(a, lds, lds_flag, yrs, S0, hist, stop);
+    } else if (GM::RAGGED && !zlast) qcr2_iterations<GM, HIST, (GM::RAGGED ? ZR - 1 : ZR), NORM>(a, lds, lds_flag, yrs, S0, hist, stop);
+    else qcr2_iterations<GM, HIST, ZR, NORM>(a, lds, lds_flag, yrs, S0, hist, stop);
     const int last = stop ? stop : a.max_iter;
 
     // ---- outputs from S of the last iteration ----

@@ -52,7 +52,7 @@ typedef __attribute__((address_space(4))) const unsigned qcr_const_u32;
 
 // Iterations 1 .. max_iter-1 for a wave that covers NZ tiles of the circulant.  S0[z]: a-posteriori value of
 // variable (LC, tid + z*TPB), kept in registers across the whole decode.
-template <typename GM, bool HIST, int NZ>
+template <typename GM, bool HIST, int NZ, bool NORM>
 __device__ __forceinline__ void qcr_iterations(const QcArgs &a, char *lds, int *lds_flag, const __amdgpu_buffer_rsrc_t yrs,
                                                float (&S0)[GM::ZR], unsigned long long &hist, int &stop)
 {
@@ -159,7 +159,7 @@ __device__ __forceinline__ void qcr_iterations(const QcArgs &a, char *lds, int *
                 const int idx = WCS - 1 - (int)__builtin_ctz(lower | (1u << (WCS - 1)));
                 // R_p = Sign[25]*Sign[p] * magnitude: output sign bit p = parity of all signs XOR sign p
                 if (__builtin_popcount(signs) & 1) signs ^= (1u << WCS) - 1u;
-                m1[j][z] = n1; m2[j][z] = n2;
+                m1[j][z] = NORM ? a.alpha * n1 : n1; m2[j][z] = NORM ? a.alpha * n2 : n2; // NORM: R = +-fl(alpha * min), scaled once per state
                 w2[j][z] = signs | ((unsigned)idx << 27);
                 // the state is complete HERE: three registers, not the chain of values it was computed from (left alone
                 // the compiler sinks the min2 chain into phase 2, where its inputs have to be spilled to survive)
@@ -267,7 +267,7 @@ __device__ __forceinline__ void qcr_iterations(const QcArgs &a, char *lds, int *
 
 // LDS: S float[N] | flag.
 // PERSIST (per-frame exit only): frames of this XCD from the counter a.work[xcd], see k_qcr2 / k_qc2p
-template <typename GM, bool HIST, bool PERSIST = false> __global__ __launch_bounds__(GM::TPB) void k_qcr(QcArgs a)
+template <typename GM, bool HIST, bool PERSIST = false, bool NORM = false> __global__ __launch_bounds__(GM::TPB) void k_qcr(QcArgs a)
 {
     constexpr int Z = GM::Z, TPB = GM::TPB, ZR = GM::ZR, N = GM::L * Z;
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -316,8 +316,8 @@ template <typename GM, bool HIST, bool PERSIST = false> __global__ __launch_boun
     }
 
     if (stop) {
-    } else if (GM::RAGGED && !zlast) qcr_iterations<GM, HIST, (GM::RAGGED ? ZR - 1 : ZR)>(a, lds, lds_flag, yrs, S0, hist, stop);
-    else qcr_iterations<GM, HIST, ZR>(a, lds, lds_flag, yrs, S0, hist, stop);
+    } else if (GM::RAGGED && !zlast) qcr_iterations<GM, HIST, (GM::RAGGED ? ZR - 1 : ZR), NORM>(a, lds, lds_flag, yrs, S0, hist, stop);
+    else qcr_iterations<GM, HIST, ZR, NORM>(a, lds, lds_flag, yrs, S0, hist, stop);
     const int last = stop ? stop : a.max_iter;
 
     // ---- outputs from S of the last iteration ----

@@ -55,6 +55,7 @@ struct TableArgs {
     const int *iters;       // per-frame exit: [F] iteration at which the frame stopped, 0 = still running (nullptr = off);
                             // a stopped frame keeps the D / app columns of that iteration
     int F, Z, Wv, Wc, length;
+    float alpha = 1.0f;     // k_table_cn<VEC, true> only: the normalisation factor
 };
 
 // Variable-node pass over nodes node_list[n0 .. n0+count) (LDPC_Decoder.cu:172-211).
@@ -127,7 +128,8 @@ template <int VEC> __global__ __launch_bounds__(256) void k_table_vn(TableArgs a
 
 // Check-node pass over all M rows (LDPC_Decoder.cu:262-315).
 // grid = (ceil(F / (VEC*256)), min(M, 65535)); block = 256.
-template <int VEC> __global__ __launch_bounds__(256) void k_table_cn(TableArgs a, int M)
+// NORM: normalised min-sum, R_i = +-fl(alpha * magnitude): cn_out's result scaled (the product keeps the sign bit).
+template <int VEC, bool NORM = false> __global__ __launch_bounds__(256) void k_table_cn(TableArgs a, int M)
 {
     const int f = (blockIdx.x * 256 + threadIdx.x) * VEC;
     if (f >= a.F) return;
@@ -156,6 +158,10 @@ template <int VEC> __global__ __launch_bounds__(256) void k_table_cn(TableArgs a
                 float R[VEC];
 #pragma unroll
                 for (int v = 0; v < VEC; v++) R[v] = cn_out(Q[i][v], acc[v].m2, key[v]);
+                if (NORM) {
+#pragma unroll
+                    for (int v = 0; v < VEC; v++) R[v] = a.alpha * R[v];
+                }
                 vstore<VEC>(row + (size_t)i * a.F, R);
             }
     }

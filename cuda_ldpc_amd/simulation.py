@@ -29,6 +29,9 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
     size), decodes them with a fixed iteration count, replaces the flag row of D by the syndrome check and counts errors
     against the sent CodeWord.  The flooding decoders' early exit assumes the zero word, so PN_Message=1 needs EXIT_FIXED there.
 
+    schedule="flooding" with alpha != 1.0 decodes with the normalised flooding kernels (LDPC_Decoder_GPU(alpha=alpha)): EXIT_FIXED or
+    EXIT_PER_FRAME; PN_Message=1 still needs EXIT_FIXED, the prefix rule tests for the zero word.
+
     schedule="layered" decodes with LDPC_Decoder_Layered_GPU (normalisation factor `alpha`; EXIT_FIXED or EXIT_PER_FRAME, `kernel`
     is not used).  stop_rule defaults to STOP_SYNDROME with PN_Message=1 and to STOP_PREFIX otherwise; with STOP_SYNDROME the flag
     row already means "valid codeword", so random codewords run with EXIT_PER_FRAME and no separate Syndrome call.
@@ -42,8 +45,11 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
     if schedule not in ("flooding", "layered"):
         raise ValueError("schedule must be 'flooding' or 'layered'")
     layered = schedule == "layered"
-    if not layered and (alpha != 1.0 or stop_rule is not None):
-        raise ValueError("alpha and stop_rule belong to schedule='layered'")
+    if not layered and stop_rule is not None:
+        raise ValueError("stop_rule belongs to schedule='layered'")
+    norm = not layered and alpha != 1.0  # normalised min-sum on the flooding decoders (LDPC_Decoder_GPU(alpha=...))
+    if norm and exit_mode not in (EXIT_FIXED, EXIT_PER_FRAME):
+        raise ValueError("schedule='flooding' with alpha takes EXIT_FIXED or EXIT_PER_FRAME")
     if layered:
         if stop_rule is None:
             stop_rule = STOP_SYNDROME if PN_Message else STOP_PREFIX
@@ -104,11 +110,16 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
             st = torch.cuda.current_stream(device).cuda_stream
             check(lib.bldpc_statistic_per_frame(code._h, _dev_ptr(D), _dev_ptr(cw), count, length, _dev_ptr(r["iters"]), _dev_ptr(dev_cnt), st),
                   "Statistic")
-        elif count and PN_Message:
-            r = LDPC_Decoder_GPU(code, yd, max_iter=maxIT, length=length, exit_mode=EXIT_FIXED, kernel=kernel, D=D)
-            Syndrome(code, D, into_flag_row=True)  # flag row: "valid codeword" instead of "first `length` bits zero"
+        elif count and (PN_Message or norm):
+            r = LDPC_Decoder_GPU(code, yd, max_iter=maxIT, length=length, exit_mode=exit_mode, kernel=kernel, D=D, alpha=alpha if norm else None)
+            if PN_Message:
+                Syndrome(code, D, into_flag_row=True)  # flag row: "valid codeword" instead of "first `length` bits zero"
             st = torch.cuda.current_stream(device).cuda_stream
-            check(lib.bldpc_statistic(code._h, _dev_ptr(D), _dev_ptr(cw), count, length, r["iteraTime"], _dev_ptr(dev_cnt), st), "Statistic")
+            if r.get("iters") is not None:
+                check(lib.bldpc_statistic_per_frame(code._h, _dev_ptr(D), _dev_ptr(cw), count, length, _dev_ptr(r["iters"]), _dev_ptr(dev_cnt), st),
+                      "Statistic")
+            else:
+                check(lib.bldpc_statistic(code._h, _dev_ptr(D), _dev_ptr(cw), count, length, r["iteraTime"], _dev_ptr(dev_cnt), st), "Statistic")
         elif count:
             Decode_Statistic(code, yd, dev_cnt, max_iter=maxIT, length=length, exit_mode=exit_mode, kernel=kernel, D=D)  # Simulation.cu:143-145
         sharding.allreduce_counters(dev_cnt, dist)

@@ -256,6 +256,48 @@ int bldpc_decode_layered(bldpc_code *code, const float *Channel_Out, int F, int 
 int bldpc_decode_layered_host(int J, int L, int Z, const int *H, const float *Channel_Out, int F, int max_iter, float alpha,
                               int length, int exit_mode, int stop_rule, int *D, float *app, int *iters);
 
+/* -- normalised min-sum on the flooding decoders (not in the reference, whose flooding min-sum is un-normalised) ----- */
+
+/* The flooding iteration exactly as bldpc_decode runs it, with one change in the check-node update.  Semantics, IEEE fp32
+ * without fused multiply-add and without flushing denormals:
+ *
+ *   state per frame: one message word per edge, R = +0.0f (Memory_RQ = 0, LDPC_Decoder.cu:82).
+ *   one iteration:
+ *     1. variable nodes (LDPC_Decoder.cu:188-210): for every variable v with edges e_0 .. e_{w-1} in ascending block row,
+ *        S[v] = (((0 + R_0) + R_1) + ...) + Channel_Out[v];  Q_i = S[v] - R_i replaces R_i on every edge
+ *     2. hard bits d[v] = S[v] < 0;  the frame's flag = no d[v] is 1 among the first `length` variables (0 means K = N - M)
+ *     3. the decoder stops here after max_iter iterations, and a frame under per-frame exit at its first set flag: the
+ *        check-node pass after the last variable-node pass is not executed
+ *     4. check nodes (:279-314): for every check with edges i = 0 .. w-1 in ascending block column,
+ *        sg_i = Q_i < 0 ? -1 : +1;  P = product of all sg_i;  a_i = |Q_i|;  m1 <= m2 the two smallest a_i with multiplicity;
+ *        first = lowest i with a_i == m1
+ *        mag_i = alpha * (i == first ? m2 : m1)          (one fp32 multiplication: the only change)
+ *        R_i = (float)(P * sg_i) * mag_i  replaces Q_i   (a multiplication by +-1: the bits of +-mag_i)
+ *
+ *   With alpha == 1.0f the results are those of bldpc_decode (BLDPC_EXIT_FIXED) and bldpc_decode_per_frame bit for bit:
+ *   x * 1.0f is exact, signed zeros and denormals included.  An underflowing product makes R_i = +-0 where the minimum is not 0;
+ *   S is still never -0.0f (it is accumulated from +0.0f) and Q = S - R never is either.
+ *
+ *   exit_mode  BLDPC_EXIT_FIXED or BLDPC_EXIT_PER_FRAME (iters[f] and column f of D and app as bldpc_decode_per_frame returns them).
+ *              BLDPC_EXIT_BATCH_GLOBAL is refused (BLDPC_EINVAL), as the layered decoder refuses it.
+ *   alpha      normalisation factor in (0, 1]; outside it or not finite: BLDPC_EINVAL
+ *   iters      device int32 [F] (out) with per-frame exit, where NULL is refused (BLDPC_EINVAL); not written with BLDPC_EXIT_FIXED
+ * All other arguments, layouts, scratch and asynchrony are those of bldpc_decode and bldpc_decode_per_frame; there is no flag
+ * history.  The call always runs the normalised instantiations of the kernels, at alpha == 1.0f too, and bldpc_last_kernel
+ * reports the name the plain path reports for that tier with "_norm" appended.  Codes built from an address table are accepted and
+ * run the table kernels.  One corner has no fused normalised kernel: the per-frame exit of a row-local plan WITHOUT a nested plain
+ * plan (a pinned entry, BLDPC_LOCAL_PER_FRAME); BLDPC_KERNEL_AUTO runs the table kernels there ("table_vec4_norm"), an explicit
+ * BLDPC_KERNEL_QC_LDS is refused with BLDPC_EUNSUPPORTED. */
+int bldpc_decode_normalised(bldpc_code *code, const float *Channel_Out, int F, int max_iter, float alpha, int length,
+                            int exit_mode, int kernel, int *D, float *app, int *iters, void *stream);
+
+/* The same decoder on the host for QC codes, all pointers host, no device needed: plain C++ that follows the steps above
+ * literally (one R per edge), frames over at most 16 threads.  It is the statement of the semantics inside the product, as
+ * bldpc_decode_layered_host is for the layered decoder, and what the normalised kernels are tested against bit for bit.  Block
+ * rows of weight < 2 are refused (BLDPC_EUNSUPPORTED).  iters may be NULL with BLDPC_EXIT_FIXED.  NOT a fast path. */
+int bldpc_decode_normalised_host(int J, int L, int Z, const int *H, const float *Channel_Out, int F, int max_iter, float alpha,
+                                 int length, int exit_mode, int *D, float *app, int *iters);
+
 /* -- binary codes over QAM: bit mapper and max-log soft demapper (not in the reference, whose binary channel is BPSK) -- */
 
 /* Bit-interleaved coded modulation without the interleaver: m consecutive codeword bits label one of q = 2^m constellation

@@ -44,7 +44,8 @@ def main():
     ap.add_argument("--pn-message", action="store_true", help="send random codewords (PN_Message 1, define.cuh:26); binary: needs --fixed")
     ap.add_argument("--pn-seed", type=int, default=1, help="--pn-message: seed of the message stream (bldpc_encode_random / nbldpc_encode_random)")
     ap.add_argument("--layered", action="store_true", help="binary: row-layered normalised min-sum (bldpc_decode_layered); with --fixed or --per-frame")
-    ap.add_argument("--alpha", type=float, default=1.0, help="--layered: normalisation factor in (0, 1]")
+    ap.add_argument("--alpha", type=float, default=1.0, help="binary: normalisation factor in (0, 1]; with --layered the layered decoder's, without it "
+                    "normalised min-sum on the flooding decoders (with --fixed or --per-frame)")
     ap.add_argument("--stop-rule", choices=["prefix", "syndrome"], default=None,
                     help="--layered: stop rule / meaning of the flag row (default: syndrome with --pn-message, else prefix)")
     ap.add_argument("--as-written", action="store_true", help="decode on the reference's Transform_H table as written (SURVEY F3)")
@@ -54,9 +55,11 @@ def main():
             ap.error("--layered needs a QC code and --fixed or --per-frame")
         if args.pn_message and args.per_frame and args.stop_rule == "prefix":
             ap.error("--pn-message --per-frame needs --stop-rule syndrome (the prefix rule tests for the all-zero word)")
-    elif args.alpha != 1.0 or args.stop_rule is not None:
-        ap.error("--alpha and --stop-rule belong to the binary sweep with --layered")
-    elif args.which == "binary" and args.pn_message and (not args.fixed or args.as_written):
+    elif args.stop_rule is not None or (args.alpha != 1.0 and args.which != "binary"):
+        ap.error("--stop-rule belongs to the binary sweep with --layered, --alpha to the binary sweep")
+    elif args.alpha != 1.0 and not (args.fixed or args.per_frame):
+        ap.error("--alpha without --layered (normalised flooding min-sum) needs --fixed or --per-frame")
+    if args.which == "binary" and not args.layered and args.pn_message and (not args.fixed or args.as_written):
         ap.error("--pn-message needs the binary sweep with --fixed (the decoders' early exit tests for the all-zero word) on a QC code")
     if args.which == "binary" and args.qam != 2 and not (args.pn_message and args.device_channel):
         ap.error("binary --qam %d needs --pn-message (a QAM channel is not symmetric: the all-zero word is not representative) and "
@@ -90,6 +93,8 @@ def main():
         else:
             code = C.BinaryCode.from_blockh(args.matrix, args.J, args.L, args.Z)
         lay = {}
+        if not args.layered and args.alpha != 1.0:
+            lay = dict(alpha=args.alpha)
         if args.layered:
             stop = args.stop_rule or ("syndrome" if args.pn_message else "prefix")
             lay = dict(schedule="layered", alpha=args.alpha, stop_rule=C.STOP_SYNDROME if stop == "syndrome" else C.STOP_PREFIX)
@@ -99,7 +104,8 @@ def main():
         if rank == 0:
             print("# %s N=%d K=%d, %s%s%s, maxIT=%d, batch=%d x %d GPU(s)%s" % (os.path.basename(args.matrix), code.N, code.K,
                   "" if args.qam == 2 else "%d-QAM (Gray) %d bits per point, max-log demapper, Eb/N0, " % (args.qam, args.qam.bit_length() - 1),
-                  "layered min-sum alpha=%g stop=%s, " % (args.alpha, stop) if args.layered else "",
+                  "layered min-sum alpha=%g stop=%s, " % (args.alpha, stop) if args.layered else
+                  ("normalised flooding min-sum alpha=%g, " % args.alpha if args.alpha != 1.0 else ""),
                   "fixed iterations" if args.fixed else ("per-frame early exit" if args.per_frame else "batch-global early exit"),
                   args.iters or (25 if args.layered else 50), args.batch, world,
                   ", random codewords (PN seed %d, K'=%d), syndrome flag" % (args.pn_seed, code.K_info) if args.pn_message else ""))
