@@ -62,6 +62,17 @@ lib.bldpc_qam_map.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
 lib.bldpc_qam_demap.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_float, c_int, c_int, c_void_p, c_void_p]
 lib.bldpc_qam_map_host.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p]
 lib.bldpc_qam_demap_host.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_float, c_int, c_int, c_void_p]
+lib.bldpc_rm_create.argtypes = [c_int, c_void_p, c_int, c_void_p, c_int, ctypes.POINTER(c_void_p)]
+lib.bldpc_rm_destroy.argtypes = [c_void_p]
+lib.bldpc_rm_dims.argtypes = [c_void_p, c_void_p]
+lib.bldpc_rm_tx_pos.argtypes = [c_void_p, c_void_p]
+lib.bldpc_rm_select.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p]
+lib.bldpc_rm_recover.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_float, c_void_p, c_void_p]
+lib.bldpc_rm_awgn_channel_device.argtypes = [c_void_p, c_void_p, ctypes.c_float, c_void_p, c_int, ctypes.c_float, c_void_p, c_void_p]
+lib.bldpc_rm_select_host.argtypes = [c_void_p, c_void_p, c_int, c_void_p]
+lib.bldpc_rm_recover_host.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_float, c_void_p]
+lib.bldpc_rm_awgn_channel_host.argtypes = [c_void_p, c_void_p, ctypes.c_float, c_void_p, c_int, ctypes.c_float, c_void_p]
+lib.bldpc_rm_encode_random.argtypes = [c_void_p, c_void_p, ctypes.c_ulonglong, ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p]
 lib.bldpc_sigma.restype = ctypes.c_float
 lib.bldpc_sigma.argtypes = [ctypes.c_float, c_int, ctypes.c_float]
 

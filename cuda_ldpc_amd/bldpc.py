@@ -278,12 +278,15 @@ def Encode(code, msg, CodeWord=None, stream=None):
     return CodeWord
 
 
-def PN_CodeWords(code, seed, F, first_frame=0, want_msg=False, device=None, CodeWord=None, stream=None):
+def PN_CodeWords(code, seed, F, first_frame=0, want_msg=False, device=None, CodeWord=None, stream=None, rate_match=None):
     """bldpc_encode_random: the codewords of frames first_frame .. first_frame+F-1 of the message stream `seed`
     (counter-based rule of bldpc.h, mirrored by pn_messages below).  Returns CodeWord int32 [N, F] on the device, or
-    (CodeWord, msg [K', F]) with want_msg."""
+    (CodeWord, msg [K', F]) with want_msg.  rate_match (a RateMatch over the code's N): bldpc_rm_encode_random, every message bit on
+    a shortened position forced to 0; a shortened position outside code.info_positions is refused."""
     if F <= 0 or first_frame < 0:
         raise ValueError("F must be positive and first_frame >= 0")
+    if rate_match is not None and rate_match.N != code.N:
+        raise ValueError("rate_match is over N=%d positions, the code has N=%d" % (rate_match.N, code.N))
     device = device or torch.device("cuda", torch.cuda.current_device())
     if CodeWord is None:
         CodeWord = torch.empty((code.N, F), dtype=torch.int32, device=device)
@@ -291,8 +294,12 @@ def PN_CodeWords(code, seed, F, first_frame=0, want_msg=False, device=None, Code
         _check_cw(CodeWord, code.N, F, device)
     msg = torch.empty((code.K_info, F), dtype=torch.int32, device=device) if want_msg else None
     st = ctypes.c_void_p((stream or torch.cuda.current_stream(device)).cuda_stream)
-    check(lib.bldpc_encode_random(code._h, ctypes.c_ulonglong(int(seed) % (1 << 64)), int(first_frame), F, _dev_ptr(msg), _dev_ptr(CodeWord), st),
-          "PN_CodeWords")
+    if rate_match is not None:
+        check(lib.bldpc_rm_encode_random(code._h, rate_match._h, ctypes.c_ulonglong(int(seed) % (1 << 64)), int(first_frame), F, _dev_ptr(msg),
+                                         _dev_ptr(CodeWord), st), "PN_CodeWords")
+    else:
+        check(lib.bldpc_encode_random(code._h, ctypes.c_ulonglong(int(seed) % (1 << 64)), int(first_frame), F, _dev_ptr(msg), _dev_ptr(CodeWord), st),
+              "PN_CodeWords")
     return (CodeWord, msg) if want_msg else CodeWord
 
 
@@ -552,6 +559,127 @@ def Demodulate_QAM_host(rx, constellation, scale, N):
     F = rx.shape[0]
     out = np.empty((N, F), np.float32)
     check(lib.bldpc_qam_demap_host(_np_ptr(rx), _np_ptr(con), con.shape[0], ctypes.c_float(scale), N, F, _np_ptr(out)), "Demodulate_QAM_host")
+    return out
+
+
+class RateMatch:
+    """A shortening / puncturing profile over a mother code of N bits (bldpc_rm, semantics in include/bldpc.h).  shorten, puncture:
+    codeword positions in [0, N), in any order, disjoint and without repeats.  E = N - n_short - n_punct bits are transmitted, in
+    ascending position tx_pos (int32 [E], host).  Host only until the first device call on it."""
+
+    def __init__(self, N, shorten=(), puncture=()):
+        sh, pu = (np.ascontiguousarray(np.asarray(x if isinstance(x, np.ndarray) else list(x)).reshape(-1), np.int32) for x in (shorten, puncture))
+        self._h = None
+        h = ctypes.c_void_p()
+        check(lib.bldpc_rm_create(int(N), _np_ptr(sh) if sh.size else None, int(sh.size), _np_ptr(pu) if pu.size else None, int(pu.size),
+                                  ctypes.byref(h)), "RateMatch")
+        self._h = h
+        d = np.zeros(4, np.int32)
+        check(lib.bldpc_rm_dims(self._h, _np_ptr(d)), "bldpc_rm_dims")
+        self.N, self.E, self.n_short, self.n_punct = (int(x) for x in d)
+        self.tx_pos = np.zeros(self.E, np.int32)
+        check(lib.bldpc_rm_tx_pos(self._h, _np_ptr(self.tx_pos)), "bldpc_rm_tx_pos")
+        self.shorten, self.puncture = np.sort(sh), np.sort(pu)
+
+    def rate(self, K):
+        """(K - n_short) / E: the rate of the derived code, K the information bits of the mother code."""
+        return (K - self.n_short) / self.E
+
+    def close(self):
+        if self._h:
+            lib.bldpc_rm_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _check_short_llr(short_llr):
+    if not (np.isfinite(short_llr) and short_llr > 0):
+        raise ValueError("short_llr must be finite and > 0, not %r" % (short_llr,))
+
+
+def RM_Select(rm, CodeWord, stream=None):
+    """bldpc_rm_select: CodeWord CUDA int32 [N, F] -> the transmitted rows, int32 [E, F] (tx[e] = CodeWord[tx_pos[e]])."""
+    if not (torch.is_tensor(CodeWord) and CodeWord.dim() == 2 and CodeWord.shape[1] > 0):
+        raise ValueError("CodeWord must be [N=%d, F]" % rm.N)
+    F, dev = int(CodeWord.shape[1]), CodeWord.device
+    _check_cw(CodeWord, rm.N, F, dev)
+    tx = torch.empty((rm.E, F), dtype=torch.int32, device=dev)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(dev)).cuda_stream)
+    check(lib.bldpc_rm_select(rm._h, _dev_ptr(CodeWord), F, _dev_ptr(tx), st), "RM_Select")
+    return tx
+
+
+def RM_Recover(rm, rx, short_llr=1.0e4, stream=None):
+    """bldpc_rm_recover: received values rx CUDA float32 [E, F] -> Channel_Out [N, F]: the same bits on the transmitted rows, +0.0 on
+    the punctured ones, short_llr on the shortened ones."""
+    if not (torch.is_tensor(rx) and rx.is_cuda and rx.dtype == torch.float32 and rx.is_contiguous() and rx.dim() == 2
+            and rx.shape[0] == rm.E and rx.shape[1] > 0):
+        raise ValueError("rx must be a contiguous CUDA float32 tensor [E=%d, F]" % rm.E)
+    _check_short_llr(short_llr)
+    F = int(rx.shape[1])
+    out = torch.empty((rm.N, F), dtype=torch.float32, device=rx.device)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(rx.device)).cuda_stream)
+    check(lib.bldpc_rm_recover(rm._h, _dev_ptr(rx), F, ctypes.c_float(short_llr), _dev_ptr(out), st), "RM_Recover")
+    return out
+
+
+def AWGNChannel_RM_GPU(rm, seed, sigma, F, device=None, CodeWord=None, short_llr=1.0e4, stream=None):
+    """bldpc_rm_awgn_channel_device: the decoder's input [N, F] of a rate-matched batch from one kernel.  Noise is drawn for the E
+    transmitted bits only (the rows AWGNChannel_GPU(seed, sigma, E, F, CodeWord=RM_Select(rm, CodeWord)) returns, bit for bit);
+    seed (int32[3]) is advanced by 2 * E * F draws.  CodeWord: CUDA int32 [N, F] or None for the all-zero word."""
+    if not (isinstance(seed, np.ndarray) and seed.dtype == np.int32 and seed.size == 3):
+        raise ValueError("seed must be an int32 numpy array of 3")
+    if F <= 0:
+        raise ValueError("F must be positive")
+    _check_short_llr(short_llr)
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    if CodeWord is not None:
+        _check_cw(CodeWord, rm.N, F, device)
+    out = torch.empty((rm.N, F), dtype=torch.float32, device=device)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(device)).cuda_stream)
+    check(lib.bldpc_rm_awgn_channel_device(rm._h, _np_ptr(seed), ctypes.c_float(sigma), _dev_ptr(CodeWord), F, ctypes.c_float(short_llr),
+                                           _dev_ptr(out), st), "AWGNChannel_RM_GPU")
+    return out
+
+
+def RM_Select_host(rm, CodeWord):
+    """bldpc_rm_select_host: RM_Select on a host array int32 [N, F], no device needed."""
+    cw = np.ascontiguousarray(CodeWord, np.int32)
+    if cw.ndim != 2 or cw.shape[0] != rm.N or cw.shape[1] <= 0:
+        raise ValueError("CodeWord must be [N=%d, F]" % rm.N)
+    tx = np.empty((rm.E, cw.shape[1]), np.int32)
+    check(lib.bldpc_rm_select_host(rm._h, _np_ptr(cw), cw.shape[1], _np_ptr(tx)), "RM_Select_host")
+    return tx
+
+
+def RM_Recover_host(rm, rx, short_llr=1.0e4):
+    """bldpc_rm_recover_host: RM_Recover on a host array float32 [E, F], no device needed."""
+    rx = np.ascontiguousarray(rx, np.float32)
+    if rx.ndim != 2 or rx.shape[0] != rm.E or rx.shape[1] <= 0:
+        raise ValueError("rx must be [E=%d, F]" % rm.E)
+    out = np.empty((rm.N, rx.shape[1]), np.float32)
+    check(lib.bldpc_rm_recover_host(rm._h, _np_ptr(rx), rx.shape[1], ctypes.c_float(short_llr), _np_ptr(out)), "RM_Recover_host")
+    return out
+
+
+def AWGNChannel_RM_CPU(rm, seed, sigma, F, CodeWord=None, short_llr=1.0e4):
+    """bldpc_rm_awgn_channel_host: RM_Recover_host(AWGNChannel_CPU(seed, sigma, E, F, CodeWord=CodeWord[tx_pos])) in one call, host
+    libm; seed (int32[3]) advanced by 2 * E * F draws.  Returns float32 [N, F]."""
+    if not (isinstance(seed, np.ndarray) and seed.dtype == np.int32 and seed.size == 3):
+        raise ValueError("seed must be an int32 numpy array of 3")
+    cw = None
+    if CodeWord is not None:
+        cw = np.ascontiguousarray(CodeWord, np.int32)
+        if cw.shape != (rm.N, F):
+            raise ValueError("CodeWord must be [N=%d, F=%d]" % (rm.N, F))
+    out = np.empty((rm.N, F), np.float32)
+    check(lib.bldpc_rm_awgn_channel_host(rm._h, _np_ptr(seed), ctypes.c_float(sigma), None if cw is None else _np_ptr(cw), int(F),
+                                         ctypes.c_float(short_llr), _np_ptr(out)), "AWGNChannel_RM_CPU")
     return out
 
 

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "bldpc_encode.hpp"
+#include "bldpc_ratematch.hpp"
 #include "common.hpp"
 
 using namespace cldpc;
@@ -180,10 +181,13 @@ int build_generator(int J, int L, int Z, const int *H, Generator &g)
 // --------------------------------------------------------------------------------------------------------- device
 // Packing pass.  Wave (g, w): frames 64g .. 64g+63 (one per lane), information bits 64w .. 64w+63.  Writes the systematic
 // bits into CodeWord (and, for generated messages, into msg_out) and the 64 slices of the word into slices[g][K'].
-template <bool RANDOM>
-__global__ __launch_bounds__(256) void k_enc_pack(const int *__restrict__ msg, int *__restrict__ msg_out, int F, int K, int KW,
-                                                  const int *__restrict__ info_pos, int *__restrict__ cw, u64 *__restrict__ slices,
-                                                  u64 seed, long long first_frame)
+// SHORT (bldpc_rm_encode_random): a message bit whose information position is marked kRmShort in rm_map is forced to 0 before it is
+// written or packed; info_pos[k] and rm_map[info_pos[k]] are wave-uniform loads.  The body is shared; the two kernels below are its
+// instantiations, and k_enc_pack keeps the arguments and the code it had before SHORT existed.
+template <bool RANDOM, bool SHORT>
+__device__ __forceinline__ void enc_pack(const int *__restrict__ msg, int *__restrict__ msg_out, int F, int K, int KW,
+                                         const int *__restrict__ info_pos, int *__restrict__ cw, u64 *__restrict__ slices, u64 seed,
+                                         long long first_frame, const int *__restrict__ rm_map)
 {
     const int lane = threadIdx.x & 63;
     const int w = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -200,6 +204,7 @@ __global__ __launch_bounds__(256) void k_enc_pack(const int *__restrict__ msg, i
         int bit = 0;
         if (RANDOM) bit = (int)(x >> j) & 1;
         else if (valid) bit = msg[(size_t)k * F + f] & 1;
+        if (SHORT && rm_map[info_pos[k]] == kRmShort) bit = 0;
         if (valid) {
             if (msg_out) msg_out[(size_t)k * F + f] = bit;
             cw[(size_t)info_pos[k] * F + f] = bit;
@@ -208,6 +213,21 @@ __global__ __launch_bounds__(256) void k_enc_pack(const int *__restrict__ msg, i
         if (lane == j) mine = b;
     }
     if (lane < kend) slices[g * K + w * 64 + lane] = mine;
+}
+
+template <bool RANDOM>
+__global__ __launch_bounds__(256) void k_enc_pack(const int *__restrict__ msg, int *__restrict__ msg_out, int F, int K, int KW,
+                                                  const int *__restrict__ info_pos, int *__restrict__ cw, u64 *__restrict__ slices,
+                                                  u64 seed, long long first_frame)
+{
+    enc_pack<RANDOM, false>(msg, msg_out, F, K, KW, info_pos, cw, slices, seed, first_frame, nullptr);
+}
+
+__global__ __launch_bounds__(256) void k_enc_pack_short(int *__restrict__ msg_out, int F, int K, int KW, const int *__restrict__ info_pos,
+                                                        int *__restrict__ cw, u64 *__restrict__ slices, u64 seed, long long first_frame,
+                                                        const int *__restrict__ rm_map)
+{
+    enc_pack<true, true>(nullptr, msg_out, F, K, KW, info_pos, cw, slices, seed, first_frame, rm_map);
 }
 
 // Parity pass.  Workgroup (g, chunk): the slices of frame group g in LDS (zero-padded to a multiple of 32 words of 64), then
@@ -385,7 +405,7 @@ extern "C" int bldpc_encoder_info(bldpc_code *code, int *K_info, int *rank, int 
 }
 
 static int encode_impl(bldpc_code *code, const int *msg, int *msg_out, bool random, u64 seed, long long first_frame, int F, int *cw,
-                       void *stream, const char *who)
+                       void *stream, const char *who, const int *rm_map = nullptr)
 {
     EncState *s = nullptr;
     if (!cw || F <= 0 || (!random && !msg)) return fail(BLDPC_EINVAL, "%s: null argument or F=%d", who, F);
@@ -404,7 +424,9 @@ static int encode_impl(bldpc_code *code, const int *msg, int *msg_out, bool rand
     CLDPC_HIP(s->slices.reserve((size_t)G * g.K * sizeof(u64)), BLDPC_ENOMEM);
     u64 *sl = (u64 *)s->slices.p;
     const dim3 pg((unsigned)G, (unsigned)((g.KW + 3) / 4));
-    if (random)
+    if (random && rm_map)
+        hipLaunchKernelGGL(k_enc_pack_short, pg, dim3(256), 0, st, msg_out, F, g.K, g.KW, s->d_info, cw, sl, seed, first_frame, rm_map);
+    else if (random)
         hipLaunchKernelGGL(k_enc_pack<true>, pg, dim3(256), 0, st, nullptr, msg_out, F, g.K, g.KW, s->d_info, cw, sl, seed, first_frame);
     else
         hipLaunchKernelGGL(k_enc_pack<false>, pg, dim3(256), 0, st, msg, nullptr, F, g.K, g.KW, s->d_info, cw, sl, 0ull, 0ll);
@@ -433,6 +455,20 @@ extern "C" int bldpc_encode_random(bldpc_code *code, unsigned long long seed, lo
                                    void *stream)
 {
     return encode_impl(code, nullptr, msg, true, seed, first_frame, F, CodeWord, stream, "bldpc_encode_random");
+}
+
+int cldpc::encode_random_shortened(bldpc_code *code, const int *d_map, const int *short_pos, int n_short, u64 seed, long long first_frame,
+                                   int F, int *msg, int *cw, void *stream)
+{
+    const char *who = "bldpc_rm_encode_random";
+    EncState *s = nullptr;
+    int r = ensure_generator(code, who, s);
+    if (r) return r;
+    for (int i = 0; i < n_short; i++)
+        if (!std::binary_search(s->g.info_pos.begin(), s->g.info_pos.end(), short_pos[i]))
+            return fail(BLDPC_EINVAL, "%s: shortened position %d is a parity position of the generator, not an information position", who,
+                        short_pos[i]);
+    return encode_impl(code, nullptr, msg, true, seed, first_frame, F, cw, stream, who, n_short ? d_map : nullptr);
 }
 
 extern "C" int bldpc_syndrome(const bldpc_code *code, const int *D, int F, int *flag, int *unsat, void *stream)

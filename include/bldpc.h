@@ -345,6 +345,69 @@ int bldpc_qam_demap(const float *rx, const float *constellation, int q, float sc
 int bldpc_qam_map_host(const int *CodeWord, int N, int F, int m, int *sym);
 int bldpc_qam_demap_host(const float *rx, const float *constellation, int q, float scale, int N, int F, float *Channel_Out);
 
+/* -- rate matching: shortened and punctured codes (not in the reference, which transmits every bit of the mother code) -- */
+
+/* A profile over a mother code of N bits names two disjoint sets of codeword positions.  Semantics:
+ *
+ *   shortened   the bit is 0 by agreement and is not sent; the receiver knows it: its channel value is short_llr, a large
+ *               positive confidence (positive means bit 0, as with y = 1 - 2c).
+ *   punctured   the bit is whatever the encoder made it and is not sent; the receiver knows nothing: its channel value is +0.0f.
+ *   transmitted every other position, E = N - n_short - n_punct of them, in ascending codeword position:
+ *               tx_pos[0] < ... < tx_pos[E-1].  The rate of the derived code is (K - n_short) / E.
+ *
+ *   select:   tx[e][f] = CodeWord[tx_pos[e]][f]                                  a gather; the shortened rows are not looked at
+ *   recover:  Channel_Out[n][f] = rx[e][f]     (the same 32 bits)                 n = tx_pos[e]
+ *                               = +0.0f        (0x00000000)                       n punctured
+ *                               = short_llr                                       n shortened
+ *             the de-rate-matcher for values from any source, bldpc_qam_demap included (run the modem with N := E)
+ *   channel:  recover(bldpc_awgn_channel(select(CodeWord)) with N := E) as ONE pass: noise is drawn for the transmitted bits only, on
+ *             the reference's stream -- sample (f, e) uses draws 2(f*E + e) and 2(f*E + e) + 1 of RandomModule, in the arithmetic of
+ *             bldpc_awgn_channel_host / _device, and seed[3] advances by 2*E*F draws.  The device version writes [N][F] from one
+ *             kernel, with no [E][F] intermediate; its transmitted rows carry the bits bldpc_awgn_channel_device gives for N := E
+ *             on the selected codeword, the host version those of bldpc_awgn_channel_host.
+ *
+ * Every decoder of this library takes such an input as it stands: nothing in a min-sum iteration treats 0 or a large value apart.
+ * short_llr must be finite and > 0 (BLDPC_EINVAL).  +inf is refused on purpose: a check all of whose other neighbours are shortened
+ * sends inf, and the next S - R is inf - inf.  The min-sum decoders are scale-invariant, so any value far above the channel's serves.
+ *
+ *   CodeWord     device int32 [N][F] (the channel: or NULL = the all-zero word)      tx   device int32 [E][F]
+ *   rx           device float [E][F]                                                Channel_Out  device float [N][F]
+ * All arrays frame-fastest.  The device calls are asynchronous on `stream` and allocate nothing per call (the profile's device
+ * tables are uploaded by the first of them: use a profile from one host thread at a time, like a code object).
+ * Out of scope: hard-decision (BSC) input, repetition (E > N), the position lists of any standard, the GF(q) half. */
+typedef struct bldpc_rm bldpc_rm; /* opaque: the kind of every position, its rank among the transmitted ones, tx_pos; host + device */
+
+/* Positions are codeword positions in [0, N), in any order.  BLDPC_EINVAL: a position out of range, a position repeated or present
+ * in both lists, E < 1, a null list with a non-zero count, a negative count, N < 1 or N > 2 097 120 (the launch grid of the kernels).
+ * Both counts zero is the identity profile.  Host only: no device is touched until the first device call on the profile. */
+int bldpc_rm_create(int N, const int *short_pos, int n_short, const int *punct_pos, int n_punct, bldpc_rm **rm);
+int bldpc_rm_destroy(bldpc_rm *rm);
+int bldpc_rm_dims(const bldpc_rm *rm, int dims[4]);   /* N, E, n_short, n_punct */
+int bldpc_rm_tx_pos(const bldpc_rm *rm, int *tx_pos); /* host int [E] */
+
+int bldpc_rm_select(const bldpc_rm *rm, const int *CodeWord, int F, int *tx, void *stream);
+int bldpc_rm_recover(const bldpc_rm *rm, const float *rx, int F, float short_llr, float *Channel_Out, void *stream);
+/* seed[3]: host, every state in [0, m) as for bldpc_awgn_channel_device (BLDPC_EINVAL otherwise), advanced in place. */
+int bldpc_rm_awgn_channel_device(const bldpc_rm *rm, int seed[3], float sigma, const int *CodeWord, int F, float short_llr,
+                                 float *Channel_Out, void *stream);
+
+/* The same on host pointers, no device needed (and so no stream: they return when done): plain C++ that follows the steps above
+ * literally -- the channel IS select, bldpc_awgn_channel_host with N := E, recover.  They are the statement of the semantics inside
+ * the product and what the kernels are tested against bit for bit.  Same argument checks (any int triple is a seed here, as for
+ * bldpc_awgn_channel_host). */
+int bldpc_rm_select_host(const bldpc_rm *rm, const int *CodeWord, int F, int *tx);
+int bldpc_rm_recover_host(const bldpc_rm *rm, const float *rx, int F, float short_llr, float *Channel_Out);
+int bldpc_rm_awgn_channel_host(const bldpc_rm *rm, int seed[3], float sigma, const int *CodeWord, int F, float short_llr,
+                               float *Channel_Out);
+
+/* bldpc_encode_random with shortened bits: the message rule of bldpc_encode_random, then every message bit k whose info_pos[k] is a
+ * shortened position of `rm` is forced to 0, then the encoding; msg (when not NULL) receives the messages after the forcing.  Frame g
+ * is still the same codeword at any world size.  BLDPC_EINVAL: rm's N differs from the code's, or a shortened position is not an
+ * information position of the code's generator (a parity bit is determined by the message and cannot be agreed to be 0).
+ * Punctured positions play no part.  Other arguments, limits and asynchrony as bldpc_encode_random. */
+int bldpc_rm_encode_random(bldpc_code *code, const bldpc_rm *rm, unsigned long long seed, long long first_frame, int F, int *msg,
+                           int *CodeWord, void *stream);
+
 /* sigma of the sweep point (main.cu:120-127): snrtype 0 = Eb/N0 (uses rate), 1 = Es/N0. */
 float bldpc_sigma(float SNR, int snrtype, float rate);
 

@@ -20,6 +20,19 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 
+def parse_positions(spec, N=None):
+    """SPEC of --shorten / --puncture: comma-separated half-open ranges a:b of codeword positions -> sorted list of positions."""
+    pos = set()
+    for part in spec.split(","):
+        a, sep, b = part.strip().partition(":")
+        if not sep or not a.strip().isdigit() or not b.strip().isdigit() or int(a) >= int(b):
+            raise ValueError("%r is not a range a:b of codeword positions with a < b" % part)
+        if N is not None and int(b) > N:
+            raise ValueError("range %s ends past N=%d" % (part.strip(), N))
+        pos.update(range(int(a), int(b)))
+    return sorted(pos)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("which", choices=["binary", "nb"])
@@ -49,6 +62,10 @@ def main():
     ap.add_argument("--stop-rule", choices=["prefix", "syndrome"], default=None,
                     help="--layered: stop rule / meaning of the flag row (default: syndrome with --pn-message, else prefix)")
     ap.add_argument("--as-written", action="store_true", help="decode on the reference's Transform_H table as written (SURVEY F3)")
+    ap.add_argument("--shorten", metavar="SPEC", default=None, help="binary: codeword positions fixed to 0 and not sent, comma-separated half-open "
+                    "ranges a:b (information positions; needs --device-channel)")
+    ap.add_argument("--puncture", metavar="SPEC", default=None, help="binary: codeword positions not sent, same SPEC (needs --device-channel)")
+    ap.add_argument("--short-llr", type=float, default=1.0e4, help="--shorten: the decoder's input on a shortened position")
     args = ap.parse_args()
     if args.which == "binary" and args.layered:
         if args.as_written or not (args.fixed or args.per_frame):
@@ -64,6 +81,17 @@ def main():
     if args.which == "binary" and args.qam != 2 and not (args.pn_message and args.device_channel):
         ap.error("binary --qam %d needs --pn-message (a QAM channel is not symmetric: the all-zero word is not representative) and "
                  "--device-channel (there is no host QAM channel on this path)" % args.qam)
+    ratematch = args.shorten is not None or args.puncture is not None
+    if ratematch:
+        if args.which != "binary" or not args.device_channel:
+            ap.error("--shorten / --puncture belong to the binary sweep with --device-channel")
+        try:
+            shorten = parse_positions(args.shorten, args.L * args.Z) if args.shorten else []
+            puncture = parse_positions(args.puncture, args.L * args.Z) if args.puncture else []
+        except ValueError as e:
+            ap.error(str(e))
+        if not (args.short_llr > 0 and args.short_llr < float("inf")):
+            ap.error("--short-llr must be finite and > 0")
     nbd = os.path.join(ROOT, "data", "nb")
     if args.which == "nb":
         mpath = args.nb_matrix if os.path.exists(args.nb_matrix) else os.path.join(nbd, args.nb_matrix)
@@ -101,6 +129,12 @@ def main():
         mod = {}
         if args.qam != 2:  # the GF(q) half's constellation file and sigma (Eb/N0, n_QAM in the formula): the two sweeps share both
             mod = dict(n_QAM=args.qam, CONSTELLATION=C.Get_CONSTELLATION(os.path.join(nbd, "Constellation", "GRAY_%dQAM.txt" % args.qam), args.qam))
+        if ratematch:
+            rm = C.RateMatch(code.N, shorten, puncture)
+            mod.update(rate_match=rm, short_llr=args.short_llr)
+            if rank == 0:
+                print("# rate matching: %d shortened, %d punctured, E=%d transmitted, rate (K - n_short) / E = %.4f" % (
+                    rm.n_short, rm.n_punct, rm.E, rm.rate(code.K)))
         if rank == 0:
             print("# %s N=%d K=%d, %s%s%s, maxIT=%d, batch=%d x %d GPU(s)%s" % (os.path.basename(args.matrix), code.N, code.K,
                   "" if args.qam == 2 else "%d-QAM (Gray) %d bits per point, max-log demapper, Eb/N0, " % (args.qam, args.qam.bit_length() - 1),
