@@ -177,6 +177,13 @@ extern "C" int nbldpc_code_create(int N, int M, int q, int dv, int dc, const int
 
 extern "C" const char *nbldpc_last_kernel(const nbldpc_code *c) { return c ? c->last_kernel : "none"; }
 
+extern "C" int nbldpc_code_grids(const nbldpc_code *c, int info[4])
+{
+    if (!c || !info) return fail(NBLDPC_EINVAL, "nbldpc_code_grids: null argument");
+    info[0] = c->persist_grid; info[1] = c->pipe_grid; info[2] = c->tmm_grid[0]; info[3] = c->tmm_grid[1];
+    return NBLDPC_OK;
+}
+
 extern "C" int nbldpc_code_destroy(nbldpc_code *c)
 {
     if (!c) return NBLDPC_OK;

@@ -431,7 +431,7 @@ template <int Q, int DVM, int NT> __global__ __launch_bounds__(NT) void k_nb_ems
     float *LLRo = nullptr;
     const bool active = lane < q - 1;          // lanes 0..q-2 <-> field elements 1..q-1
     const int sym = active ? lane + 1 : 0;     // lane q-1 carries element 0 (value 0, :250)
-    constexpr int CPW = 96 * 64 / NT; // columns per wave whose channel vector stays in registers (N <= 96)
+    constexpr int CPW = 96 * 64 / NT; // columns per wave whose channel vector stays in registers: the first 96 columns; the tail loop of phase A takes the others
     float lch[CPW];
     // The graph does not change between iterations: for narrow codes (dv <= 2) each lane keeps, per column and edge, the
     // LDS offset of ITS entry of the check thread's max array, E[mul(sym, h)][thr], so an iteration starts with that one

@@ -28,6 +28,7 @@ lib.nbldpc_awgn_channel_device.argtypes = [c_void_p, c_float, c_void_p, c_int, c
 lib.nbldpc_read_constellation.argtypes = [c_char_p, c_int, c_void_p]
 lib.nbldpc_last_kernel.argtypes = [c_void_p]
 lib.nbldpc_last_kernel.restype = ctypes.c_char_p
+lib.nbldpc_code_grids.argtypes = [c_void_p, c_void_p]
 lib.nbldpc_awgn_channel_host_qam.argtypes = [c_void_p, c_float, c_void_p, c_int, c_void_p, c_int, c_void_p]
 lib.nbldpc_awgn_channel_device_qam.argtypes = [c_void_p, c_float, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]
 lib.nbldpc_demodulate_qam.argtypes = [c_void_p, c_void_p, c_void_p, c_float, c_int, c_void_p, c_void_p]
@@ -127,6 +128,17 @@ class NBCode(NBMatrix):
     def last_kernel(self):
         """Name of the kernel the last decode call on this code launched (nbldpc_last_kernel)."""
         return lib.nbldpc_last_kernel(self._h).decode()
+
+    def grids(self):
+        """nbldpc_code_grids: dict(persist_grid, pipe_grid, tmm_grid, tmm_grid_layered) -- a batch larger than a kernel's grid is
+        decoded by its persistent form (frames from a counter)."""
+        d = np.zeros(4, np.int32)
+        _check(lib.nbldpc_code_grids(self._h, _np(d)), "nbldpc_code_grids")
+        return dict(persist_grid=int(d[0]), pipe_grid=int(d[1]), tmm_grid=int(d[2]), tmm_grid_layered=int(d[3]))
+
+    @property
+    def persist_grid(self):
+        return self.grids()["persist_grid"]
 
     def close(self):
         if getattr(self, "_h", None):

@@ -68,6 +68,12 @@ int nbldpc_code_destroy(nbldpc_code *code);
  * equivalent -- its kernels are fixed at compile time (myNBLDPC/src/Decode_GPU.cu:138-356). */
 const char *nbldpc_last_kernel(const nbldpc_code *code);
 
+/* How many workgroups of this code's kernels the device holds at once, as nbldpc_code_create found it: info[0] k_nb_ems /
+ * k_nb_ems_wide, info[1] k_nb_ems2, info[2] / info[3] k_nb_tmm flooding / layered; 0: no such kernel for this code (or the device
+ * did not say).  A batch with more frames than that is decoded by persistent workgroups that take their frames from a counter.
+ * The counterpart of bldpc_code_qc_info's persist_grid (include/bldpc.h). */
+int nbldpc_code_grids(const nbldpc_code *code, int info[4]);
+
 /* Replaces Decoding_EMS / Decoding_EMS_GPU for a batch (all pointers DEVICE memory).
  *   EMS_Nm, EMS_Nc   reference macros EMS_NM / EMS_NC (define.h:31-32)
  *   maxIT            reference macro maxIT (define.h:35)
