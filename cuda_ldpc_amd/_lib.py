@@ -73,6 +73,16 @@ lib.bldpc_rm_select_host.argtypes = [c_void_p, c_void_p, c_int, c_void_p]
 lib.bldpc_rm_recover_host.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_float, c_void_p]
 lib.bldpc_rm_awgn_channel_host.argtypes = [c_void_p, c_void_p, ctypes.c_float, c_void_p, c_int, ctypes.c_float, c_void_p]
 lib.bldpc_rm_encode_random.argtypes = [c_void_p, c_void_p, ctypes.c_ulonglong, ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p]
+lib.bldpc_rm_create_circular.argtypes = [c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_void_p)]
+lib.bldpc_rm_circ.argtypes = [c_void_p, c_void_p]
+lib.bldpc_rm_combine.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_float, c_void_p, c_void_p, c_void_p]
+lib.bldpc_rm_awgn_combine_device.argtypes = [c_void_p, c_void_p, ctypes.c_float, c_void_p, c_int, ctypes.c_float, c_void_p, c_void_p, c_void_p]
+lib.bldpc_rm_combine_host.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_float, c_void_p, c_void_p]
+lib.bldpc_rm_awgn_combine_host.argtypes = [c_void_p, c_void_p, ctypes.c_float, c_void_p, c_int, ctypes.c_float, c_void_p, c_void_p]
+lib.bldpc_frames_gather.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]
+lib.bldpc_frames_scatter.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]
+lib.bldpc_frames_gather_host.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]
+lib.bldpc_frames_scatter_host.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]
 lib.bldpc_sigma.restype = ctypes.c_float
 lib.bldpc_sigma.argtypes = [ctypes.c_float, c_int, ctypes.c_float]
 

@@ -565,14 +565,18 @@ def Demodulate_QAM_host(rx, constellation, scale, N):
 class RateMatch:
     """A shortening / puncturing profile over a mother code of N bits (bldpc_rm, semantics in include/bldpc.h).  shorten, puncture:
     codeword positions in [0, N), in any order, disjoint and without repeats.  E = N - n_short - n_punct bits are transmitted, in
-    ascending position tx_pos (int32 [E], host).  Host only until the first device call on it."""
+    ascending position tx_pos (int32 [E], host).  Host only until the first device call on it.  RateMatch.circular makes the HARQ kind;
+    every profile has Ncb (buffer length), k0 and laps (a linear one: E, 0, 1)."""
 
-    def __init__(self, N, shorten=(), puncture=()):
+    def __init__(self, N, shorten=(), puncture=(), _circular=None):
         sh, pu = (np.ascontiguousarray(np.asarray(x if isinstance(x, np.ndarray) else list(x)).reshape(-1), np.int32) for x in (shorten, puncture))
         self._h = None
         h = ctypes.c_void_p()
-        check(lib.bldpc_rm_create(int(N), _np_ptr(sh) if sh.size else None, int(sh.size), _np_ptr(pu) if pu.size else None, int(pu.size),
-                                  ctypes.byref(h)), "RateMatch")
+        lists = (_np_ptr(sh) if sh.size else None, int(sh.size), _np_ptr(pu) if pu.size else None, int(pu.size))
+        if _circular is None:
+            check(lib.bldpc_rm_create(int(N), *lists, ctypes.byref(h)), "RateMatch")
+        else:
+            check(lib.bldpc_rm_create_circular(int(N), *lists, int(_circular[0]), int(_circular[1]), ctypes.byref(h)), "RateMatch.circular")
         self._h = h
         d = np.zeros(4, np.int32)
         check(lib.bldpc_rm_dims(self._h, _np_ptr(d)), "bldpc_rm_dims")
@@ -580,6 +584,16 @@ class RateMatch:
         self.tx_pos = np.zeros(self.E, np.int32)
         check(lib.bldpc_rm_tx_pos(self._h, _np_ptr(self.tx_pos)), "bldpc_rm_tx_pos")
         self.shorten, self.puncture = np.sort(sh), np.sort(pu)
+        check(lib.bldpc_rm_circ(self._h, _np_ptr(d)), "bldpc_rm_circ")
+        self.Ncb, self.k0, self.laps = int(d[0]), int(d[1]), int(d[3])
+        self.is_circular = _circular is not None
+
+    @classmethod
+    def circular(cls, N, shorten, puncture, k0, E):
+        """bldpc_rm_create_circular: one HARQ transmission.  The buffer is the Ncb = N - n_short - n_punct positions a RateMatch of the same
+        lists transmits; this profile sends tx_pos[e] = buffer[(k0 + e) % Ncb] for e < E, around the end and up to 8 times over
+        (laps = ceil(E / Ncb)).  E is what rate() divides by."""
+        return cls(N, shorten, puncture, _circular=(k0, E))
 
     def rate(self, K):
         """(K - n_short) / E: the rate of the derived code, K the information bits of the mother code."""
@@ -681,6 +695,158 @@ def AWGNChannel_RM_CPU(rm, seed, sigma, F, CodeWord=None, short_llr=1.0e4):
     check(lib.bldpc_rm_awgn_channel_host(rm._h, _np_ptr(seed), ctypes.c_float(sigma), None if cw is None else _np_ptr(cw), int(F),
                                          ctypes.c_float(short_llr), _np_ptr(out)), "AWGNChannel_RM_CPU")
     return out
+
+
+def _check_done(done, F, dev):
+    if done is not None and not (torch.is_tensor(done) and done.is_cuda and done.device == dev and done.dtype == torch.int32 and done.dim() == 1
+                                 and done.is_contiguous() and done.shape[0] == F):
+        raise ValueError("done must be a contiguous CUDA int32 tensor [F=%d] on %s (a row of D will do)" % (F, dev))
+
+
+def _check_acc(rm, Channel_Acc):
+    if not (torch.is_tensor(Channel_Acc) and Channel_Acc.is_cuda and Channel_Acc.dtype == torch.float32 and Channel_Acc.is_contiguous()
+            and Channel_Acc.dim() == 2 and Channel_Acc.shape[0] == rm.N and Channel_Acc.shape[1] > 0):
+        raise ValueError("Channel_Acc must be a contiguous CUDA float32 tensor [N=%d, F]" % rm.N)
+
+
+def RM_Combine(rm, rx, Channel_Acc, done=None, short_llr=1.0e4, stream=None):
+    """bldpc_rm_combine: add one more transmission rx CUDA float32 [E, F] into Channel_Acc [N, F] in place (and return it): every
+    position's contributions in ascending e, starting from the stored value; shortened rows are set to short_llr; rows without a
+    contribution and the columns of frames with done[f] != 0 (CUDA int32 [F], e.g. D[N]) keep their bits."""
+    _check_acc(rm, Channel_Acc)
+    F, dev = int(Channel_Acc.shape[1]), Channel_Acc.device
+    if not (torch.is_tensor(rx) and rx.is_cuda and rx.device == dev and rx.dtype == torch.float32 and rx.is_contiguous()
+            and tuple(rx.shape) == (rm.E, F)):
+        raise ValueError("rx must be a contiguous CUDA float32 tensor [E=%d, F=%d]" % (rm.E, F))
+    _check_short_llr(short_llr)
+    _check_done(done, F, dev)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(dev)).cuda_stream)
+    check(lib.bldpc_rm_combine(rm._h, _dev_ptr(rx), F, ctypes.c_float(short_llr), _dev_ptr(done), _dev_ptr(Channel_Acc), st), "RM_Combine")
+    return Channel_Acc
+
+
+def AWGNChannel_RM_Combine_GPU(rm, seed, sigma, Channel_Acc, done=None, CodeWord=None, short_llr=1.0e4, stream=None):
+    """bldpc_rm_awgn_combine_device: the samples AWGNChannel_RM_GPU would draw for this transmission, combined into Channel_Acc [N, F] in
+    place under done, from one kernel.  seed (int32[3]) is advanced by 2 * E * F draws whatever done holds."""
+    if not (isinstance(seed, np.ndarray) and seed.dtype == np.int32 and seed.size == 3):
+        raise ValueError("seed must be an int32 numpy array of 3")
+    _check_acc(rm, Channel_Acc)
+    F, dev = int(Channel_Acc.shape[1]), Channel_Acc.device
+    _check_short_llr(short_llr)
+    _check_done(done, F, dev)
+    if CodeWord is not None:
+        _check_cw(CodeWord, rm.N, F, dev)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(dev)).cuda_stream)
+    check(lib.bldpc_rm_awgn_combine_device(rm._h, _np_ptr(seed), ctypes.c_float(sigma), _dev_ptr(CodeWord), F, ctypes.c_float(short_llr),
+                                           _dev_ptr(done), _dev_ptr(Channel_Acc), st), "AWGNChannel_RM_Combine_GPU")
+    return Channel_Acc
+
+
+def _host_acc(rm, acc):
+    if not (isinstance(acc, np.ndarray) and acc.dtype == np.float32 and acc.flags.c_contiguous and acc.ndim == 2 and acc.shape[0] == rm.N
+            and acc.shape[1] > 0):
+        raise ValueError("Channel_Acc must be a C-contiguous float32 array [N=%d, F], updated in place" % rm.N)
+    return acc, acc.shape[1]
+
+
+def _host_done(done, F):
+    if done is None:
+        return None
+    done = np.ascontiguousarray(done, np.int32)
+    if done.shape != (F,):
+        raise ValueError("done must be int32 [F=%d]" % F)
+    return done
+
+
+def RM_Combine_host(rm, rx, Channel_Acc, done=None, short_llr=1.0e4):
+    """bldpc_rm_combine_host: RM_Combine on host arrays, no device needed.  Channel_Acc float32 [N, F] (C-contiguous) is updated in place."""
+    acc, F = _host_acc(rm, Channel_Acc)
+    rx = np.ascontiguousarray(rx, np.float32)
+    if rx.shape != (rm.E, F):
+        raise ValueError("rx must be [E=%d, F=%d]" % (rm.E, F))
+    done = _host_done(done, F)
+    check(lib.bldpc_rm_combine_host(rm._h, _np_ptr(rx), F, ctypes.c_float(short_llr), None if done is None else _np_ptr(done), _np_ptr(acc)),
+          "RM_Combine_host")
+    return acc
+
+
+def AWGNChannel_RM_Combine_CPU(rm, seed, sigma, Channel_Acc, done=None, CodeWord=None, short_llr=1.0e4):
+    """bldpc_rm_awgn_combine_host: RM_Select_host, AWGNChannel_CPU at E, RM_Combine_host in one call; seed advanced by 2 * E * F draws."""
+    if not (isinstance(seed, np.ndarray) and seed.dtype == np.int32 and seed.size == 3):
+        raise ValueError("seed must be an int32 numpy array of 3")
+    acc, F = _host_acc(rm, Channel_Acc)
+    cw = None
+    if CodeWord is not None:
+        cw = np.ascontiguousarray(CodeWord, np.int32)
+        if cw.shape != (rm.N, F):
+            raise ValueError("CodeWord must be [N=%d, F=%d]" % (rm.N, F))
+    done = _host_done(done, F)
+    check(lib.bldpc_rm_awgn_combine_host(rm._h, _np_ptr(seed), ctypes.c_float(sigma), None if cw is None else _np_ptr(cw), F,
+                                         ctypes.c_float(short_llr), None if done is None else _np_ptr(done), _np_ptr(acc)), "AWGNChannel_RM_Combine_CPU")
+    return acc
+
+
+def _check_frames_dev(src, idx, what):
+    if not (torch.is_tensor(src) and src.is_cuda and src.is_contiguous() and src.element_size() == 4 and src.dim() in (1, 2) and src.numel() > 0):
+        raise ValueError("%s must be a contiguous CUDA tensor of 32-bit elements, [rows, F] or [F]" % what)
+    if not (torch.is_tensor(idx) and idx.is_cuda and idx.device == src.device and idx.dtype == torch.int32 and idx.is_contiguous() and idx.dim() == 1
+            and idx.numel() > 0):
+        raise ValueError("idx must be a non-empty contiguous CUDA int32 tensor [Fa] on the device of %s" % what)
+
+
+def Frames_Gather(src, idx, stream=None):
+    """bldpc_frames_gather: the columns idx (CUDA int32 [Fa], strictly ascending in [0, F)) of src, a CUDA tensor [rows, F] or [F] of
+    32-bit elements -> [rows, Fa] or [Fa] of the same dtype."""
+    _check_frames_dev(src, idx, "src")
+    F, Fa = int(src.shape[-1]), int(idx.numel())
+    if Fa > F:
+        raise ValueError("idx holds %d frames, src has %d" % (Fa, F))
+    dst = torch.empty(tuple(src.shape[:-1]) + (Fa,), dtype=src.dtype, device=src.device)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(src.device)).cuda_stream)
+    check(lib.bldpc_frames_gather(_dev_ptr(src), src.numel() // F, F, _dev_ptr(idx), Fa, _dev_ptr(dst), st), "Frames_Gather")
+    return dst
+
+
+def Frames_Scatter(src, idx, dst, stream=None):
+    """bldpc_frames_scatter: dst[:, idx[a]] = src[:, a] in place (and returns dst); src [rows, Fa] or [Fa], dst [rows, F] or [F], the
+    other columns of dst keep their bits."""
+    _check_frames_dev(src, idx, "src")
+    if not (torch.is_tensor(dst) and dst.is_cuda and dst.device == src.device and dst.is_contiguous() and dst.dtype == src.dtype
+            and dst.dim() == src.dim() and dst.shape[:-1] == src.shape[:-1]):
+        raise ValueError("dst must be a contiguous CUDA tensor like src with F columns")
+    F, Fa = int(dst.shape[-1]), int(idx.numel())
+    if int(src.shape[-1]) != Fa or Fa > F:
+        raise ValueError("src holds %d frames, idx %d, dst %d" % (src.shape[-1], Fa, F))
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(src.device)).cuda_stream)
+    check(lib.bldpc_frames_scatter(_dev_ptr(src), src.numel() // Fa, F, _dev_ptr(idx), Fa, _dev_ptr(dst), st), "Frames_Scatter")
+    return dst
+
+
+def _frames_host(src, idx):
+    src = np.ascontiguousarray(src)
+    if src.dtype.itemsize != 4 or src.ndim not in (1, 2) or src.size == 0:
+        raise ValueError("src must hold 32-bit elements, [rows, F] or [F]")
+    return src, np.ascontiguousarray(idx, np.int32).reshape(-1)
+
+
+def Frames_Gather_host(src, idx):
+    """bldpc_frames_gather_host: Frames_Gather on host arrays; idx is checked (strictly ascending in [0, F))."""
+    src, idx = _frames_host(src, idx)
+    F = src.shape[-1]
+    dst = np.empty(src.shape[:-1] + (idx.size,), src.dtype)
+    check(lib.bldpc_frames_gather_host(_np_ptr(src), src.size // F, F, _np_ptr(idx), int(idx.size), _np_ptr(dst)), "Frames_Gather_host")
+    return dst
+
+
+def Frames_Scatter_host(src, idx, dst):
+    """bldpc_frames_scatter_host: Frames_Scatter on host arrays, dst (C-contiguous, same dtype) updated in place."""
+    src, idx = _frames_host(src, idx)
+    if not (isinstance(dst, np.ndarray) and dst.flags.c_contiguous and dst.dtype == src.dtype and dst.ndim == src.ndim
+            and dst.shape[:-1] == src.shape[:-1]) or src.shape[-1] != idx.size:
+        raise ValueError("dst must be a C-contiguous array like src with F columns, src must hold one column per index")
+    F = dst.shape[-1]
+    check(lib.bldpc_frames_scatter_host(_np_ptr(src), src.size // max(idx.size, 1), F, _np_ptr(idx), int(idx.size), _np_ptr(dst)), "Frames_Scatter_host")
+    return dst
 
 
 def Decode_Statistic(code, Channel_Out, counters, max_iter=50, length=0, exit_mode=EXIT_BATCH_GLOBAL, kernel=KERNEL_AUTO, D=None, stream=None):

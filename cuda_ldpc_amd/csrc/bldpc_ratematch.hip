@@ -5,6 +5,11 @@
 // received values, +0.0f on punctured rows, short_llr on shortened ones) and the sweep's hot path, the AWGN channel that writes the
 // decoder's [N][F] input in one pass.  Every kernel keeps the frame index along threadIdx.x, so that a wavefront reads and writes 64
 // consecutive words of one row, and reads map / tx_pos at wave-uniform addresses.
+//
+// HARQ (include/bldpc.h, "HARQ"): a circular profile reads the same buffer from k0 for E positions, wrapping and repeating, and the
+// combining movements add a transmission into an accumulator [N][F] under a per-frame done mask.  They have kernels of their own
+// (k_rm_circ, k_rm_awgn_circ); a profile from bldpc_rm_create keeps k_rm_recover and k_rm_awgn in the entry points it had.  Frame
+// compaction (bldpc_frames_gather / _scatter) moves the columns of the unacknowledged frames.
 #include "../../include/bldpc.h"
 
 #include <algorithm>
@@ -22,7 +27,9 @@ using namespace cldpc::lcg;
 
 struct bldpc_rm {
     int N = 0, E = 0, n_short = 0, n_punct = 0;
-    std::vector<int> map, tx_pos, short_pos;      // [N], [E] ascending, [n_short] ascending
+    bool circular = false;                        // made by bldpc_rm_create_circular: tx_pos is in transmission order
+    int Ncb = 0, k0 = 0;                          // buffer length N - n_short - n_punct and start (linear: Ncb = E, k0 = 0)
+    std::vector<int> map, tx_pos, short_pos;      // [N] rank in the buffer, [E] (linear: ascending), [n_short] ascending
     mutable int *d_map = nullptr, *d_tx = nullptr; // uploaded by the first device call
 };
 
@@ -30,6 +37,9 @@ namespace {
 
 constexpr int kRows = 32;            // rows (codeword positions) per thread, as k_awgn's run of bldpc_channel.hip
 constexpr int kMaxN = 65535 * kRows; // gridDim.y
+constexpr int kMaxLaps = 8;          // E <= kMaxLaps * Ncb: k_rm_awgn_circ keeps one LCG state per lap in registers
+
+int laps_of(const bldpc_rm *rm) { return (rm->E + rm->Ncb - 1) / rm->Ncb; }
 
 __global__ __launch_bounds__(256) void k_rm_select(const int *__restrict__ tx_pos, const int *__restrict__ cw, int E, int F, int *__restrict__ tx)
 {
@@ -82,6 +92,108 @@ __global__ __launch_bounds__(256) void k_rm_awgn(const int *__restrict__ map, un
     }
 }
 
+// ---- HARQ: circular profiles and combining ----
+// Position n of rank b in the buffer is sent at e0 = (b - k0) mod Ncb and again at e0 + Ncb, e0 + 2 Ncb, ... < E.  One owner per (n, f)
+// adds its contributions in ascending e, so the order of the fp32 additions is the stated one without atomics.  COMBINE: the sum
+// starts from the stored value, a position without a contribution is not written, a lane whose frame is done returns at once.
+// !COMBINE (recover): the first sample moves as 32 bits, a position without a contribution gets 0x00000000.
+template <bool COMBINE>
+__global__ __launch_bounds__(256) void k_rm_circ(const int *__restrict__ map, const unsigned *__restrict__ rx, int N, int Ncb, int k0, int E, int F,
+                                                 unsigned short_bits, const int *__restrict__ done, unsigned *out)
+{
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    const int n0 = blockIdx.y * kRows;
+    if (f >= F) return;
+    if (COMBINE && done && done[f]) return;
+    for (int n = n0; n < min(N, n0 + kRows); n++) {
+        const int b = map[n]; // wave-uniform, and so is everything derived from it
+        const size_t at = (size_t)n * F + f;
+        if (b == kRmShort) {
+            out[at] = short_bits;
+            continue;
+        }
+        int e = b - k0;
+        if (e < 0) e += Ncb;
+        if (b < 0 || e >= E) { // punctured, or not reached by this transmission
+            if (!COMBINE) out[at] = 0u;
+            continue;
+        }
+        unsigned w = rx[(size_t)e * F + f];
+        if (COMBINE) w = __float_as_uint(__uint_as_float(out[at]) + __uint_as_float(w));
+        for (e += Ncb; e < E; e += Ncb) w = __float_as_uint(__uint_as_float(w) + __uint_as_float(rx[(size_t)e * F + f]));
+        out[at] = w;
+    }
+}
+
+// k_rm_awgn's shape with one LCG state per lap, LAPS >= ceil(E / Ncb), all in registers (every index below is a compile-time constant
+// after unrolling).  Walking ascending n walks ascending e0 except where b passes k0, so the states are re-jumped whenever the draw
+// needed is not the next one: at the first reached position of the run, after an unreached stretch, and at the wrap.  Lap l is live
+// while e0 + l Ncb < E; e0 only grows between two jumps, so a lap that was not jumped is not stepped either.
+template <int LAPS, bool COMBINE>
+__global__ __launch_bounds__(256) void k_rm_awgn_circ(const int *__restrict__ map, unsigned s0, unsigned s1, unsigned s2, float sigma,
+                                                      const int *__restrict__ cw, int N, int Ncb, int k0, int E, int F, float short_llr,
+                                                      const int *__restrict__ done, float *out)
+{
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    const int n0 = blockIdx.y * kRows;
+    if (f >= F) return;
+    if (COMBINE && done && done[f]) return; // no jump, no draw, no store: the frame's draws stay unused
+    unsigned s[LAPS][3];
+    int next = -1; // the e0 whose draws the states stand at
+    const double two_pi = 2 * 3.1415926;
+    for (int n = n0; n < min(N, n0 + kRows); n++) {
+        const int b = map[n]; // wave-uniform
+        const size_t at = (size_t)n * F + f;
+        if (b == kRmShort) {
+            out[at] = short_llr;
+            continue;
+        }
+        int e0 = b - k0;
+        if (e0 < 0) e0 += Ncb;
+        if (b < 0 || e0 >= E) {
+            if (!COMBINE) out[at] = 0.0f;
+            continue;
+        }
+        if (e0 != next) {
+#pragma unroll
+            for (int l = 0; l < LAPS; l++)
+                if (e0 + l * Ncb < E) {
+                    s[l][0] = s0, s[l][1] = s1, s[l][2] = s2;
+                    jump(s[l], 2ull * ((unsigned long long)f * E + (unsigned)(e0 + l * Ncb)));
+                }
+        }
+        next = e0 + 1;
+        const int c = cw ? cw[at] : 0;
+        float v = COMBINE ? out[at] : 0.0f;
+#pragma unroll
+        for (int l = 0; l < LAPS; l++)
+            if (e0 + l * Ncb < E) {
+                const float u[2] = {uniform(s[l]), uniform(s[l])};
+                const float amp = sqrtf(-2.0f * logf(1.0f - u[0]));
+                const float y = (float)((double)sigma * sin(two_pi * (double)u[1]) * (double)amp + 1.0 - (double)(2 * c));
+                v = (!COMBINE && l == 0) ? y : v + y;
+            }
+        out[at] = v;
+    }
+}
+
+// The columns idx[0] < idx[1] < ... of a [rows][F] array of 32-bit words, to or from a [rows][Fa] array: thread a along threadIdx.x,
+// kRows rows per thread.  An index outside [0, F) breaks the precondition; it moves nothing.
+template <bool SCATTER>
+__global__ __launch_bounds__(256) void k_frames(const unsigned *__restrict__ src, int rows, int F, const int *__restrict__ idx, int Fa,
+                                                unsigned *__restrict__ dst)
+{
+    const int a = blockIdx.x * 256 + threadIdx.x;
+    const int r0 = blockIdx.y * kRows;
+    if (a >= Fa) return;
+    const int i = idx[a];
+    if ((unsigned)i >= (unsigned)F) return;
+    for (int r = r0; r < min(rows, r0 + kRows); r++) {
+        if (SCATTER) dst[(size_t)r * F + i] = src[(size_t)r * Fa + a];
+        else dst[(size_t)r * Fa + a] = src[(size_t)r * F + i];
+    }
+}
+
 int check_rm(const bldpc_rm *rm, int F, const char *who)
 {
     if (!rm) return fail(BLDPC_EINVAL, "%s: null profile", who);
@@ -119,17 +231,68 @@ unsigned bits_of(float v)
     return u;
 }
 
+// The words of "recover" and "combine" on a circular profile (include/bldpc.h), position by position and frame by frame.  combine:
+// the sum starts from acc and frames with done[f] != 0 are passed over; recover: it starts from the 32 bits of the first sample.
+void circ_host(const bldpc_rm *rm, const float *rx, int F, float short_llr, const int *done, float *acc, bool combine)
+{
+    for (int n = 0; n < rm->N; n++) {
+        const int b = rm->map[n];
+        const int e0 = b < 0 ? -1 : (b - rm->k0 + rm->Ncb) % rm->Ncb;
+        for (int f = 0; f < F; f++) {
+            if (combine && done && done[f]) continue;
+            float *v = acc + (size_t)n * F + f;
+            if (b == kRmShort) *v = short_llr;
+            else if (b < 0 || e0 >= rm->E) {
+                if (!combine) memset(v, 0, 4);
+            } else {
+                int e = e0;
+                if (!combine) {
+                    memcpy(v, rx + (size_t)e * F + f, 4);
+                    e += rm->Ncb;
+                }
+                for (; e < rm->E; e += rm->Ncb) *v = *v + rx[(size_t)e * F + f];
+            }
+        }
+    }
+}
+
+// The circular kernels serve every profile: a linear one is the buffer read once from its start (k0 = 0, E = Ncb).
+template <bool COMBINE> int launch_circ(const bldpc_rm *rm, const float *rx, int F, float short_llr, const int *done, float *out, void *stream)
+{
+    hipLaunchKernelGGL(k_rm_circ<COMBINE>, grid_of(F, rm->N), dim3(256), 0, (hipStream_t)stream, rm->d_map, (const unsigned *)rx, rm->N, rm->Ncb,
+                       rm->k0, rm->E, F, bits_of(short_llr), done, (unsigned *)out);
+    CLDPC_HIP(hipGetLastError(), BLDPC_EHIP);
+    return BLDPC_OK;
+}
+
+template <bool COMBINE>
+int launch_awgn_circ(const bldpc_rm *rm, const int seed[3], float sigma, const int *cw, int F, float short_llr, const int *done, float *out, void *stream)
+{
+    const int laps = laps_of(rm);
+#define CLDPC_CIRC(L)                                                                                                                         \
+    hipLaunchKernelGGL((k_rm_awgn_circ<L, COMBINE>), grid_of(F, rm->N), dim3(256), 0, (hipStream_t)stream, rm->d_map, (unsigned)seed[0],      \
+                       (unsigned)seed[1], (unsigned)seed[2], sigma, cw, rm->N, rm->Ncb, rm->k0, rm->E, F, short_llr, done, out)
+    if (laps <= 1) CLDPC_CIRC(1);
+    else if (laps <= 2) CLDPC_CIRC(2);
+    else if (laps <= 4) CLDPC_CIRC(4);
+    else CLDPC_CIRC(8);
+#undef CLDPC_CIRC
+    CLDPC_HIP(hipGetLastError(), BLDPC_EHIP);
+    return BLDPC_OK;
+}
+
 } // namespace
 
 // ------------------------------------------------------------------------------------------------------------ profile
-extern "C" int bldpc_rm_create(int N, const int *short_pos, int n_short, const int *punct_pos, int n_punct, bldpc_rm **out)
+// what bldpc_rm_create and bldpc_rm_create_circular share: the checks, map[] and the buffer (tx_pos ascending); `who` names the entry
+static int rm_build(const char *who, int N, const int *short_pos, int n_short, const int *punct_pos, int n_punct, bldpc_rm **out)
 {
-    if (!out) return fail(BLDPC_EINVAL, "bldpc_rm_create: null result pointer");
+    if (!out) return fail(BLDPC_EINVAL, "%s: null result pointer", who);
     *out = nullptr;
-    if (N < 1 || N > kMaxN) return fail(BLDPC_EINVAL, "bldpc_rm_create: N=%d outside [1, %d]", N, kMaxN);
-    if (n_short < 0 || n_punct < 0) return fail(BLDPC_EINVAL, "bldpc_rm_create: negative count (n_short=%d, n_punct=%d)", n_short, n_punct);
+    if (N < 1 || N > kMaxN) return fail(BLDPC_EINVAL, "%s: N=%d outside [1, %d]", who, N, kMaxN);
+    if (n_short < 0 || n_punct < 0) return fail(BLDPC_EINVAL, "%s: negative count (n_short=%d, n_punct=%d)", who, n_short, n_punct);
     if ((n_short && !short_pos) || (n_punct && !punct_pos))
-        return fail(BLDPC_EINVAL, "bldpc_rm_create: null list with a non-zero count (n_short=%d, n_punct=%d)", n_short, n_punct);
+        return fail(BLDPC_EINVAL, "%s: null list with a non-zero count (n_short=%d, n_punct=%d)", who, n_short, n_punct);
     bldpc_rm *rm = new (std::nothrow) bldpc_rm;
     if (!rm) return fail(BLDPC_ENOMEM, "out of host memory");
     try {
@@ -147,9 +310,9 @@ extern "C" int bldpc_rm_create(int N, const int *short_pos, int n_short, const i
         for (int i = 0; i < l.n; i++) {
             const int p = l.pos[i];
             int r = BLDPC_OK;
-            if (p < 0 || p >= N) r = fail(BLDPC_EINVAL, "bldpc_rm_create: %s position %d out of range [0, %d)", l.name, p, N);
-            else if (rm->map[p] == l.kind) r = fail(BLDPC_EINVAL, "bldpc_rm_create: %s position %d repeated", l.name, p);
-            else if (rm->map[p] != 0) r = fail(BLDPC_EINVAL, "bldpc_rm_create: position %d is in both lists", p);
+            if (p < 0 || p >= N) r = fail(BLDPC_EINVAL, "%s: %s position %d out of range [0, %d)", who, l.name, p, N);
+            else if (rm->map[p] == l.kind) r = fail(BLDPC_EINVAL, "%s: %s position %d repeated", who, l.name, p);
+            else if (rm->map[p] != 0) r = fail(BLDPC_EINVAL, "%s: position %d is in both lists", who, p);
             if (r) {
                 delete rm;
                 return r;
@@ -159,10 +322,10 @@ extern "C" int bldpc_rm_create(int N, const int *short_pos, int n_short, const i
     rm->N = N;
     rm->n_short = n_short;
     rm->n_punct = n_punct;
-    rm->E = N - n_short - n_punct; // the lists are disjoint and free of repeats
+    rm->E = rm->Ncb = N - n_short - n_punct; // the lists are disjoint and free of repeats
     if (rm->E < 1) {
         delete rm;
-        return fail(BLDPC_EINVAL, "bldpc_rm_create: E = N - n_short - n_punct = %d, nothing is transmitted", N - n_short - n_punct);
+        return fail(BLDPC_EINVAL, "%s: E = N - n_short - n_punct = %d, nothing is transmitted", who, N - n_short - n_punct);
     }
     for (int n = 0; n < N; n++) {
         if (rm->map[n] == 0) {
@@ -172,6 +335,53 @@ extern "C" int bldpc_rm_create(int N, const int *short_pos, int n_short, const i
             rm->short_pos.push_back(n);
     }
     *out = rm;
+    return BLDPC_OK;
+}
+
+extern "C" int bldpc_rm_create(int N, const int *short_pos, int n_short, const int *punct_pos, int n_punct, bldpc_rm **out)
+{
+    return rm_build("bldpc_rm_create", N, short_pos, n_short, punct_pos, n_punct, out);
+}
+
+extern "C" int bldpc_rm_create_circular(int N, const int *short_pos, int n_short, const int *punct_pos, int n_punct, int k0, int E, bldpc_rm **out)
+{
+    static const char *who = "bldpc_rm_create_circular";
+    int r = rm_build(who, N, short_pos, n_short, punct_pos, n_punct, out);
+    if (r) return r;
+    bldpc_rm *rm = *out;
+    *out = nullptr;
+    const int Ncb = rm->Ncb;
+    if (k0 < 0 || k0 >= Ncb) r = fail(BLDPC_EINVAL, "%s: k0=%d outside [0, Ncb=%d)", who, k0, Ncb);
+    else if (E < 1) r = fail(BLDPC_EINVAL, "%s: E=%d, nothing is transmitted", who, E);
+    else if ((long long)E > (long long)kMaxLaps * Ncb) r = fail(BLDPC_EINVAL, "%s: E=%d is more than %d laps of the buffer (Ncb=%d)", who, E, kMaxLaps, Ncb);
+    else if (E > kMaxN) r = fail(BLDPC_EINVAL, "%s: E=%d outside [1, %d]", who, E, kMaxN);
+    if (r) {
+        delete rm;
+        return r;
+    }
+    try {
+        std::vector<int> buf; // the ascending list rm_build left
+        buf.swap(rm->tx_pos);
+        rm->tx_pos.resize(E);
+        for (int e = 0; e < E; e++) rm->tx_pos[e] = buf[(size_t)((long long)k0 + e) % Ncb];
+    } catch (const std::bad_alloc &) {
+        delete rm;
+        return fail(BLDPC_ENOMEM, "out of host memory");
+    }
+    rm->circular = true;
+    rm->k0 = k0;
+    rm->E = E;
+    *out = rm;
+    return BLDPC_OK;
+}
+
+extern "C" int bldpc_rm_circ(const bldpc_rm *rm, int info[4])
+{
+    if (!rm || !info) return fail(BLDPC_EINVAL, "bldpc_rm_circ: null argument");
+    info[0] = rm->Ncb;
+    info[1] = rm->k0;
+    info[2] = rm->E;
+    info[3] = laps_of(rm);
     return BLDPC_OK;
 }
 
@@ -216,6 +426,10 @@ extern "C" int bldpc_rm_recover_host(const bldpc_rm *rm, const float *rx, int F,
     int r = check_rm(rm, F, "bldpc_rm_recover_host");
     if (r || (r = check_short_llr(short_llr, "bldpc_rm_recover_host"))) return r;
     if (!rx || !out) return fail(BLDPC_EINVAL, "bldpc_rm_recover_host: null argument");
+    if (rm->circular) {
+        circ_host(rm, rx, F, short_llr, nullptr, out, false);
+        return BLDPC_OK;
+    }
     for (int n = 0; n < rm->N; n++) {
         const int e = rm->map[n];
         float *row = out + (size_t)n * F;
@@ -243,6 +457,72 @@ extern "C" int bldpc_rm_awgn_channel_host(const bldpc_rm *rm, int seed[3], float
     return bldpc_rm_recover_host(rm, rx.data(), F, short_llr, out);
 }
 
+extern "C" int bldpc_rm_combine_host(const bldpc_rm *rm, const float *rx, int F, float short_llr, const int *done, float *acc)
+{
+    int r = check_rm(rm, F, "bldpc_rm_combine_host");
+    if (r || (r = check_short_llr(short_llr, "bldpc_rm_combine_host"))) return r;
+    if (!rx || !acc) return fail(BLDPC_EINVAL, "bldpc_rm_combine_host: null argument");
+    circ_host(rm, rx, F, short_llr, done, acc, true);
+    return BLDPC_OK;
+}
+
+extern "C" int bldpc_rm_awgn_combine_host(const bldpc_rm *rm, int seed[3], float sigma, const int *cw, int F, float short_llr, const int *done,
+                                          float *acc)
+{
+    int r = check_rm(rm, F, "bldpc_rm_awgn_combine_host");
+    if (r || (r = check_short_llr(short_llr, "bldpc_rm_awgn_combine_host"))) return r;
+    if (!seed || !acc) return fail(BLDPC_EINVAL, "bldpc_rm_awgn_combine_host: null argument");
+    std::vector<float> rx;
+    std::vector<int> tx;
+    try {
+        rx.resize((size_t)rm->E * F);
+        if (cw) tx.resize((size_t)rm->E * F);
+    } catch (const std::bad_alloc &) {
+        return fail(BLDPC_ENOMEM, "out of host memory");
+    }
+    if (cw && (r = bldpc_rm_select_host(rm, cw, F, tx.data()))) return r;
+    if ((r = bldpc_awgn_channel_host(seed, sigma, rx.data(), cw ? tx.data() : nullptr, rm->E, F))) return r;
+    return bldpc_rm_combine_host(rm, rx.data(), F, short_llr, done, acc);
+}
+
+static int check_frames(const void *src, int rows, int F, const void *idx, int Fa, const void *dst, const char *who)
+{
+    if (!src || !idx || !dst) return fail(BLDPC_EINVAL, "%s: null argument", who);
+    if (rows < 1 || rows > kMaxN) return fail(BLDPC_EINVAL, "%s: rows=%d outside [1, %d]", who, rows, kMaxN);
+    if (F < 1 || Fa < 1 || Fa > F) return fail(BLDPC_EINVAL, "%s: Fa=%d outside [1, F=%d]", who, Fa, F);
+    return BLDPC_OK;
+}
+
+static int check_idx_host(const int *idx, int F, int Fa, const char *who)
+{
+    for (int a = 0; a < Fa; a++)
+        if (idx[a] < 0 || idx[a] >= F || (a && idx[a] <= idx[a - 1]))
+            return fail(BLDPC_EINVAL, "%s: idx[%d]=%d: the list must be strictly ascending in [0, F=%d)", who, a, idx[a], F);
+    return BLDPC_OK;
+}
+
+extern "C" int bldpc_frames_gather_host(const void *src, int rows, int F, const int *idx, int Fa, void *dst)
+{
+    int r = check_frames(src, rows, F, idx, Fa, dst, "bldpc_frames_gather_host");
+    if (r || (r = check_idx_host(idx, F, Fa, "bldpc_frames_gather_host"))) return r;
+    const unsigned *s = (const unsigned *)src;
+    unsigned *d = (unsigned *)dst;
+    for (int row = 0; row < rows; row++)
+        for (int a = 0; a < Fa; a++) d[(size_t)row * Fa + a] = s[(size_t)row * F + idx[a]];
+    return BLDPC_OK;
+}
+
+extern "C" int bldpc_frames_scatter_host(const void *src, int rows, int F, const int *idx, int Fa, void *dst)
+{
+    int r = check_frames(src, rows, F, idx, Fa, dst, "bldpc_frames_scatter_host");
+    if (r || (r = check_idx_host(idx, F, Fa, "bldpc_frames_scatter_host"))) return r;
+    const unsigned *s = (const unsigned *)src;
+    unsigned *d = (unsigned *)dst;
+    for (int row = 0; row < rows; row++)
+        for (int a = 0; a < Fa; a++) d[(size_t)row * F + idx[a]] = s[(size_t)row * Fa + a];
+    return BLDPC_OK;
+}
+
 // ------------------------------------------------------------------------------------------------------------- device
 extern "C" int bldpc_rm_select(const bldpc_rm *rm, const int *cw, int F, int *tx, void *stream)
 {
@@ -261,6 +541,7 @@ extern "C" int bldpc_rm_recover(const bldpc_rm *rm, const float *rx, int F, floa
     if (r || (r = check_short_llr(short_llr, "bldpc_rm_recover"))) return r;
     if (!rx || !out) return fail(BLDPC_EINVAL, "bldpc_rm_recover: null argument");
     if ((r = device_tables(rm))) return r;
+    if (rm->circular) return launch_circ<false>(rm, rx, F, short_llr, nullptr, out, stream);
     hipLaunchKernelGGL(k_rm_recover, grid_of(F, rm->N), dim3(256), 0, (hipStream_t)stream, rm->d_map, (const unsigned *)rx, rm->N, F,
                        bits_of(short_llr), (unsigned *)out);
     CLDPC_HIP(hipGetLastError(), BLDPC_EHIP);
@@ -276,10 +557,55 @@ extern "C" int bldpc_rm_awgn_channel_device(const bldpc_rm *rm, int seed[3], flo
     int i = 0;
     if (!seed_in_range(seed, &i)) return fail(BLDPC_EINVAL, "seed[%d]=%d outside [0,%u)", i, seed[i], kM[i]);
     if ((r = device_tables(rm))) return r;
-    hipLaunchKernelGGL(k_rm_awgn, grid_of(F, rm->N), dim3(256), 0, (hipStream_t)stream, rm->d_map, (unsigned)seed[0], (unsigned)seed[1],
-                       (unsigned)seed[2], sigma, cw, rm->N, rm->E, F, short_llr, out);
-    CLDPC_HIP(hipGetLastError(), BLDPC_EHIP);
+    if (rm->circular) {
+        if ((r = launch_awgn_circ<false>(rm, seed, sigma, cw, F, short_llr, nullptr, out, stream))) return r;
+    } else {
+        hipLaunchKernelGGL(k_rm_awgn, grid_of(F, rm->N), dim3(256), 0, (hipStream_t)stream, rm->d_map, (unsigned)seed[0], (unsigned)seed[1],
+                           (unsigned)seed[2], sigma, cw, rm->N, rm->E, F, short_llr, out);
+        CLDPC_HIP(hipGetLastError(), BLDPC_EHIP);
+    }
     jump(seed, 2ull * (unsigned long long)rm->E * F);
+    return BLDPC_OK;
+}
+
+extern "C" int bldpc_rm_combine(const bldpc_rm *rm, const float *rx, int F, float short_llr, const int *done, float *acc, void *stream)
+{
+    int r = check_rm(rm, F, "bldpc_rm_combine");
+    if (r || (r = check_short_llr(short_llr, "bldpc_rm_combine"))) return r;
+    if (!rx || !acc) return fail(BLDPC_EINVAL, "bldpc_rm_combine: null argument");
+    if ((r = device_tables(rm))) return r;
+    return launch_circ<true>(rm, rx, F, short_llr, done, acc, stream);
+}
+
+extern "C" int bldpc_rm_awgn_combine_device(const bldpc_rm *rm, int seed[3], float sigma, const int *cw, int F, float short_llr, const int *done,
+                                            float *acc, void *stream)
+{
+    int r = check_rm(rm, F, "bldpc_rm_awgn_combine_device");
+    if (r || (r = check_short_llr(short_llr, "bldpc_rm_awgn_combine_device"))) return r;
+    if (!seed || !acc) return fail(BLDPC_EINVAL, "bldpc_rm_awgn_combine_device: null argument");
+    int i = 0;
+    if (!seed_in_range(seed, &i)) return fail(BLDPC_EINVAL, "seed[%d]=%d outside [0,%u)", i, seed[i], kM[i]);
+    if ((r = device_tables(rm))) return r;
+    if ((r = launch_awgn_circ<true>(rm, seed, sigma, cw, F, short_llr, done, acc, stream))) return r;
+    jump(seed, 2ull * (unsigned long long)rm->E * F); // whatever done holds
+    return BLDPC_OK;
+}
+
+extern "C" int bldpc_frames_gather(const void *src, int rows, int F, const int *idx, int Fa, void *dst, void *stream)
+{
+    int r = check_frames(src, rows, F, idx, Fa, dst, "bldpc_frames_gather");
+    if (r) return r;
+    hipLaunchKernelGGL(k_frames<false>, grid_of(Fa, rows), dim3(256), 0, (hipStream_t)stream, (const unsigned *)src, rows, F, idx, Fa, (unsigned *)dst);
+    CLDPC_HIP(hipGetLastError(), BLDPC_EHIP);
+    return BLDPC_OK;
+}
+
+extern "C" int bldpc_frames_scatter(const void *src, int rows, int F, const int *idx, int Fa, void *dst, void *stream)
+{
+    int r = check_frames(src, rows, F, idx, Fa, dst, "bldpc_frames_scatter");
+    if (r) return r;
+    hipLaunchKernelGGL(k_frames<true>, grid_of(Fa, rows), dim3(256), 0, (hipStream_t)stream, (const unsigned *)src, rows, F, idx, Fa, (unsigned *)dst);
+    CLDPC_HIP(hipGetLastError(), BLDPC_EHIP);
     return BLDPC_OK;
 }
 

@@ -5,7 +5,8 @@ struct bldpc_code;
 
 namespace cldpc {
 
-// The profile's one table, int [N]: the rank e >= 0 of a transmitted position among the transmitted ones, or one of these.
+// The profile's one table, int [N]: the rank b >= 0 of a position in the buffer (the positions neither shortened nor punctured,
+// ascending; a linear profile transmits them in this order, so b is its e), or one of these.
 constexpr int kRmPunct = -1, kRmShort = -2;
 
 // bldpc_encode.hip: bldpc_encode_random with every message bit whose information position is marked kRmShort in d_map (device

@@ -6,14 +6,17 @@ float advanced by a double step).  Differences: shapes are arguments instead of 
 statistics run on the device, and the batch may be sharded over ranks (sharding.py) with one all-reduce
 of the counters per batch.
 """
+from dataclasses import dataclass, field
+
 import numpy as np
 import torch
 
 from . import sharding
 from ._lib import check, lib
 from .bldpc import (EXIT_BATCH_GLOBAL, EXIT_FIXED, EXIT_PER_FRAME, KERNEL_AUTO, STOP_PREFIX, STOP_SYNDROME, AWGNChannel_CPU, AWGNChannel_GPU,
-                    AWGNChannel_QAM_GPU, AWGNChannel_RM_GPU, Decode_Statistic, Demodulate_QAM, LDPC_Decoder_GPU, LDPC_Decoder_Layered_GPU,
-                    Modulate_QAM, PN_CodeWords, RM_Recover, RM_Select, SimCounters, Syndrome, _dev_ptr, sigma_of)
+                    AWGNChannel_QAM_GPU, AWGNChannel_RM_Combine_GPU, AWGNChannel_RM_GPU, Decode_Statistic, Demodulate_QAM, Frames_Gather,
+                    Frames_Scatter, LDPC_Decoder_GPU, LDPC_Decoder_Layered_GPU, Modulate_QAM, PN_CodeWords, RM_Recover, RM_Select, SimCounters,
+                    Syndrome, _dev_ptr, sigma_of)
 from .nbldpc import sigma_of as nb_sigma_of
 
 
@@ -163,6 +166,189 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
             log(format_row(SIM, ber_bits))
         if stop or (max_batches is not None and batches >= max_batches):
             return 1 if stop else 0
+
+
+@dataclass
+class HarqCounters:
+    """What Simulation_HARQ_GPU accumulates over the batches of one SNR point, all exact integers.  acked[t]: frames acknowledged at
+    transmission t (0-based); undetected[t]: those of them whose first K bits differ from the word sent; never_acked: frames still
+    unacknowledged after the last transmission; bits_sent: the sum of E_t over the transmissions each frame used."""
+    num_Frames: int = 0
+    acked: list = field(default_factory=list)
+    undetected: list = field(default_factory=list)
+    never_acked: int = 0
+    bits_sent: int = 0
+    Total_Iteration: int = 0
+    SNR: float = 0.0
+
+    def ratios(self, info_bits):
+        """FER after each transmission (a frame is good once it is acknowledged with the right word), mean transmissions per frame
+        and throughput = info_bits * correctly acknowledged frames / bits sent."""
+        n, T = max(self.num_Frames, 1), len(self.acked)
+        good = np.cumsum([a - u for a, u in zip(self.acked, self.undetected)])
+        used = sum((t + 1) * a for t, a in enumerate(self.acked)) + T * self.never_acked
+        return dict(FER=[1.0 - g / n for g in good], MeanTx=used / n, Throughput=info_bits * (int(good[-1]) if T else 0) / max(self.bits_sent, 1),
+                    AverageIT=self.Total_Iteration / n)
+
+
+def format_harq_row(SIM, info_bits):
+    """SNR NTF, the FER after each transmission, mean transmissions, throughput, iterations per frame."""
+    r = SIM.ratios(info_bits)
+    return " %.1f %8d  %s  %.3f  %.4f  %.2f" % (SIM.SNR, SIM.num_Frames, " ".join("%6.4e" % x for x in r["FER"]), r["MeanTx"], r["Throughput"],
+                                             r["AverageIT"])
+
+
+def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, maxIT=50, exit_mode=EXIT_FIXED, kernel=KERNEL_AUTO,
+                        leastErrorFrames=50, leastTestFrames=10000, dist=None, device=None, max_batches=None, log=print, PN_Message=0,
+                        pn_seed=0, schedule="flooding", alpha=1.0, stop_rule=None, short_llr=1.0e4, compact=True, keep_D=None):
+    """One SNR point of incremental-redundancy HARQ over BPSK on the device channel.  rvs = [rm_0, ..., rm_{T-1}]: the profile of
+    each transmission (RateMatch.circular or RateMatch, all over code.N with the same shortened positions).  SIM is a HarqCounters.
+
+    A batch: rvs[0] is sent for all F frames (AWGNChannel_RM_GPU: recover semantics) and decoded; row N of D is the ACK.  For
+    t = 1 .. T-1, while a frame of this rank is unacknowledged: rvs[t] is combined into the decoder input of the unacknowledged frames
+    (AWGNChannel_RM_Combine_GPU under done = D[N]), those frames are gathered (Frames_Gather on torch.nonzero of the flag row), decoded
+    and their D and iteration counts scattered back.  compact=False decodes the whole batch instead; the per-frame results of
+    EXIT_FIXED and EXIT_PER_FRAME do not depend on the batch, so the counters and D are the same.
+
+    The ACK must hold for the word that was sent.  PN_Message=0 (the all-zero word): the decoder's own flag, flooding (plain, or
+    normalised with alpha != 1.0) or layered, EXIT_FIXED or EXIT_PER_FRAME.  PN_Message=1 (random codewords): flooding with EXIT_FIXED
+    followed by Syndrome(into_flag_row=True), or layered with STOP_SYNDROME (its default here) and either exit.  EXIT_BATCH_GLOBAL is
+    refused: its results depend on the batch.  A position no transmission has reached yet holds +0.0 and decides 0, so on the all-zero
+    word the flag flatters a first transmission with E < Ncb; random codewords do not have that bias.
+
+    Draws: transmission t of a batch owns 2 * E_t * F draws of the noise stream, used or not -- `seed` (int32[3]) is advanced by the
+    sum over all T transmissions after every batch on every rank, whatever was acknowledged, and rank r jumps first_r * 2 * E_t draws
+    into each.  One all-reduce of the counters per batch.  keep_D (a list) receives this rank's final D of every batch."""
+    if PN_Message not in (0, 1):
+        raise ValueError("PN_Message must be 0 (all-zero codeword) or 1 (random codewords)")
+    if schedule not in ("flooding", "layered"):
+        raise ValueError("schedule must be 'flooding' or 'layered'")
+    layered = schedule == "layered"
+    if exit_mode not in (EXIT_FIXED, EXIT_PER_FRAME):
+        raise ValueError("HARQ takes EXIT_FIXED or EXIT_PER_FRAME: the results of EXIT_BATCH_GLOBAL depend on the batch")
+    if not layered and stop_rule is not None:
+        raise ValueError("stop_rule belongs to schedule='layered'")
+    norm = not layered and alpha != 1.0
+    if layered:
+        if stop_rule is None:
+            stop_rule = STOP_SYNDROME if PN_Message else STOP_PREFIX
+        if stop_rule not in (STOP_PREFIX, STOP_SYNDROME):
+            raise ValueError("stop_rule must be STOP_PREFIX or STOP_SYNDROME")
+        if PN_Message == 1 and stop_rule != STOP_SYNDROME and exit_mode != EXIT_FIXED:
+            raise ValueError("PN_Message=1 with per-frame exit needs stop_rule=STOP_SYNDROME: STOP_PREFIX tests for the all-zero word")
+    elif PN_Message == 1 and exit_mode != EXIT_FIXED:
+        raise ValueError("PN_Message=1 needs exit_mode=EXIT_FIXED: the flooding decoders' early exit tests for the all-zero word")
+    rvs = list(rvs) if rvs is not None else []
+    if not rvs:
+        raise ValueError("rvs must hold at least one profile")
+    for t, rm in enumerate(rvs):
+        if rm.N != code.N:
+            raise ValueError("rvs[%d] is over N=%d positions, the code has N=%d" % (t, rm.N, code.N))
+        if not np.array_equal(rm.shorten, rvs[0].shorten):
+            raise ValueError("rvs[%d] shortens other positions than rvs[0]: the shortened bits are fixed by the codeword, not by the transmission" % t)
+    if not (np.isfinite(short_llr) and short_llr > 0):
+        raise ValueError("short_llr must be finite and > 0, not %r" % (short_llr,))
+    if PN_Message and rvs[0].n_short and not np.isin(rvs[0].shorten, code.info_positions).all():
+        raise ValueError("rvs shorten a parity position of the code's generator; only information positions (code.info_positions) "
+                         "can be agreed to be 0")
+    T = len(rvs)
+    if not SIM.acked:
+        SIM.acked, SIM.undetected = [0] * T, [0] * T
+    if len(SIM.acked) != T:
+        raise ValueError("SIM holds counters of %d transmissions, rvs has %d" % (len(SIM.acked), T))
+    rank = dist.get_rank() if dist is not None and dist.is_initialized() else 0
+    world = dist.get_world_size() if dist is not None and dist.is_initialized() else 1
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    F = Num_Frames_OneTime
+    first, count = sharding.shard_frames(F, world, rank)
+    N, K = code.N, code.K
+    info_bits = K - rvs[0].n_short
+    cnt = torch.zeros(2 * T + 3, dtype=torch.int64, device=device)  # acked[T], undetected[T], never, bits, iterations
+
+    def decode(y, D):
+        """Decode y into D, leave the ACK in row N, return the iterations of every frame (int32 [F'])."""
+        if layered:
+            r = LDPC_Decoder_Layered_GPU(code, y, max_iter=maxIT, alpha=alpha, length=K, exit_mode=exit_mode, stop_rule=stop_rule, D=D)
+            if PN_Message and stop_rule != STOP_SYNDROME:
+                Syndrome(code, D, into_flag_row=True)
+            return r["iters"]
+        r = LDPC_Decoder_GPU(code, y, max_iter=maxIT, length=K, exit_mode=exit_mode, kernel=kernel, D=D, alpha=alpha if norm else None)
+        if PN_Message:
+            Syndrome(code, D, into_flag_row=True)
+        if r.get("iters") is not None:
+            return r["iters"]
+        return torch.full((y.shape[1],), r["iteraTime"], dtype=torch.int32, device=device)
+
+    batches = 0
+    while True:
+        SIM.num_Frames += F
+        cnt.zero_()
+        if count:
+            cw = PN_CodeWords(code, pn_seed, count, first_frame=batches * F + first, device=device, rate_match=rvs[0]) if PN_Message else None
+            D = torch.empty((N + 1, count), dtype=torch.int32, device=device)
+            acked = torch.zeros(count, dtype=torch.bool, device=device)
+        for t, rm in enumerate(rvs):
+            per_frame = sharding.binary_draws_per_frame(rm.E)
+            my_seed = sharding.lcg_jump(seed, first * per_frame)
+            seed[:] = sharding.lcg_jump(seed, F * per_frame)  # owned by this transmission whether it is used or not
+            if not count or (t and bool(acked.all())):
+                continue
+            active = ~acked
+            if t == 0:
+                acc = AWGNChannel_RM_GPU(rm, my_seed, sigma, count, device=device, CodeWord=cw, short_llr=short_llr)
+                iters = decode(acc, D)
+            else:
+                AWGNChannel_RM_Combine_GPU(rm, my_seed, sigma, acc, done=D[N], CodeWord=cw, short_llr=short_llr)
+                if compact:
+                    idx = torch.nonzero(active).view(-1).to(torch.int32)
+                    Da = torch.empty((N + 1, idx.numel()), dtype=torch.int32, device=device)
+                    ia = decode(Frames_Gather(acc, idx), Da)
+                    Frames_Scatter(Da, idx, D)
+                    Frames_Scatter(ia, idx, iters)
+                else:
+                    iters = decode(acc, D)
+            now = (D[N] != 0) & active
+            wrong = ((D[:K] != cw[:K]) if cw is not None else (D[:K] != 0)).any(0)
+            cnt[t] += now.sum()
+            cnt[T + t] += (now & wrong).sum()
+            cnt[2 * T + 1] += rm.E * active.sum()
+            cnt[2 * T + 2] += iters[active].sum()
+            acked |= now
+        if count:
+            cnt[2 * T] += (~acked).sum()
+            if keep_D is not None:
+                keep_D.append(D)
+        sharding.allreduce_counters(cnt, dist)
+        c = cnt.cpu().tolist()
+        for t in range(T):
+            SIM.acked[t] += c[t]
+            SIM.undetected[t] += c[T + t]
+        SIM.never_acked += c[2 * T]
+        SIM.bits_sent += c[2 * T + 1]
+        SIM.Total_Iteration += c[2 * T + 2]
+        batches += 1
+        errors = SIM.never_acked + sum(SIM.undetected)
+        stop = errors >= leastErrorFrames and SIM.num_Frames >= leastTestFrames
+        last = max_batches is not None and batches >= max_batches
+        if rank == 0 and log and (stop or last):
+            log(format_harq_row(SIM, info_bits))
+        if stop or last:
+            return 1 if stop else 0
+
+
+def sweep_harq(code, rvs, startSNR=0.0, stopSNR=13.0, stepSNR=0.2, snrtype=1, seeds=(173, 173, 173), dist=None, log=print, **kw):
+    """The sweep of `sweep` over Simulation_HARQ_GPU: a list of HarqCounters, one per SNR point.  Under Eb/N0 (snrtype 0) sigma comes
+    from the rate of the FIRST transmission, rvs[0].rate(code.K): the operating point is named by what is sent when nothing goes wrong,
+    and the later transmissions run over the same channel."""
+    out = []
+    rate = rvs[0].rate(code.K)
+    for snr in snr_grid(startSNR, stopSNR, stepSNR):
+        seed = np.array(seeds, np.int32)
+        SIM = HarqCounters()
+        SIM.SNR = snr
+        Simulation_HARQ_GPU(code, seed, sigma_of(snr, snrtype, rate), SIM, rvs, dist=dist, log=log, **kw)
+        out.append(SIM)
+    return out
 
 
 def format_row(SIM, length):

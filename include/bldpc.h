@@ -374,7 +374,8 @@ int bldpc_qam_demap_host(const float *rx, const float *constellation, int q, flo
  *   rx           device float [E][F]                                                Channel_Out  device float [N][F]
  * All arrays frame-fastest.  The device calls are asynchronous on `stream` and allocate nothing per call (the profile's device
  * tables are uploaded by the first of them: use a profile from one host thread at a time, like a code object).
- * Out of scope: hard-decision (BSC) input, repetition (E > N), the position lists of any standard, the GF(q) half. */
+ * Out of scope: hard-decision (BSC) input, the position lists of any standard, HARQ over QAM in the sweep (the primitives compose
+ * with bldpc_qam_demap through bldpc_rm_combine, see "HARQ" below), the GF(q) half. */
 typedef struct bldpc_rm bldpc_rm; /* opaque: the kind of every position, its rank among the transmitted ones, tx_pos; host + device */
 
 /* Positions are codeword positions in [0, N), in any order.  BLDPC_EINVAL: a position out of range, a position repeated or present
@@ -407,6 +408,74 @@ int bldpc_rm_awgn_channel_host(const bldpc_rm *rm, int seed[3], float sigma, con
  * Punctured positions play no part.  Other arguments, limits and asynchrony as bldpc_encode_random. */
 int bldpc_rm_encode_random(bldpc_code *code, const bldpc_rm *rm, unsigned long long seed, long long first_frame, int F, int *msg,
                            int *CodeWord, void *stream);
+
+/* -- HARQ: circular-buffer rate matching, soft combining, frame compaction (not in the reference) -- */
+
+/* A circular profile reads the BUFFER of a profile -- the Ncb = N - n_short - n_punct positions that are neither shortened nor
+ * punctured, ascending, buf[0..Ncb), what bldpc_rm_create calls the transmitted positions -- from a redundancy-version start k0 for
+ * E positions, around the end and as often as E asks:
+ *
+ *   tx_pos[e] = buf[(k0 + e) mod Ncb],  0 <= e < E       no longer ascending; E > Ncb repeats positions, E < Ncb leaves the positions
+ *                                                       not reached without a sample in this transmission; punctured positions are
+ *                                                       never sent by any transmission
+ *   Position n of rank b in the buffer (buf[b] = n) has the contributions e_0 = (b - k0) mod Ncb, e_0 + Ncb, e_0 + 2 Ncb, ... < E.
+ *
+ *   select:   tx[e][f] = CodeWord[tx_pos[e]][f]
+ *   recover:  Channel_Out[n][f] = the 32 bits of rx[e_0][f], then + rx[e_1][f], then + rx[e_2][f], ...: fp32 additions in ascending
+ *             e, not contracted, not reordered.  With one contribution this is the copy of a linear profile (-0.0f and NaN payloads
+ *             survive); the sum does not start from zero, so -0.0f sent twice gives -0.0f.
+ *                               = 0x00000000   no contribution: n punctured or not reached
+ *                               = short_llr    n shortened
+ *   combine:  Channel_Acc[n][f] (read and written), for every frame with done[f] == 0 (done == NULL: every frame):
+ *                               = ((acc + rx[e_0][f]) + rx[e_1][f]) + ...    starting from the stored value
+ *                               unchanged      no contribution
+ *                               = short_llr    n shortened
+ *             A frame with done[f] != 0 is not touched at all: its column keeps its bits.  done may be row N of a decoder's D after
+ *             bldpc_syndrome (or a decoder with BLDPC_STOP_SYNDROME) wrote the flag there.
+ *             The first transmission of a codeword is recover, every later one is combine.  The same profile twice is Chase
+ *             combining, profiles of different k0 are incremental redundancy.  rx may come from any source: with bldpc_qam_demap
+ *             run at N := E on the selected bits, combine is HARQ over QAM.
+ *   channel:  bldpc_rm_awgn_channel_device / _host on a circular profile: sample (f, e) uses draws 2(f*E + e) and 2(f*E + e) + 1 in the
+ *             arithmetic of bldpc_awgn_channel_device / _host, seed[3] advances by 2*E*F draws, the output is recover of those samples.
+ *   channel + combine:  the same samples combined into Channel_Acc under done, ONE kernel, no [E][F] intermediate.  The draws of a done
+ *             frame are skipped, not handed to another frame, and seed[3] advances by 2*E*F whatever done holds: a frame's noise
+ *             depends neither on its batch mates nor on the world size.
+ *
+ * bldpc_rm_create_circular refuses (BLDPC_EINVAL) everything bldpc_rm_create refuses, k0 outside [0, Ncb), E < 1, E > 8 * Ncb (the
+ * fused kernel keeps one generator state per lap of the buffer in registers, eight at most) and E > 2 097 120 (the launch grid of a
+ * kernel that walks E rows).  bldpc_rm_dims reports this E, bldpc_rm_tx_pos the E entries in transmission order, and the rate
+ * (K - n_short) / E is that of this one transmission.  No device table is added: the profile's one table still holds the rank b.
+ * A profile from bldpc_rm_create is the circular profile k0 = 0, E = Ncb.  In the entry points it had before (select, recover, channel)
+ * it runs the kernels it ran before; bldpc_rm_combine and bldpc_rm_awgn_combine_device take both kinds.
+ *
+ *   rx           device float [E][F]            done         device int32 [F] or NULL
+ *   Channel_Acc  device float [N][F]            CodeWord     device int32 [N][F] or NULL = the all-zero word
+ * Asynchronous on `stream`, nothing allocated per call; checks of short_llr, seed and F as in "rate matching". */
+int bldpc_rm_create_circular(int N, const int *short_pos, int n_short, const int *punct_pos, int n_punct, int k0, int E, bldpc_rm **rm);
+int bldpc_rm_circ(const bldpc_rm *rm, int info[4]); /* Ncb, k0, E, laps = ceil(E / Ncb); a linear profile: Ncb, 0, Ncb, 1 */
+int bldpc_rm_combine(const bldpc_rm *rm, const float *rx, int F, float short_llr, const int *done, float *Channel_Acc, void *stream);
+int bldpc_rm_awgn_combine_device(const bldpc_rm *rm, int seed[3], float sigma, const int *CodeWord, int F, float short_llr, const int *done,
+                                 float *Channel_Acc, void *stream);
+/* Host statements (all pointers host, no device needed): plain C++ that follows the words above literally; channel + combine IS
+ * select, bldpc_awgn_channel_host with N := E, combine.  bldpc_rm_select_host, bldpc_rm_recover_host and bldpc_rm_awgn_channel_host
+ * take a circular profile as their device twins do. */
+int bldpc_rm_combine_host(const bldpc_rm *rm, const float *rx, int F, float short_llr, const int *done, float *Channel_Acc);
+int bldpc_rm_awgn_combine_host(const bldpc_rm *rm, int seed[3], float sigma, const int *CodeWord, int F, float short_llr, const int *done,
+                               float *Channel_Acc);
+
+/* Frame compaction: the columns idx[0] < idx[1] < ... < idx[Fa-1] of an array [rows][F] of 32-bit words of any meaning (a decoder's
+ * float input, its int32 D with rows = N + 1, iters with rows = 1):
+ *   gather:   dst[r][a] = src[r][idx[a]]      src [rows][F],  dst [rows][Fa]
+ *   scatter:  dst[r][idx[a]] = src[r][a]      src [rows][Fa], dst [rows][F]; the other columns of dst are not touched
+ * idx is device int32 [Fa], strictly ascending in [0, F): a precondition of the device calls (an index outside [0, F) moves nothing, a
+ * repeated one makes scatter's result undefined), checked by the host twins (BLDPC_EINVAL).  The per-frame results of BLDPC_EXIT_FIXED
+ * and BLDPC_EXIT_PER_FRAME do not depend on a frame's batch mates, so decoding the gathered unacknowledged frames and scattering D and
+ * iters back gives the bits of decoding every frame again.  BLDPC_EINVAL: a null pointer, Fa < 1, Fa > F, rows < 1 or > 2 097 120.
+ * The list comes from the caller (in Python: torch.nonzero on the flag row). */
+int bldpc_frames_gather(const void *src, int rows, int F, const int *idx, int Fa, void *dst, void *stream);
+int bldpc_frames_scatter(const void *src, int rows, int F, const int *idx, int Fa, void *dst, void *stream);
+int bldpc_frames_gather_host(const void *src, int rows, int F, const int *idx, int Fa, void *dst);
+int bldpc_frames_scatter_host(const void *src, int rows, int F, const int *idx, int Fa, void *dst);
 
 /* sigma of the sweep point (main.cu:120-127): snrtype 0 = Eb/N0 (uses rate), 1 = Es/N0. */
 float bldpc_sigma(float SNR, int snrtype, float rate);

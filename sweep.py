@@ -3,10 +3,12 @@
 
     python sweep.py binary --matrix data/bldpc/J4_L24_Z96_BlockH.txt --J 4 --L 24 --Z 96 --start 0 --stop 4.4 --step 0.2
     python sweep.py nb     --start 0 --stop 5 --step 0.5
+    python sweep.py binary --device-channel --layered --per-frame --pn-message --harq 0:2160,2160:144,500:2400 --start 2 --stop 3 --step 0.5
     python -m torch.distributed.run --nproc-per-node N sweep.py binary ...      (frames sharded over N GPUs)
 
 binary: rows `SNR NTF NEF FER BER AverIT FER_F FER_A` as Simulation.cu:272 prints them (Es/N0, seeds 173/173/173,
 batches of --batch frames, stop at >= 50 error frames and >= 10000 frames, or --max-batches).
+        with --harq: rows `SNR NTF FER-after-each-transmission mean-transmissions throughput AverIT` (Simulation_HARQ_GPU).
 nb:     rows `SNR NTF NEF FER BER AverIT` as Simulation.cpp:198 (Eb/N0, stop at >= 50 error frames and >= 1000 frames).
 """
 import argparse
@@ -31,6 +33,17 @@ def parse_positions(spec, N=None):
             raise ValueError("range %s ends past N=%d" % (part.strip(), N))
         pos.update(range(int(a), int(b)))
     return sorted(pos)
+
+
+def parse_harq(spec):
+    """SPEC of --harq: comma-separated K0:E, one per transmission -> [(k0, E), ...]."""
+    out = []
+    for part in spec.split(","):
+        a, sep, b = part.strip().partition(":")
+        if not sep or not a.strip().isdigit() or not b.strip().isdigit() or int(b) < 1:
+            raise ValueError("%r is not K0:E with a buffer start K0 >= 0 and a length E >= 1" % part)
+        out.append((int(a), int(b)))
+    return out
 
 
 def main():
@@ -66,7 +79,22 @@ def main():
                     "ranges a:b (information positions; needs --device-channel)")
     ap.add_argument("--puncture", metavar="SPEC", default=None, help="binary: codeword positions not sent, same SPEC (needs --device-channel)")
     ap.add_argument("--short-llr", type=float, default=1.0e4, help="--shorten: the decoder's input on a shortened position")
+    ap.add_argument("--harq", metavar="K0:E[,K0:E...]", default=None, help="binary: incremental-redundancy HARQ over BPSK, one circular-buffer "
+                    "transmission per K0:E (start in the buffer of the positions left by --shorten / --puncture, length; E above the buffer "
+                    "repeats); only unacknowledged frames are sent and decoded again; --snrtype applies, sigma under Eb/N0 from the FIRST "
+                    "transmission's rate (needs --device-channel and --fixed or --per-frame)")
+    ap.add_argument("--snrtype", type=int, default=None, choices=[0, 1], help="--harq: 0 = Eb/N0 on the first transmission's rate, 1 = Es/N0 (default)")
+    ap.add_argument("--no-compact", action="store_true", help="--harq: decode the whole batch after every transmission (timing and checking)")
     args = ap.parse_args()
+    if args.harq is not None:
+        if args.which != "binary" or not args.device_channel or args.qam != 2 or args.as_written or not (args.fixed or args.per_frame):
+            ap.error("--harq belongs to the binary sweep over BPSK with --device-channel and --fixed or --per-frame")
+        try:
+            harq = parse_harq(args.harq)
+        except ValueError as e:
+            ap.error(str(e))
+    elif args.snrtype is not None or args.no_compact:
+        ap.error("--snrtype and --no-compact belong to --harq")
     if args.which == "binary" and args.layered:
         if args.as_written or not (args.fixed or args.per_frame):
             ap.error("--layered needs a QC code and --fixed or --per-frame")
@@ -81,7 +109,7 @@ def main():
     if args.which == "binary" and args.qam != 2 and not (args.pn_message and args.device_channel):
         ap.error("binary --qam %d needs --pn-message (a QAM channel is not symmetric: the all-zero word is not representative) and "
                  "--device-channel (there is no host QAM channel on this path)" % args.qam)
-    ratematch = args.shorten is not None or args.puncture is not None
+    ratematch = args.shorten is not None or args.puncture is not None or args.harq is not None
     if ratematch:
         if args.which != "binary" or not args.device_channel:
             ap.error("--shorten / --puncture belong to the binary sweep with --device-channel")
@@ -129,6 +157,24 @@ def main():
         mod = {}
         if args.qam != 2:  # the GF(q) half's constellation file and sigma (Eb/N0, n_QAM in the formula): the two sweeps share both
             mod = dict(n_QAM=args.qam, CONSTELLATION=C.Get_CONSTELLATION(os.path.join(nbd, "Constellation", "GRAY_%dQAM.txt" % args.qam), args.qam))
+        if args.harq is not None:
+            from cuda_ldpc_amd.simulation import sweep_harq
+            rvs = [C.RateMatch.circular(code.N, shorten, puncture, k0, E) for k0, E in harq]
+            if rank == 0:
+                print("# %s N=%d K=%d, HARQ over BPSK: buffer Ncb=%d (%d shortened, %d punctured), transmissions K0:E %s, first rate %.4f, %s, %s, "
+                      "maxIT=%d, batch=%d x %d GPU(s)%s" % (os.path.basename(args.matrix), code.N, code.K, rvs[0].Ncb, rvs[0].n_short, rvs[0].n_punct,
+                                                          args.harq, rvs[0].rate(code.K), "layered alpha=%g" % args.alpha if args.layered else
+                                                          "flooding alpha=%g" % args.alpha, "fixed iterations" if args.fixed else "per-frame early exit",
+                                                          args.iters or (25 if args.layered else 50), args.batch, world,
+                                                          ", random codewords (PN seed %d)" % args.pn_seed if args.pn_message else ""))
+                print("# SNR      NTF  FER after each transmission ...  mean transmissions  throughput (information bits per bit sent)  AverIT")
+            sweep_harq(code, rvs, args.start, args.stop, args.step, snrtype=1 if args.snrtype is None else args.snrtype, dist=dist,
+                       Num_Frames_OneTime=args.batch, maxIT=args.iters or (25 if args.layered else 50),
+                       exit_mode=C.EXIT_FIXED if args.fixed else C.EXIT_PER_FRAME, max_batches=args.max_batches, PN_Message=1 if args.pn_message else 0,
+                       pn_seed=args.pn_seed, log=print if rank == 0 else None, short_llr=args.short_llr, compact=not args.no_compact, **lay)
+            if world > 1:
+                dist.destroy_process_group()
+            return
         if ratematch:
             rm = C.RateMatch(code.N, shorten, puncture)
             mod.update(rate_match=rm, short_llr=args.short_llr)
