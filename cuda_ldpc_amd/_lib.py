@@ -55,6 +55,10 @@ lib.bldpc_syndrome.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_
 lib.bldpc_decode_layered.argtypes = [c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
 lib.bldpc_decode_layered_host.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_int, c_int, c_int, c_void_p,
                                           c_void_p, c_void_p]
+lib.bldpc_decode_layered_bp.argtypes = [c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
+lib.bldpc_decode_layered_bp_host.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_int, c_int, c_int, c_void_p,
+                                             c_void_p, c_void_p]
+lib.bldpc_bp_table.argtypes = [c_void_p]
 lib.bldpc_decode_normalised.argtypes = [c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
 lib.bldpc_decode_normalised_host.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_int, c_int, c_void_p, c_void_p,
                                              c_void_p]

@@ -436,6 +436,59 @@ def layered_host(H, J, L, Z, y, max_iter=25, alpha=1.0, length=0, exit_mode=EXIT
     return dict(D=D, app=app, iters=iters)
 
 
+def LDPC_Decoder_BP_GPU(code, Channel_Out, max_iter=25, llr_scale=1.0, length=0, exit_mode=EXIT_FIXED, stop_rule=STOP_PREFIX, D=None,
+                        want_app=False, stream=None):
+    """bldpc_decode_layered_bp: row-layered sum-product (box-plus with a 128-entry correction table; semantics in include/bldpc.h),
+    codes made from block shifts only.
+
+    Channel_Out: CUDA float32 tensor [N, F] (frame-fastest).  llr_scale turns it into true LLRs: 2 / sigma^2 for the BPSK channels,
+    1.0 after Demodulate_QAM with scale 1 / (2 sigma^2).  stop_rule, exit_mode, length and D as in LDPC_Decoder_Layered_GPU.
+    Returns dict(D=int32 [N+1, F], app=float32 [N, F] or None, iters=int32 [F]: iterations run by each frame)."""
+    if not (torch.is_tensor(Channel_Out) and Channel_Out.is_cuda and Channel_Out.dtype == torch.float32 and Channel_Out.is_contiguous()):
+        raise ValueError("Channel_Out must be a contiguous CUDA float32 tensor")
+    if Channel_Out.dim() != 2 or Channel_Out.shape[0] != code.N or Channel_Out.shape[1] <= 0:
+        raise ValueError("Channel_Out must be [N=%d, F]" % code.N)
+    F = int(Channel_Out.shape[1])
+    dev = Channel_Out.device
+    if D is None:
+        D = torch.empty((code.N + 1, F), dtype=torch.int32, device=dev)
+    else:
+        _check_D(D, code.N, F, dev)
+    app = torch.empty((code.N, F), dtype=torch.float32, device=dev) if want_app else None
+    iters = torch.empty(F, dtype=torch.int32, device=dev)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(dev)).cuda_stream)
+    check(lib.bldpc_decode_layered_bp(code._h, _dev_ptr(Channel_Out), F, int(max_iter), ctypes.c_float(llr_scale), int(length), int(exit_mode),
+                                      int(stop_rule), _dev_ptr(D), _dev_ptr(app), _dev_ptr(iters), st), "LDPC_Decoder_BP_GPU")
+    return dict(D=D, app=app, iters=iters)
+
+
+def bp_host(H, J, L, Z, y, max_iter=25, llr_scale=1.0, length=0, exit_mode=EXIT_FIXED, stop_rule=STOP_PREFIX, want_app=True):
+    """bldpc_decode_layered_bp_host: the sum-product decoder on the host (no device), the statement of its semantics.  y: float32
+    [N, F] host array (frame-fastest).  Returns dict(D=int32 [N+1, F], app=float32 [N, F] or None, iters=int32 [F])."""
+    H = np.ascontiguousarray(H, np.int32)
+    if H.size != J * L:
+        raise ValueError("H must hold J*L shifts")
+    y = np.ascontiguousarray(y, np.float32)
+    N = L * Z
+    if y.ndim != 2 or y.shape[0] != N or y.shape[1] <= 0:
+        raise ValueError("y must be [N=%d, F]" % N)
+    F = y.shape[1]
+    D = np.zeros((N + 1, F), np.int32)
+    app = np.zeros((N, F), np.float32) if want_app else None
+    iters = np.zeros(F, np.int32)
+    check(lib.bldpc_decode_layered_bp_host(J, L, Z, _np_ptr(H), _np_ptr(y), F, int(max_iter), ctypes.c_float(llr_scale), int(length),
+                                           int(exit_mode), int(stop_rule), _np_ptr(D), None if app is None else _np_ptr(app), _np_ptr(iters)),
+          "bp_host")
+    return dict(D=D, app=app, iters=iters)
+
+
+def BP_Table():
+    """bldpc_bp_table: the sum-product decoders' correction table, float32 [128]: T[k] = log1p(exp(-(k + 0.5) / 16)) to the nearest fp32."""
+    T = np.zeros(128, np.float32)
+    check(lib.bldpc_bp_table(_np_ptr(T)), "BP_Table")
+    return T
+
+
 def normalised_host(H, J, L, Z, y, max_iter=50, alpha=1.0, length=0, exit_mode=EXIT_FIXED, want_app=True):
     """bldpc_decode_normalised_host: the flooding decoder with normalised min-sum on the host (no device), the statement of its
     semantics.  y: float32 [N, F] host array (frame-fastest).  Returns dict(D=int32 [N+1, F], app=float32 [N, F] or None,

@@ -12,6 +12,7 @@
 #include <new>
 #include <vector>
 
+#include "bldpc_bp.hpp"
 #include "bldpc_encode.hpp"
 #include "bldpc_layered.hpp"
 #include "bldpc_norm.hpp"
@@ -42,11 +43,17 @@ struct bldpc_code {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     EncState *enc = nullptr; // systematic encoder and syndrome tables (bldpc_encode.hip), built on first use
     LayPlan *lay = nullptr;  // layered decoder: edge tables and its own scratch (bldpc_layered.hip), built on first use
+    BpPlan *bp = nullptr;    // layered sum-product decoder: the same of its own (bldpc_bp.hip), built on first use
 };
 
 LayView cldpc::lay_view(bldpc_code *c)
 {
     return LayView{c->J, c->L, c->Z, c->N, c->M, c->K, c->has_qc ? c->H.data() : nullptr, &c->lay, &c->last_kernel};
+}
+
+BpView cldpc::bp_view(bldpc_code *c)
+{
+    return BpView{c->J, c->L, c->Z, c->N, c->M, c->K, c->has_qc ? c->H.data() : nullptr, &c->bp, &c->last_kernel};
 }
 
 CodeView cldpc::code_view(const bldpc_code *c)
@@ -228,6 +235,7 @@ extern "C" int bldpc_code_destroy(bldpc_code *c)
     qc_plan_release(&c->qc);
     enc_state_free(c->enc);
     lay_plan_free(c->lay);
+    bp_plan_free(c->bp);
     for (hipEvent_t e : c->evr)
         if (e) (void)hipEventDestroy(e);
     delete c;

@@ -190,6 +190,18 @@ void cldpc::lay_plan_free(LayPlan *p)
     delete p;
 }
 
+void cldpc::lay_launch_transpose(const float *src, float *dst, int R, int C, void *stream)
+{
+    const dim3 grid((unsigned)((C + 63) / 64), (unsigned)((R + 63) / 64));
+    hipLaunchKernelGGL(k_lay_transpose, grid, dim3(256), 0, (hipStream_t)stream, src, dst, R, C);
+}
+
+void cldpc::lay_launch_expand(const unsigned *bits, int *D, int F, int N, void *stream)
+{
+    const int NW = (N + 31) / 32; // the caller keeps NW within the grid's 65535
+    hipLaunchKernelGGL(k_lay_expand, dim3((unsigned)((F + 255) / 256), (unsigned)NW), dim3(256), 0, (hipStream_t)stream, bits, D, F, N);
+}
+
 namespace {
 
 using LayKernel = void (*)(LayArgs);

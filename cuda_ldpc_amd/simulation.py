@@ -15,7 +15,7 @@ from . import sharding
 from ._lib import check, lib
 from .bldpc import (EXIT_BATCH_GLOBAL, EXIT_FIXED, EXIT_PER_FRAME, KERNEL_AUTO, STOP_PREFIX, STOP_SYNDROME, AWGNChannel_CPU, AWGNChannel_GPU,
                     AWGNChannel_QAM_GPU, AWGNChannel_RM_Combine_GPU, AWGNChannel_RM_GPU, Decode_Statistic, Demodulate_QAM, Frames_Gather,
-                    Frames_Scatter, LDPC_Decoder_GPU, LDPC_Decoder_Layered_GPU, Modulate_QAM, PN_CodeWords, RM_Recover, RM_Select, SimCounters,
+                    Frames_Scatter, LDPC_Decoder_BP_GPU, LDPC_Decoder_GPU, LDPC_Decoder_Layered_GPU, Modulate_QAM, PN_CodeWords, RM_Recover, RM_Select, SimCounters,
                     Syndrome, _dev_ptr, sigma_of)
 from .nbldpc import sigma_of as nb_sigma_of
 
@@ -39,6 +39,11 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
     is not used).  stop_rule defaults to STOP_SYNDROME with PN_Message=1 and to STOP_PREFIX otherwise; with STOP_SYNDROME the flag
     row already means "valid codeword", so random codewords run with EXIT_PER_FRAME and no separate Syndrome call.
 
+    schedule="bp" decodes with LDPC_Decoder_BP_GPU (layered sum-product): everything said of schedule="layered" holds, except that
+    `alpha` is refused (sum-product has no normalisation factor) and that the decoder is given llr_scale = 2 / sigma^2 on the BPSK paths,
+    rate-matched included, which turns y = 1 - 2c + noise into a true LLR, and 1.0 on the QAM paths, whose demapper already scales by
+    1 / (2 sigma^2).
+
     n_QAM != 2 sends the codewords over n_QAM-QAM instead of BPSK: CONSTELLATION (host float32 [n_QAM, 2], Get_CONSTELLATION) labels
     log2(n_QAM) consecutive codeword bits per point; a batch is encode -> Modulate_QAM -> AWGNChannel_QAM_GPU (four draws per symbol
     of the same noise stream) -> Demodulate_QAM with scale 1 / (2 sigma^2) -> the chosen decoder, and the caller passes the sigma of
@@ -53,11 +58,14 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
     device_channel=True."""
     if PN_Message not in (0, 1):
         raise ValueError("PN_Message must be 0 (all-zero codeword) or 1 (random codewords)")
-    if schedule not in ("flooding", "layered"):
-        raise ValueError("schedule must be 'flooding' or 'layered'")
-    layered = schedule == "layered"
+    if schedule not in ("flooding", "layered", "bp"):
+        raise ValueError("schedule must be 'flooding', 'layered' or 'bp'")
+    bp = schedule == "bp"
+    layered = schedule == "layered" or bp  # sum-product shares the layered decoder's modes, rules and outputs
+    if bp and alpha != 1.0:
+        raise ValueError("alpha belongs to the min-sum decoders: schedule='bp' has no normalisation factor")
     if not layered and stop_rule is not None:
-        raise ValueError("stop_rule belongs to schedule='layered'")
+        raise ValueError("stop_rule belongs to schedule='layered' and schedule='bp'")
     norm = not layered and alpha != 1.0  # normalised min-sum on the flooding decoders (LDPC_Decoder_GPU(alpha=...))
     if norm and exit_mode not in (EXIT_FIXED, EXIT_PER_FRAME):
         raise ValueError("schedule='flooding' with alpha takes EXIT_FIXED or EXIT_PER_FRAME")
@@ -67,7 +75,7 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
         if stop_rule not in (STOP_PREFIX, STOP_SYNDROME):
             raise ValueError("stop_rule must be STOP_PREFIX or STOP_SYNDROME")
         if exit_mode not in (EXIT_FIXED, EXIT_PER_FRAME):
-            raise ValueError("schedule='layered' takes EXIT_FIXED or EXIT_PER_FRAME")
+            raise ValueError("schedule='%s' takes EXIT_FIXED or EXIT_PER_FRAME" % schedule)
         if PN_Message == 1 and stop_rule != STOP_SYNDROME and exit_mode != EXIT_FIXED:
             raise ValueError("PN_Message=1 with per-frame exit needs stop_rule=STOP_SYNDROME: STOP_PREFIX tests for the all-zero word")
     elif PN_Message == 1 and exit_mode != EXIT_FIXED:
@@ -111,6 +119,7 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
     dev_cnt = torch.zeros(5, dtype=torch.int64, device=device)
     D = torch.empty((code.N + 1, max(count, 1)), dtype=torch.int32, device=device)
     length = code.K  # Message_CW 0 (define.cuh:61)
+    llr_scale = 1.0 if qam_m else 2.0 / (sigma * sigma)  # schedule="bp": what makes the decoder's input a true LLR
     ber_bits = length - (int((rm.shorten < length).sum()) if rm is not None else 0)  # the prefix bits that carry information
     batches = 0
     while True:
@@ -134,7 +143,10 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
         seed[:] = sharding.lcg_jump(seed, F * per_frame)
         dev_cnt.zero_()
         if count and layered:
-            r = LDPC_Decoder_Layered_GPU(code, yd, max_iter=maxIT, alpha=alpha, length=length, exit_mode=exit_mode, stop_rule=stop_rule, D=D)
+            if bp:
+                r = LDPC_Decoder_BP_GPU(code, yd, max_iter=maxIT, llr_scale=llr_scale, length=length, exit_mode=exit_mode, stop_rule=stop_rule, D=D)
+            else:
+                r = LDPC_Decoder_Layered_GPU(code, yd, max_iter=maxIT, alpha=alpha, length=length, exit_mode=exit_mode, stop_rule=stop_rule, D=D)
             if PN_Message and stop_rule != STOP_SYNDROME:
                 Syndrome(code, D, into_flag_row=True)
             st = torch.cuda.current_stream(device).cuda_stream
@@ -213,7 +225,9 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
     The ACK must hold for the word that was sent.  PN_Message=0 (the all-zero word): the decoder's own flag, flooding (plain, or
     normalised with alpha != 1.0) or layered, EXIT_FIXED or EXIT_PER_FRAME.  PN_Message=1 (random codewords): flooding with EXIT_FIXED
     followed by Syndrome(into_flag_row=True), or layered with STOP_SYNDROME (its default here) and either exit.  EXIT_BATCH_GLOBAL is
-    refused: its results depend on the batch.  A position no transmission has reached yet holds +0.0 and decides 0, so on the all-zero
+    refused: its results depend on the batch.  schedule="bp" (layered sum-product, LDPC_Decoder_BP_GPU) takes what schedule="layered"
+    takes, but no `alpha`, and decodes with llr_scale = 2 / sigma^2: the sum of equal-sigma transmissions of a bit is a true LLR under that
+    factor.  A position no transmission has reached yet holds +0.0 and decides 0, so on the all-zero
     word the flag flatters a first transmission with E < Ncb; random codewords do not have that bias.
 
     Draws: transmission t of a batch owns 2 * E_t * F draws of the noise stream, used or not -- `seed` (int32[3]) is advanced by the
@@ -221,13 +235,16 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
     into each.  One all-reduce of the counters per batch.  keep_D (a list) receives this rank's final D of every batch."""
     if PN_Message not in (0, 1):
         raise ValueError("PN_Message must be 0 (all-zero codeword) or 1 (random codewords)")
-    if schedule not in ("flooding", "layered"):
-        raise ValueError("schedule must be 'flooding' or 'layered'")
-    layered = schedule == "layered"
+    if schedule not in ("flooding", "layered", "bp"):
+        raise ValueError("schedule must be 'flooding', 'layered' or 'bp'")
+    bp = schedule == "bp"
+    layered = schedule == "layered" or bp  # sum-product shares the layered decoder's modes, rules and outputs
+    if bp and alpha != 1.0:
+        raise ValueError("alpha belongs to the min-sum decoders: schedule='bp' has no normalisation factor")
     if exit_mode not in (EXIT_FIXED, EXIT_PER_FRAME):
         raise ValueError("HARQ takes EXIT_FIXED or EXIT_PER_FRAME: the results of EXIT_BATCH_GLOBAL depend on the batch")
     if not layered and stop_rule is not None:
-        raise ValueError("stop_rule belongs to schedule='layered'")
+        raise ValueError("stop_rule belongs to schedule='layered' and schedule='bp'")
     norm = not layered and alpha != 1.0
     if layered:
         if stop_rule is None:
@@ -268,7 +285,11 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
     def decode(y, D):
         """Decode y into D, leave the ACK in row N, return the iterations of every frame (int32 [F'])."""
         if layered:
-            r = LDPC_Decoder_Layered_GPU(code, y, max_iter=maxIT, alpha=alpha, length=K, exit_mode=exit_mode, stop_rule=stop_rule, D=D)
+            if bp:
+                r = LDPC_Decoder_BP_GPU(code, y, max_iter=maxIT, llr_scale=2.0 / (sigma * sigma), length=K, exit_mode=exit_mode, stop_rule=stop_rule,
+                                        D=D)
+            else:
+                r = LDPC_Decoder_Layered_GPU(code, y, max_iter=maxIT, alpha=alpha, length=K, exit_mode=exit_mode, stop_rule=stop_rule, D=D)
             if PN_Message and stop_rule != STOP_SYNDROME:
                 Syndrome(code, D, into_flag_row=True)
             return r["iters"]

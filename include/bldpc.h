@@ -256,6 +256,57 @@ int bldpc_decode_layered(bldpc_code *code, const float *Channel_Out, int F, int 
 int bldpc_decode_layered_host(int J, int L, int Z, const int *H, const float *Channel_Out, int F, int max_iter, float alpha,
                               int length, int exit_mode, int stop_rule, int *D, float *app, int *iters);
 
+/* -- row-layered sum-product (belief propagation; not in the reference, whose check node is min-sum) ---------------- */
+
+/* The schedule of bldpc_decode_layered with the exact check-node rule in place of the two minima, for codes made by
+ * bldpc_code_create_qc.  Semantics, IEEE fp32, no fused multiply-add, no denormal flushing.
+ *
+ * Sum-product needs true LLRs.  The min-sum decoders are scale-invariant and take the raw channel value, so this entry point takes
+ * a factor llr_scale: 2 / sigma^2 for the BPSK channels here, 1.0 after bldpc_qam_demap, which is already given 1 / (2 sigma^2).
+ *
+ *   Correction table.  T[k] is the fp32 nearest to log1p(exp(-(k + 0.5) / 16)), k = 0 .. 127: 128 literals in a header of its own
+ *   (csrc/bldpc_bp_table.hpp), exported by bldpc_bp_table.  It is not computed at run time, so every machine carries the same bits.
+ *     corr(x) for x >= 0:  x < 8.0f ? T[(int)(x * 16.0f)] : +0.0f        (the product is exact and the index is at most 127)
+ *
+ *   Box-plus.  bp(a, b):
+ *     aa = |a|;  ab = |b|;  m = min(aa, ab);  p = aa + ab;  d = |aa - ab|
+ *     r = (m + corr(p)) - corr(d), in exactly that order;  r = (r < 0) ? +0.0f : r
+ *     the result has the bits of r, with the sign bit set to signbit(a) xor signbit(b); a -0.0f input counts as negative.
+ *   The sum and difference are taken on the magnitudes, not on a +- b (with a +- b the correction has the wrong sign when the signs
+ *   differ).
+ *
+ *   Decoder.  State per frame: S[v] = llr_scale * Channel_Out[v] (one fp32 product per value), R = +0.0f per edge.
+ *   One iteration visits the block rows j = 0 .. J-1 in order; within a block row every t in 0 .. Z-1 is independent of the others;
+ *   the edges i = 0 .. w-1 run in ascending block column, with v_i as in bldpc_decode_layered.  Per row:
+ *     1. Q_i = S[v_i] - R_i
+ *     2. F_0 = Q_0;  F_i = bp(F_{i-1}, Q_i) for i = 1 .. w-2
+ *     3. B_{w-1} = Q_{w-1};  B_i = bp(Q_i, B_{i+1}) for i = w-2 .. 1
+ *     4. R_0' = B_1;  R_{w-1}' = F_{w-2};  otherwise R_i' = bp(F_{i-1}, B_{i+1})
+ *     5. S[v_i] = Q_i + R_i';  R_i' replaces R_i
+ *   For w = 2 this gives R_0' = Q_1 and R_1' = Q_0 with no box-plus at all.
+ *
+ * Hard bits, flag, length, stop_rule (BLDPC_STOP_PREFIX or BLDPC_STOP_SYNDROME), exit_mode (BLDPC_EXIT_FIXED or
+ * BLDPC_EXIT_PER_FRAME; BLDPC_EXIT_BATCH_GLOBAL refused), D, app (= S), iters and asynchrony are exactly those of
+ * bldpc_decode_layered.
+ * Refused with BLDPC_EINVAL: llr_scale not finite or <= 0, max_iter < 1, length outside [0, N], an unknown rule or mode,
+ * iters == NULL with per-frame exit.  Refused with BLDPC_EUNSUPPORTED, with a message in bldpc_last_error: codes built from an
+ * address table, block rows of weight < 2.  Inputs with |llr_scale * y| > 2^100, infinities and NaN are undefined.
+ * No allocation per call once the code object's scratch has grown (scratch and workspace of its own, apart from the other
+ * decoders').  bldpc_last_kernel names the tier that ran: "k_lbp" (all iterations on-chip: S and R of one or more frames in LDS,
+ * 4 N + 4 E bytes per frame, E = edges; codes whose N is a multiple of 64, Z <= 1024 and of which one frame fits) or "k_lbp_ws"
+ * (one workgroup per frame, S in place, R in a device workspace kept in the code object: every other code). */
+int bldpc_decode_layered_bp(bldpc_code *code, const float *Channel_Out, int F, int max_iter, float llr_scale, int length,
+                            int exit_mode, int stop_rule, int *D, float *app, int *iters, void *stream);
+
+/* The same decoder on the host, all pointers host, no device needed: plain C++ that follows the steps above literally (one R per
+ * edge), frames over at most 16 threads, no weight limit.  It is the statement of the semantics inside the product and what the
+ * device kernels are tested against bit for bit.  NOT a fast path. */
+int bldpc_decode_layered_bp_host(int J, int L, int Z, const int *H, const float *Channel_Out, int F, int max_iter, float llr_scale,
+                                 int length, int exit_mode, int stop_rule, int *D, float *app, int *iters);
+
+/* The correction table T[0 .. 127] of the two calls above (host pointer). */
+int bldpc_bp_table(float T[128]);
+
 /* -- normalised min-sum on the flooding decoders (not in the reference, whose flooding min-sum is un-normalised) ----- */
 
 /* The flooding iteration exactly as bldpc_decode runs it, with one change in the check-node update.  Semantics, IEEE fp32
@@ -490,7 +541,7 @@ int bldpc_last_kernel_ms(bldpc_code *code, float *ms);
  * profiled call records its own event pair, nothing synchronises until this function is called.  *launches = calls averaged. */
 int bldpc_kernel_ms_mean(bldpc_code *code, float *mean_ms, int *launches);
 
-/* Name of the kernel variant the last bldpc_decode / bldpc_decode_layered on this code used (static string). */
+/* Name of the kernel variant the last bldpc_decode / bldpc_decode_layered / bldpc_decode_layered_bp on this code used (static string). */
 const char *bldpc_last_kernel(const bldpc_code *code);
 
 /* -- the table of fused (QC_LDS) kernel variants, read-only ---------------------------------------------------------- */

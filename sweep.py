@@ -4,6 +4,7 @@
     python sweep.py binary --matrix data/bldpc/J4_L24_Z96_BlockH.txt --J 4 --L 24 --Z 96 --start 0 --stop 4.4 --step 0.2
     python sweep.py nb     --start 0 --stop 5 --step 0.5
     python sweep.py binary --device-channel --layered --per-frame --pn-message --harq 0:2160,2160:144,500:2400 --start 2 --stop 3 --step 0.5
+    python sweep.py binary --device-channel --bp --per-frame --stop-rule syndrome --pn-message --start 2 --stop 3 --step 0.2
     python -m torch.distributed.run --nproc-per-node N sweep.py binary ...      (frames sharded over N GPUs)
 
 binary: rows `SNR NTF NEF FER BER AverIT FER_F FER_A` as Simulation.cu:272 prints them (Es/N0, seeds 173/173/173,
@@ -70,10 +71,12 @@ def main():
     ap.add_argument("--pn-message", action="store_true", help="send random codewords (PN_Message 1, define.cuh:26); binary: needs --fixed")
     ap.add_argument("--pn-seed", type=int, default=1, help="--pn-message: seed of the message stream (bldpc_encode_random / nbldpc_encode_random)")
     ap.add_argument("--layered", action="store_true", help="binary: row-layered normalised min-sum (bldpc_decode_layered); with --fixed or --per-frame")
+    ap.add_argument("--bp", action="store_true", help="binary: row-layered sum-product (bldpc_decode_layered_bp, llr_scale = 2 / sigma^2 over BPSK, "
+                    "1 over QAM); with --fixed or --per-frame, takes --stop-rule and every channel option, no --alpha")
     ap.add_argument("--alpha", type=float, default=1.0, help="binary: normalisation factor in (0, 1]; with --layered the layered decoder's, without it "
                     "normalised min-sum on the flooding decoders (with --fixed or --per-frame)")
     ap.add_argument("--stop-rule", choices=["prefix", "syndrome"], default=None,
-                    help="--layered: stop rule / meaning of the flag row (default: syndrome with --pn-message, else prefix)")
+                    help="--layered / --bp: stop rule / meaning of the flag row (default: syndrome with --pn-message, else prefix)")
     ap.add_argument("--as-written", action="store_true", help="decode on the reference's Transform_H table as written (SURVEY F3)")
     ap.add_argument("--shorten", metavar="SPEC", default=None, help="binary: codeword positions fixed to 0 and not sent, comma-separated half-open "
                     "ranges a:b (information positions; needs --device-channel)")
@@ -95,16 +98,19 @@ def main():
             ap.error(str(e))
     elif args.snrtype is not None or args.no_compact:
         ap.error("--snrtype and --no-compact belong to --harq")
-    if args.which == "binary" and args.layered:
+    if args.bp and (args.which != "binary" or args.layered or args.alpha != 1.0):
+        ap.error("--bp belongs to the binary sweep, without --layered and without --alpha (sum-product has no normalisation factor)")
+    rows = args.layered or args.bp  # the two row-layered decoders take the same modes and rules
+    if args.which == "binary" and rows:
         if args.as_written or not (args.fixed or args.per_frame):
-            ap.error("--layered needs a QC code and --fixed or --per-frame")
+            ap.error("--layered / --bp need a QC code and --fixed or --per-frame")
         if args.pn_message and args.per_frame and args.stop_rule == "prefix":
             ap.error("--pn-message --per-frame needs --stop-rule syndrome (the prefix rule tests for the all-zero word)")
     elif args.stop_rule is not None or (args.alpha != 1.0 and args.which != "binary"):
-        ap.error("--stop-rule belongs to the binary sweep with --layered, --alpha to the binary sweep")
+        ap.error("--stop-rule belongs to the binary sweep with --layered or --bp, --alpha to the binary sweep")
     elif args.alpha != 1.0 and not (args.fixed or args.per_frame):
         ap.error("--alpha without --layered (normalised flooding min-sum) needs --fixed or --per-frame")
-    if args.which == "binary" and not args.layered and args.pn_message and (not args.fixed or args.as_written):
+    if args.which == "binary" and not rows and args.pn_message and (not args.fixed or args.as_written):
         ap.error("--pn-message needs the binary sweep with --fixed (the decoders' early exit tests for the all-zero word) on a QC code")
     if args.which == "binary" and args.qam != 2 and not (args.pn_message and args.device_channel):
         ap.error("binary --qam %d needs --pn-message (a QAM channel is not symmetric: the all-zero word is not representative) and "
@@ -151,9 +157,11 @@ def main():
         lay = {}
         if not args.layered and args.alpha != 1.0:
             lay = dict(alpha=args.alpha)
-        if args.layered:
+        if rows:
             stop = args.stop_rule or ("syndrome" if args.pn_message else "prefix")
             lay = dict(schedule="layered", alpha=args.alpha, stop_rule=C.STOP_SYNDROME if stop == "syndrome" else C.STOP_PREFIX)
+            if args.bp:
+                lay = dict(schedule="bp", stop_rule=lay["stop_rule"])
         mod = {}
         if args.qam != 2:  # the GF(q) half's constellation file and sigma (Eb/N0, n_QAM in the formula): the two sweeps share both
             mod = dict(n_QAM=args.qam, CONSTELLATION=C.Get_CONSTELLATION(os.path.join(nbd, "Constellation", "GRAY_%dQAM.txt" % args.qam), args.qam))
@@ -163,13 +171,14 @@ def main():
             if rank == 0:
                 print("# %s N=%d K=%d, HARQ over BPSK: buffer Ncb=%d (%d shortened, %d punctured), transmissions K0:E %s, first rate %.4f, %s, %s, "
                       "maxIT=%d, batch=%d x %d GPU(s)%s" % (os.path.basename(args.matrix), code.N, code.K, rvs[0].Ncb, rvs[0].n_short, rvs[0].n_punct,
-                                                          args.harq, rvs[0].rate(code.K), "layered alpha=%g" % args.alpha if args.layered else
+                                                          args.harq, rvs[0].rate(code.K), "layered sum-product" if args.bp else
+                                                          "layered alpha=%g" % args.alpha if args.layered else
                                                           "flooding alpha=%g" % args.alpha, "fixed iterations" if args.fixed else "per-frame early exit",
-                                                          args.iters or (25 if args.layered else 50), args.batch, world,
+                                                          args.iters or (25 if rows else 50), args.batch, world,
                                                           ", random codewords (PN seed %d)" % args.pn_seed if args.pn_message else ""))
                 print("# SNR      NTF  FER after each transmission ...  mean transmissions  throughput (information bits per bit sent)  AverIT")
             sweep_harq(code, rvs, args.start, args.stop, args.step, snrtype=1 if args.snrtype is None else args.snrtype, dist=dist,
-                       Num_Frames_OneTime=args.batch, maxIT=args.iters or (25 if args.layered else 50),
+                       Num_Frames_OneTime=args.batch, maxIT=args.iters or (25 if rows else 50),
                        exit_mode=C.EXIT_FIXED if args.fixed else C.EXIT_PER_FRAME, max_batches=args.max_batches, PN_Message=1 if args.pn_message else 0,
                        pn_seed=args.pn_seed, log=print if rank == 0 else None, short_llr=args.short_llr, compact=not args.no_compact, **lay)
             if world > 1:
@@ -184,13 +193,14 @@ def main():
         if rank == 0:
             print("# %s N=%d K=%d, %s%s%s, maxIT=%d, batch=%d x %d GPU(s)%s" % (os.path.basename(args.matrix), code.N, code.K,
                   "" if args.qam == 2 else "%d-QAM (Gray) %d bits per point, max-log demapper, Eb/N0, " % (args.qam, args.qam.bit_length() - 1),
+                  "layered sum-product llr_scale=%s stop=%s, " % ("2/sigma^2" if args.qam == 2 else "1", stop) if args.bp else
                   "layered min-sum alpha=%g stop=%s, " % (args.alpha, stop) if args.layered else
                   ("normalised flooding min-sum alpha=%g, " % args.alpha if args.alpha != 1.0 else ""),
                   "fixed iterations" if args.fixed else ("per-frame early exit" if args.per_frame else "batch-global early exit"),
-                  args.iters or (25 if args.layered else 50), args.batch, world,
+                  args.iters or (25 if rows else 50), args.batch, world,
                   ", random codewords (PN seed %d, K'=%d), syndrome flag" % (args.pn_seed, code.K_info) if args.pn_message else ""))
             print("# SNR      NTF   NEF         FER         BER  AverIT       FER_F      FER_A")
-        sweep(code, args.start, args.stop, args.step, snrtype=1 if args.qam == 2 else 0, dist=dist, Num_Frames_OneTime=args.batch, maxIT=args.iters or (25 if args.layered else 50),
+        sweep(code, args.start, args.stop, args.step, snrtype=1 if args.qam == 2 else 0, dist=dist, Num_Frames_OneTime=args.batch, maxIT=args.iters or (25 if rows else 50),
               exit_mode=C.EXIT_FIXED if args.fixed else (C.EXIT_PER_FRAME if args.per_frame else C.EXIT_BATCH_GLOBAL), max_batches=args.max_batches, displayStep=10 ** 12, device_channel=args.device_channel,
               PN_Message=1 if args.pn_message else 0, pn_seed=args.pn_seed, log=print if rank == 0 else None, **lay, **mod)
     else:
