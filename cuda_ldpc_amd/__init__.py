@@ -9,7 +9,7 @@ the built extension raises.
 from . import _lib  # noqa: F401
 from .bldpc import (BinaryCode, Get_H, Transform_H, LDPC_Decoder_GPU, Decode_Statistic, Statistic, SimCounters, AWGNChannel_CPU, AWGNChannel_GPU, sigma_of,  # noqa: F401
                     Encode, PN_CodeWords, Syndrome, generator_host, pn_messages, LDPC_Decoder_Layered_GPU, layered_host, normalised_host,
-                    LDPC_Decoder_BP_GPU, bp_host, BP_Table,
+                    LDPC_Decoder_BP_GPU, bp_host, BP_Table, Quant, LDPC_Decoder_Quant_GPU, quant_host,
                     Modulate_QAM, AWGNChannel_QAM_GPU, Demodulate_QAM, Modulate_QAM_host, Demodulate_QAM_host, Get_CONSTELLATION, qc_variants, qc_plan_host,
                     RateMatch, RM_Select, RM_Recover, AWGNChannel_RM_GPU, RM_Select_host, RM_Recover_host, AWGNChannel_RM_CPU,
                     RM_Combine, AWGNChannel_RM_Combine_GPU, Frames_Gather, Frames_Scatter, RM_Combine_host, AWGNChannel_RM_Combine_CPU,
@@ -18,7 +18,7 @@ from .bldpc import (BinaryCode, Get_H, Transform_H, LDPC_Decoder_GPU, Decode_Sta
 
 __all__ = ["BinaryCode", "Get_H", "Transform_H", "LDPC_Decoder_GPU", "Decode_Statistic", "Statistic", "SimCounters", "AWGNChannel_CPU", "AWGNChannel_GPU", "sigma_of",
            "Encode", "PN_CodeWords", "Syndrome", "generator_host", "pn_messages", "LDPC_Decoder_Layered_GPU", "layered_host", "normalised_host",
-           "LDPC_Decoder_BP_GPU", "bp_host", "BP_Table",
+           "LDPC_Decoder_BP_GPU", "bp_host", "BP_Table", "Quant", "LDPC_Decoder_Quant_GPU", "quant_host",
            "Modulate_QAM", "AWGNChannel_QAM_GPU", "Demodulate_QAM", "Modulate_QAM_host", "Demodulate_QAM_host", "Get_CONSTELLATION", "qc_variants", "qc_plan_host",
            "RateMatch", "RM_Select", "RM_Recover", "AWGNChannel_RM_GPU", "RM_Select_host", "RM_Recover_host", "AWGNChannel_RM_CPU",
            "RM_Combine", "AWGNChannel_RM_Combine_GPU", "Frames_Gather", "Frames_Scatter", "RM_Combine_host", "AWGNChannel_RM_Combine_CPU",

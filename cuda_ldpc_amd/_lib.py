@@ -59,6 +59,17 @@ lib.bldpc_decode_layered_bp.argtypes = [c_void_p, c_void_p, c_int, c_int, ctypes
 lib.bldpc_decode_layered_bp_host.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_int, c_int, c_int, c_void_p,
                                              c_void_p, c_void_p]
 lib.bldpc_bp_table.argtypes = [c_void_p]
+
+
+class bldpc_quant(ctypes.Structure):
+    """struct bldpc_quant of include/bldpc.h, unchecked: cuda_ldpc_amd.Quant is the checked one."""
+    _fields_ = [("llr_scale", ctypes.c_float), ("bits_ch", c_int), ("bits_app", c_int), ("bits_msg", c_int), ("norm8", c_int), ("offset", c_int)]
+
+
+lib.bldpc_decode_layered_quant.argtypes = [c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(bldpc_quant), c_int, c_int, c_int, c_void_p, c_void_p,
+                                           c_void_p, c_void_p]
+lib.bldpc_decode_layered_quant_host.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(bldpc_quant), c_int, c_int, c_int,
+                                                c_void_p, c_void_p, c_void_p]
 lib.bldpc_decode_normalised.argtypes = [c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
 lib.bldpc_decode_normalised_host.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_int, c_int, c_void_p, c_void_p,
                                              c_void_p]

@@ -12,7 +12,7 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
-from ._lib import LdpcError, check, lib
+from ._lib import LdpcError, bldpc_quant, check, lib
 from .nbldpc import Get_CONSTELLATION  # noqa: F401  -- the constellation files serve both code families
 
 EXIT_FIXED, EXIT_BATCH_GLOBAL, EXIT_PER_FRAME = 0, 1, 2
@@ -487,6 +487,118 @@ def BP_Table():
     T = np.zeros(128, np.float32)
     check(lib.bldpc_bp_table(_np_ptr(T)), "BP_Table")
     return T
+
+
+class Quant:
+    """The word lengths of the quantised layered min-sum decoder (struct bldpc_quant, include/bldpc.h), checked as the C side checks
+    them (ValueError).
+
+    bits_ch   2 .. bits_app   channel word, saturates at +-C, C = 2^(bits_ch-1) - 1
+    bits_app  bits_msg .. 15  a-posteriori word, saturates at +-A, A = 2^(bits_app-1) - 1
+    bits_msg  2 .. 8          check-message word, magnitudes saturate at Mx = 2^(bits_msg-1) - 1
+    norm8     1 .. 8          normalisation in eighths, rounded: g(m) = max(0, ((m * norm8 + 4) >> 3) - offset); 8 = none
+    offset    0 .. Mx         offset subtracted after the normalisation
+    llr_scale finite, > 0     quantiser gain: a channel value y becomes rint(llr_scale * y), ties to even
+
+    llr_scale is an absolute gain on the channel value.  Min-sum is scale-invariant, so it only sets the resolution: y = 1.0 (a
+    noiseless BPSK symbol) becomes the integer llr_scale.  The smallest of the ~20 magnitudes of a rate-5/6 row is often a few
+    units, so a scale below about 16 costs error rate on those codes: on J4_L24_Z96 at sigma 0.52, ten iterations of (6, 8, 6),
+    norm8 = 6 leave 14 of 400 frames in error at scale 8 and 9 at scale 16, which is what the fp32 decoder leaves at alpha 0.75."""
+
+    def __init__(self, bits_ch=6, bits_app=8, bits_msg=6, norm8=6, offset=0, llr_scale=16.0):
+        ints = dict(bits_ch=bits_ch, bits_app=bits_app, bits_msg=bits_msg, norm8=norm8, offset=offset)
+        for k, v in ints.items():
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError("%s must be an integer" % k)
+        llr_scale = float(llr_scale)
+        if not (np.isfinite(llr_scale) and llr_scale > 0):
+            raise ValueError("llr_scale=%r must be finite and positive" % llr_scale)
+        if not 2 <= bits_msg <= 8:
+            raise ValueError("bits_msg=%d outside [2, 8]" % bits_msg)
+        if not bits_msg <= bits_app <= 15:
+            raise ValueError("bits_app=%d outside [bits_msg=%d, 15]" % (bits_app, bits_msg))
+        if not 2 <= bits_ch <= bits_app:
+            raise ValueError("bits_ch=%d outside [2, bits_app=%d]" % (bits_ch, bits_app))
+        if not 1 <= norm8 <= 8:
+            raise ValueError("norm8=%d outside [1, 8]" % norm8)
+        if not 0 <= offset <= (1 << (bits_msg - 1)) - 1:
+            raise ValueError("offset=%d outside [0, %d]" % (offset, (1 << (bits_msg - 1)) - 1))
+        self.bits_ch, self.bits_app, self.bits_msg, self.norm8, self.offset = (int(v) for v in ints.values())
+        self.llr_scale = llr_scale
+
+    @property
+    def C(self):
+        return (1 << (self.bits_ch - 1)) - 1
+
+    @property
+    def A(self):
+        return (1 << (self.bits_app - 1)) - 1
+
+    @property
+    def Mx(self):
+        return (1 << (self.bits_msg - 1)) - 1
+
+    def c_struct(self):
+        return bldpc_quant(self.llr_scale, self.bits_ch, self.bits_app, self.bits_msg, self.norm8, self.offset)
+
+    def __repr__(self):
+        return "Quant(bits_ch=%d, bits_app=%d, bits_msg=%d, norm8=%d, offset=%d, llr_scale=%g)" % (
+            self.bits_ch, self.bits_app, self.bits_msg, self.norm8, self.offset, self.llr_scale)
+
+
+def _quant_ref(quant):
+    """byref of the C struct of a Quant; a raw _lib.bldpc_quant passes unchecked (the C side checks it) and None is the null pointer."""
+    if quant is None:
+        return None
+    if isinstance(quant, bldpc_quant):
+        return ctypes.byref(quant)
+    if not isinstance(quant, Quant):
+        raise ValueError("quant must be a cuda_ldpc_amd.Quant")
+    return ctypes.byref(quant.c_struct())
+
+
+def LDPC_Decoder_Quant_GPU(code, Channel_Out, quant, max_iter=25, length=0, exit_mode=EXIT_FIXED, stop_rule=STOP_PREFIX, D=None,
+                           want_app=False, stream=None):
+    """bldpc_decode_layered_quant: row-layered min-sum with finite word lengths (semantics in include/bldpc.h; Quant explains the
+    parameters and llr_scale), two frames per packed 16-bit instruction, codes made from block shifts only.
+
+    Channel_Out: CUDA float32 tensor [N, F] (frame-fastest).  stop_rule, exit_mode, length and D as in LDPC_Decoder_Layered_GPU.
+    Returns dict(D=int32 [N+1, F], app=int32 [N, F] or None: the a-posteriori words, iters=int32 [F]: iterations run by each frame)."""
+    if not (torch.is_tensor(Channel_Out) and Channel_Out.is_cuda and Channel_Out.dtype == torch.float32 and Channel_Out.is_contiguous()):
+        raise ValueError("Channel_Out must be a contiguous CUDA float32 tensor")
+    if Channel_Out.dim() != 2 or Channel_Out.shape[0] != code.N or Channel_Out.shape[1] <= 0:
+        raise ValueError("Channel_Out must be [N=%d, F]" % code.N)
+    F = int(Channel_Out.shape[1])
+    dev = Channel_Out.device
+    if D is None:
+        D = torch.empty((code.N + 1, F), dtype=torch.int32, device=dev)
+    else:
+        _check_D(D, code.N, F, dev)
+    app = torch.empty((code.N, F), dtype=torch.int32, device=dev) if want_app else None
+    iters = torch.empty(F, dtype=torch.int32, device=dev)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(dev)).cuda_stream)
+    check(lib.bldpc_decode_layered_quant(code._h, _dev_ptr(Channel_Out), F, int(max_iter), _quant_ref(quant), int(length), int(exit_mode),
+                                         int(stop_rule), _dev_ptr(D), _dev_ptr(app), _dev_ptr(iters), st), "LDPC_Decoder_Quant_GPU")
+    return dict(D=D, app=app, iters=iters)
+
+
+def quant_host(H, J, L, Z, y, quant, max_iter=25, length=0, exit_mode=EXIT_FIXED, stop_rule=STOP_PREFIX, want_app=True):
+    """bldpc_decode_layered_quant_host: the quantised layered decoder on the host (no device), the statement of its semantics.
+    y: float32 [N, F] host array (frame-fastest).  Returns dict(D=int32 [N+1, F], app=int32 [N, F] or None, iters=int32 [F])."""
+    H = np.ascontiguousarray(H, np.int32)
+    if H.size != J * L:
+        raise ValueError("H must hold J*L shifts")
+    y = np.ascontiguousarray(y, np.float32)
+    N = L * Z
+    if y.ndim != 2 or y.shape[0] != N or y.shape[1] <= 0:
+        raise ValueError("y must be [N=%d, F]" % N)
+    F = y.shape[1]
+    D = np.zeros((N + 1, F), np.int32)
+    app = np.zeros((N, F), np.int32) if want_app else None
+    iters = np.zeros(F, np.int32)
+    check(lib.bldpc_decode_layered_quant_host(J, L, Z, _np_ptr(H), _np_ptr(y), F, int(max_iter), _quant_ref(quant), int(length), int(exit_mode),
+                                              int(stop_rule), _np_ptr(D), None if app is None else _np_ptr(app), _np_ptr(iters)), "quant_host")
+    return dict(D=D, app=app, iters=iters)
 
 
 def normalised_host(H, J, L, Z, y, max_iter=50, alpha=1.0, length=0, exit_mode=EXIT_FIXED, want_app=True):

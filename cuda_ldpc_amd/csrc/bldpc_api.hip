@@ -16,6 +16,7 @@
 #include "bldpc_encode.hpp"
 #include "bldpc_layered.hpp"
 #include "bldpc_norm.hpp"
+#include "bldpc_quant.hpp"
 #include "bldpc_qc_kernel.hpp"
 #include "bldpc_table_kernels.hpp"
 #include "common.hpp"
@@ -44,6 +45,7 @@ struct bldpc_code {
     EncState *enc = nullptr; // systematic encoder and syndrome tables (bldpc_encode.hip), built on first use
     LayPlan *lay = nullptr;  // layered decoder: edge tables and its own scratch (bldpc_layered.hip), built on first use
     BpPlan *bp = nullptr;    // layered sum-product decoder: the same of its own (bldpc_bp.hip), built on first use
+    QuantPlan *quant = nullptr; // quantised layered min-sum decoder: the same of its own (bldpc_quant.hip), built on first use
 };
 
 LayView cldpc::lay_view(bldpc_code *c)
@@ -54,6 +56,11 @@ LayView cldpc::lay_view(bldpc_code *c)
 BpView cldpc::bp_view(bldpc_code *c)
 {
     return BpView{c->J, c->L, c->Z, c->N, c->M, c->K, c->has_qc ? c->H.data() : nullptr, &c->bp, &c->last_kernel};
+}
+
+QuantView cldpc::quant_view(bldpc_code *c)
+{
+    return QuantView{c->J, c->L, c->Z, c->N, c->M, c->K, c->has_qc ? c->H.data() : nullptr, &c->quant, &c->last_kernel};
 }
 
 CodeView cldpc::code_view(const bldpc_code *c)
@@ -236,6 +243,7 @@ extern "C" int bldpc_code_destroy(bldpc_code *c)
     enc_state_free(c->enc);
     lay_plan_free(c->lay);
     bp_plan_free(c->bp);
+    quant_plan_free(c->quant);
     for (hipEvent_t e : c->evr)
         if (e) (void)hipEventDestroy(e);
     delete c;

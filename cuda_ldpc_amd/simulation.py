@@ -15,15 +15,15 @@ from . import sharding
 from ._lib import check, lib
 from .bldpc import (EXIT_BATCH_GLOBAL, EXIT_FIXED, EXIT_PER_FRAME, KERNEL_AUTO, STOP_PREFIX, STOP_SYNDROME, AWGNChannel_CPU, AWGNChannel_GPU,
                     AWGNChannel_QAM_GPU, AWGNChannel_RM_Combine_GPU, AWGNChannel_RM_GPU, Decode_Statistic, Demodulate_QAM, Frames_Gather,
-                    Frames_Scatter, LDPC_Decoder_BP_GPU, LDPC_Decoder_GPU, LDPC_Decoder_Layered_GPU, Modulate_QAM, PN_CodeWords, RM_Recover, RM_Select, SimCounters,
-                    Syndrome, _dev_ptr, sigma_of)
+                    Frames_Scatter, LDPC_Decoder_BP_GPU, LDPC_Decoder_GPU, LDPC_Decoder_Layered_GPU, LDPC_Decoder_Quant_GPU, Modulate_QAM, PN_CodeWords,
+                    Quant, RM_Recover, RM_Select, SimCounters, Syndrome, _dev_ptr, sigma_of)
 from .nbldpc import sigma_of as nb_sigma_of
 
 
 def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, exit_mode=EXIT_BATCH_GLOBAL, kernel=KERNEL_AUTO,
                    leastErrorFrames=50, leastTestFrames=10000, displayStep=40960, dist=None, device=None, max_batches=None,
                    log=print, device_channel=False, PN_Message=0, pn_seed=0, schedule="flooding", alpha=1.0, stop_rule=None,
-                   n_QAM=2, CONSTELLATION=None, rate_match=None, short_llr=1.0e4):
+                   n_QAM=2, CONSTELLATION=None, rate_match=None, short_llr=1.0e4, quant=None):
     """One SNR point (Simulation.cu:12-171).  `seed` (int32[3]) is the AWGN->seed state, advanced in place by the
     WHOLE batch on every rank so that all ranks stay on the reference's single noise stream.
 
@@ -44,6 +44,10 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
     rate-matched included, which turns y = 1 - 2c + noise into a true LLR, and 1.0 on the QAM paths, whose demapper already scales by
     1 / (2 sigma^2).
 
+    schedule="quant" decodes with LDPC_Decoder_Quant_GPU (layered min-sum with the finite word lengths of `quant`, a Quant): everything
+    said of schedule="layered" holds, except that `alpha` is refused (quant.norm8 and quant.offset are the correction) and that the
+    decoder's input, whatever channel, modem or rate matching made it, goes through the quantiser with the gain quant.llr_scale.
+
     n_QAM != 2 sends the codewords over n_QAM-QAM instead of BPSK: CONSTELLATION (host float32 [n_QAM, 2], Get_CONSTELLATION) labels
     log2(n_QAM) consecutive codeword bits per point; a batch is encode -> Modulate_QAM -> AWGNChannel_QAM_GPU (four draws per symbol
     of the same noise stream) -> Demodulate_QAM with scale 1 / (2 sigma^2) -> the chosen decoder, and the caller passes the sigma of
@@ -58,14 +62,18 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
     device_channel=True."""
     if PN_Message not in (0, 1):
         raise ValueError("PN_Message must be 0 (all-zero codeword) or 1 (random codewords)")
-    if schedule not in ("flooding", "layered", "bp"):
-        raise ValueError("schedule must be 'flooding', 'layered' or 'bp'")
+    if schedule not in ("flooding", "layered", "bp", "quant"):
+        raise ValueError("schedule must be 'flooding', 'layered', 'bp' or 'quant'")
     bp = schedule == "bp"
-    layered = schedule == "layered" or bp  # sum-product shares the layered decoder's modes, rules and outputs
+    layered = schedule in ("layered", "bp", "quant")  # the row-layered decoders share modes, rules and outputs
     if bp and alpha != 1.0:
         raise ValueError("alpha belongs to the min-sum decoders: schedule='bp' has no normalisation factor")
+    if (schedule == "quant") != (quant is not None) or not isinstance(quant, (Quant, type(None))):
+        raise ValueError("schedule='quant' needs quant (a Quant), and quant belongs to schedule='quant'")
+    if quant is not None and alpha != 1.0:
+        raise ValueError("schedule='quant' takes its correction from quant.norm8 and quant.offset, not from alpha")
     if not layered and stop_rule is not None:
-        raise ValueError("stop_rule belongs to schedule='layered' and schedule='bp'")
+        raise ValueError("stop_rule belongs to schedule='layered', schedule='bp' and schedule='quant'")
     norm = not layered and alpha != 1.0  # normalised min-sum on the flooding decoders (LDPC_Decoder_GPU(alpha=...))
     if norm and exit_mode not in (EXIT_FIXED, EXIT_PER_FRAME):
         raise ValueError("schedule='flooding' with alpha takes EXIT_FIXED or EXIT_PER_FRAME")
@@ -145,6 +153,8 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
         if count and layered:
             if bp:
                 r = LDPC_Decoder_BP_GPU(code, yd, max_iter=maxIT, llr_scale=llr_scale, length=length, exit_mode=exit_mode, stop_rule=stop_rule, D=D)
+            elif quant is not None:
+                r = LDPC_Decoder_Quant_GPU(code, yd, quant, max_iter=maxIT, length=length, exit_mode=exit_mode, stop_rule=stop_rule, D=D)
             else:
                 r = LDPC_Decoder_Layered_GPU(code, yd, max_iter=maxIT, alpha=alpha, length=length, exit_mode=exit_mode, stop_rule=stop_rule, D=D)
             if PN_Message and stop_rule != STOP_SYNDROME:
@@ -212,7 +222,7 @@ def format_harq_row(SIM, info_bits):
 
 def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, maxIT=50, exit_mode=EXIT_FIXED, kernel=KERNEL_AUTO,
                         leastErrorFrames=50, leastTestFrames=10000, dist=None, device=None, max_batches=None, log=print, PN_Message=0,
-                        pn_seed=0, schedule="flooding", alpha=1.0, stop_rule=None, short_llr=1.0e4, compact=True, keep_D=None):
+                        pn_seed=0, schedule="flooding", alpha=1.0, stop_rule=None, short_llr=1.0e4, compact=True, keep_D=None, quant=None):
     """One SNR point of incremental-redundancy HARQ over BPSK on the device channel.  rvs = [rm_0, ..., rm_{T-1}]: the profile of
     each transmission (RateMatch.circular or RateMatch, all over code.N with the same shortened positions).  SIM is a HarqCounters.
 
@@ -227,7 +237,9 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
     followed by Syndrome(into_flag_row=True), or layered with STOP_SYNDROME (its default here) and either exit.  EXIT_BATCH_GLOBAL is
     refused: its results depend on the batch.  schedule="bp" (layered sum-product, LDPC_Decoder_BP_GPU) takes what schedule="layered"
     takes, but no `alpha`, and decodes with llr_scale = 2 / sigma^2: the sum of equal-sigma transmissions of a bit is a true LLR under that
-    factor.  A position no transmission has reached yet holds +0.0 and decides 0, so on the all-zero
+    factor.  schedule="quant" (LDPC_Decoder_Quant_GPU with the word lengths of `quant`, a Quant) takes what schedule="layered" takes, but
+    no `alpha`: combining stays in fp32 and the decoder quantises the accumulated values with the gain quant.llr_scale.
+    A position no transmission has reached yet holds +0.0 and decides 0, so on the all-zero
     word the flag flatters a first transmission with E < Ncb; random codewords do not have that bias.
 
     Draws: transmission t of a batch owns 2 * E_t * F draws of the noise stream, used or not -- `seed` (int32[3]) is advanced by the
@@ -235,16 +247,20 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
     into each.  One all-reduce of the counters per batch.  keep_D (a list) receives this rank's final D of every batch."""
     if PN_Message not in (0, 1):
         raise ValueError("PN_Message must be 0 (all-zero codeword) or 1 (random codewords)")
-    if schedule not in ("flooding", "layered", "bp"):
-        raise ValueError("schedule must be 'flooding', 'layered' or 'bp'")
+    if schedule not in ("flooding", "layered", "bp", "quant"):
+        raise ValueError("schedule must be 'flooding', 'layered', 'bp' or 'quant'")
     bp = schedule == "bp"
-    layered = schedule == "layered" or bp  # sum-product shares the layered decoder's modes, rules and outputs
+    layered = schedule in ("layered", "bp", "quant")  # the row-layered decoders share modes, rules and outputs
     if bp and alpha != 1.0:
         raise ValueError("alpha belongs to the min-sum decoders: schedule='bp' has no normalisation factor")
+    if (schedule == "quant") != (quant is not None) or not isinstance(quant, (Quant, type(None))):
+        raise ValueError("schedule='quant' needs quant (a Quant), and quant belongs to schedule='quant'")
+    if quant is not None and alpha != 1.0:
+        raise ValueError("schedule='quant' takes its correction from quant.norm8 and quant.offset, not from alpha")
     if exit_mode not in (EXIT_FIXED, EXIT_PER_FRAME):
         raise ValueError("HARQ takes EXIT_FIXED or EXIT_PER_FRAME: the results of EXIT_BATCH_GLOBAL depend on the batch")
     if not layered and stop_rule is not None:
-        raise ValueError("stop_rule belongs to schedule='layered' and schedule='bp'")
+        raise ValueError("stop_rule belongs to schedule='layered', schedule='bp' and schedule='quant'")
     norm = not layered and alpha != 1.0
     if layered:
         if stop_rule is None:
@@ -288,6 +304,8 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
             if bp:
                 r = LDPC_Decoder_BP_GPU(code, y, max_iter=maxIT, llr_scale=2.0 / (sigma * sigma), length=K, exit_mode=exit_mode, stop_rule=stop_rule,
                                         D=D)
+            elif quant is not None:
+                r = LDPC_Decoder_Quant_GPU(code, y, quant, max_iter=maxIT, length=K, exit_mode=exit_mode, stop_rule=stop_rule, D=D)
             else:
                 r = LDPC_Decoder_Layered_GPU(code, y, max_iter=maxIT, alpha=alpha, length=K, exit_mode=exit_mode, stop_rule=stop_rule, D=D)
             if PN_Message and stop_rule != STOP_SYNDROME:

@@ -307,6 +307,55 @@ int bldpc_decode_layered_bp_host(int J, int L, int Z, const int *H, const float 
 /* The correction table T[0 .. 127] of the two calls above (host pointer). */
 int bldpc_bp_table(float T[128]);
 
+/* -- quantised row-layered min-sum (finite word lengths; not in the reference) --------------------------------------- */
+
+/* The word lengths of bldpc_decode_layered_quant.  llr_scale is an absolute gain on the channel value: min-sum is
+ * scale-invariant, so it only sets the resolution of the quantiser (a value of y = 1.0 becomes the integer llr_scale). */
+typedef struct bldpc_quant {
+    float llr_scale;   /* finite, > 0: quantiser gain on the channel value */
+    int bits_ch;       /* 2 .. bits_app   channel word:        C  = 2^(bits_ch-1)  - 1 */
+    int bits_app;      /* bits_msg .. 15  a-posteriori word:   A  = 2^(bits_app-1) - 1 */
+    int bits_msg;      /* 2 .. 8          check message word:  Mx = 2^(bits_msg-1) - 1 */
+    int norm8;         /* 1 .. 8          normalisation in eighths (8 = none) */
+    int offset;        /* 0 .. Mx         offset subtracted after normalisation */
+} bldpc_quant;
+
+/* The layered min-sum decoder a hardware designer sizes: finite word lengths, normalised and / or offset correction in integer
+ * arithmetic, saturation at every store.  The schedule, the edge order, v_i, the flag rules, length, exit_mode
+ * (BLDPC_EXIT_FIXED or BLDPC_EXIT_PER_FRAME; BLDPC_EXIT_BATCH_GLOBAL refused), stop_rule, D, iters and asynchrony are exactly
+ * those of bldpc_decode_layered.  What differs, all in two's-complement integers:
+ *
+ *   Quantiser.  x = llr_scale * Channel_Out[v] (one fp32 product);
+ *     S[v] = x >= (float)C ? C : x <= -(float)C ? -C : (int)rintf(x)      (ties to even: 0.5 -> 0, 1.5 -> 2, -0.5 -> 0, -2.5 -> -2)
+ *   NaN is undefined.  R = 0 per edge.
+ *   Per row:
+ *     1. Q_i = S[v_i] - R_i                        (no clamp: |Q| <= A + Mx < 2^15 by the parameter ranges)
+ *     2. sg_i = (Q_i < 0), zero is positive;  a_i = min(|Q_i|, Mx);  P = XOR of the sg_i;  m1 <= m2 the two smallest a_i with
+ *        multiplicity;  first = lowest i with a_i == m1
+ *     3. g(m) = max(0, ((m * norm8 + 4) >> 3) - offset);  mag_i = (i == first) ? g(m2) : g(m1)
+ *        R_i' = (P xor sg_i) ? -mag_i : +mag_i
+ *     4. S[v_i] = min(A, max(-A, Q_i + R_i'));  R_i' replaces R_i
+ *   Hard bit d[v] = (S[v] < 0): S = 0 decodes to bit 0.
+ *
+ * The normalisation rounds: the smallest of the ~20 magnitudes of a rate-5/6 row is often 1, and (1 * 6) >> 3 would be 0.
+ *   app  optional device int32 [N][F] (out): S
+ * Refused with BLDPC_EINVAL and a message in bldpc_last_error: q == NULL, a parameter outside the ranges above, and the argument
+ * errors of bldpc_decode_layered.  Refused with BLDPC_EUNSUPPORTED: codes built from an address table, block rows of weight < 2.
+ * No allocation per call once the code object's scratch has grown (scratch and workspace of its own, apart from the other
+ * decoders').  Two frames share every 32-bit word and every packed 16-bit instruction; with odd F the last frame runs alone.
+ * bldpc_last_kernel names the tier that ran: "k_lq" (all iterations on-chip: per frame pair 4 N bytes of S and 16 bytes per
+ * check row in LDS; codes with Z <= 1024 of which one pair, 4 N + 16 J Z + 16 bytes, fits the 159 KiB a workgroup may ask for) or
+ * "k_lq_ws" (one workgroup per frame pair, S in place, row states in a device workspace kept in the code object: every other
+ * code). */
+int bldpc_decode_layered_quant(bldpc_code *code, const float *Channel_Out, int F, int max_iter, const bldpc_quant *q,
+                               int length, int exit_mode, int stop_rule, int *D, int *app, int *iters, void *stream);
+
+/* The same decoder on the host, all pointers host, no device needed: plain C++ that follows the steps above literally (one R per
+ * edge), frames over at most 16 threads, no upper weight limit.  It is the statement of the semantics inside the product and what
+ * the device kernels are tested against bit for bit.  NOT a fast path. */
+int bldpc_decode_layered_quant_host(int J, int L, int Z, const int *H, const float *Channel_Out, int F, int max_iter,
+                                    const bldpc_quant *q, int length, int exit_mode, int stop_rule, int *D, int *app, int *iters);
+
 /* -- normalised min-sum on the flooding decoders (not in the reference, whose flooding min-sum is un-normalised) ----- */
 
 /* The flooding iteration exactly as bldpc_decode runs it, with one change in the check-node update.  Semantics, IEEE fp32
@@ -541,7 +590,8 @@ int bldpc_last_kernel_ms(bldpc_code *code, float *ms);
  * profiled call records its own event pair, nothing synchronises until this function is called.  *launches = calls averaged. */
 int bldpc_kernel_ms_mean(bldpc_code *code, float *mean_ms, int *launches);
 
-/* Name of the kernel variant the last bldpc_decode / bldpc_decode_layered / bldpc_decode_layered_bp on this code used (static string). */
+/* Name of the kernel variant the last bldpc_decode / bldpc_decode_layered / bldpc_decode_layered_bp / bldpc_decode_layered_quant on
+ * this code used (static string). */
 const char *bldpc_last_kernel(const bldpc_code *code);
 
 /* -- the table of fused (QC_LDS) kernel variants, read-only ---------------------------------------------------------- */

@@ -5,6 +5,7 @@
     python sweep.py nb     --start 0 --stop 5 --step 0.5
     python sweep.py binary --device-channel --layered --per-frame --pn-message --harq 0:2160,2160:144,500:2400 --start 2 --stop 3 --step 0.5
     python sweep.py binary --device-channel --bp --per-frame --stop-rule syndrome --pn-message --start 2 --stop 3 --step 0.2
+    python sweep.py binary --device-channel --quant 6,8,6 --norm8 6 --llr-scale 16 --per-frame --stop-rule syndrome --pn-message --start 2 --stop 3 --step 0.2
     python -m torch.distributed.run --nproc-per-node N sweep.py binary ...      (frames sharded over N GPUs)
 
 binary: rows `SNR NTF NEF FER BER AverIT FER_F FER_A` as Simulation.cu:272 prints them (Es/N0, seeds 173/173/173,
@@ -73,6 +74,13 @@ def main():
     ap.add_argument("--layered", action="store_true", help="binary: row-layered normalised min-sum (bldpc_decode_layered); with --fixed or --per-frame")
     ap.add_argument("--bp", action="store_true", help="binary: row-layered sum-product (bldpc_decode_layered_bp, llr_scale = 2 / sigma^2 over BPSK, "
                     "1 over QAM); with --fixed or --per-frame, takes --stop-rule and every channel option, no --alpha")
+    ap.add_argument("--quant", metavar="CH,APP,MSG", default=None, help="binary: row-layered min-sum with finite word lengths "
+                    "(bldpc_decode_layered_quant): bits of the channel, a-posteriori and check-message words; with --fixed or --per-frame, takes "
+                    "--stop-rule and every channel option, no --alpha")
+    ap.add_argument("--norm8", type=int, default=6, help="--quant: normalisation in eighths, rounded (8 = none)")
+    ap.add_argument("--quant-offset", type=int, default=0, help="--quant: offset subtracted after the normalisation")
+    ap.add_argument("--llr-scale", type=float, default=16.0, help="--quant: quantiser gain on the channel value (resolution only: min-sum is "
+                    "scale-invariant; below about 16 the rate-5/6 codes lose error rate)")
     ap.add_argument("--alpha", type=float, default=1.0, help="binary: normalisation factor in (0, 1]; with --layered the layered decoder's, without it "
                     "normalised min-sum on the flooding decoders (with --fixed or --per-frame)")
     ap.add_argument("--stop-rule", choices=["prefix", "syndrome"], default=None,
@@ -100,14 +108,25 @@ def main():
         ap.error("--snrtype and --no-compact belong to --harq")
     if args.bp and (args.which != "binary" or args.layered or args.alpha != 1.0):
         ap.error("--bp belongs to the binary sweep, without --layered and without --alpha (sum-product has no normalisation factor)")
-    rows = args.layered or args.bp  # the two row-layered decoders take the same modes and rules
+    quant = None
+    if args.quant is not None:
+        if args.which != "binary" or args.layered or args.bp or args.alpha != 1.0:
+            ap.error("--quant belongs to the binary sweep, without --layered, --bp and --alpha (--norm8 and --quant-offset are its correction)")
+        try:
+            ch, app, msg = (int(x) for x in args.quant.split(","))
+        except ValueError:
+            ap.error("--quant takes three integers CH,APP,MSG")
+        quant = (ch, app, msg, args.norm8, args.quant_offset, args.llr_scale)  # checked by Quant once the package is imported
+    elif args.norm8 != 6 or args.quant_offset != 0 or args.llr_scale != 16.0:
+        ap.error("--norm8, --quant-offset and --llr-scale belong to --quant")
+    rows = args.layered or args.bp or quant is not None  # the row-layered decoders take the same modes and rules
     if args.which == "binary" and rows:
         if args.as_written or not (args.fixed or args.per_frame):
-            ap.error("--layered / --bp need a QC code and --fixed or --per-frame")
+            ap.error("--layered / --bp / --quant need a QC code and --fixed or --per-frame")
         if args.pn_message and args.per_frame and args.stop_rule == "prefix":
             ap.error("--pn-message --per-frame needs --stop-rule syndrome (the prefix rule tests for the all-zero word)")
     elif args.stop_rule is not None or (args.alpha != 1.0 and args.which != "binary"):
-        ap.error("--stop-rule belongs to the binary sweep with --layered or --bp, --alpha to the binary sweep")
+        ap.error("--stop-rule belongs to the binary sweep with --layered, --bp or --quant, --alpha to the binary sweep")
     elif args.alpha != 1.0 and not (args.fixed or args.per_frame):
         ap.error("--alpha without --layered (normalised flooding min-sum) needs --fixed or --per-frame")
     if args.which == "binary" and not rows and args.pn_message and (not args.fixed or args.as_written):
@@ -162,6 +181,11 @@ def main():
             lay = dict(schedule="layered", alpha=args.alpha, stop_rule=C.STOP_SYNDROME if stop == "syndrome" else C.STOP_PREFIX)
             if args.bp:
                 lay = dict(schedule="bp", stop_rule=lay["stop_rule"])
+            if quant is not None:
+                try:
+                    lay = dict(schedule="quant", quant=C.Quant(*quant), stop_rule=lay["stop_rule"])
+                except ValueError as e:
+                    ap.error("--quant: %s" % e)
         mod = {}
         if args.qam != 2:  # the GF(q) half's constellation file and sigma (Eb/N0, n_QAM in the formula): the two sweeps share both
             mod = dict(n_QAM=args.qam, CONSTELLATION=C.Get_CONSTELLATION(os.path.join(nbd, "Constellation", "GRAY_%dQAM.txt" % args.qam), args.qam))
@@ -172,6 +196,7 @@ def main():
                 print("# %s N=%d K=%d, HARQ over BPSK: buffer Ncb=%d (%d shortened, %d punctured), transmissions K0:E %s, first rate %.4f, %s, %s, "
                       "maxIT=%d, batch=%d x %d GPU(s)%s" % (os.path.basename(args.matrix), code.N, code.K, rvs[0].Ncb, rvs[0].n_short, rvs[0].n_punct,
                                                           args.harq, rvs[0].rate(code.K), "layered sum-product" if args.bp else
+                                                          "quantised layered min-sum %r" % lay["quant"] if quant is not None else
                                                           "layered alpha=%g" % args.alpha if args.layered else
                                                           "flooding alpha=%g" % args.alpha, "fixed iterations" if args.fixed else "per-frame early exit",
                                                           args.iters or (25 if rows else 50), args.batch, world,
@@ -194,6 +219,7 @@ def main():
             print("# %s N=%d K=%d, %s%s%s, maxIT=%d, batch=%d x %d GPU(s)%s" % (os.path.basename(args.matrix), code.N, code.K,
                   "" if args.qam == 2 else "%d-QAM (Gray) %d bits per point, max-log demapper, Eb/N0, " % (args.qam, args.qam.bit_length() - 1),
                   "layered sum-product llr_scale=%s stop=%s, " % ("2/sigma^2" if args.qam == 2 else "1", stop) if args.bp else
+                  "quantised layered min-sum %r stop=%s, " % (lay["quant"], stop) if quant is not None else
                   "layered min-sum alpha=%g stop=%s, " % (args.alpha, stop) if args.layered else
                   ("normalised flooding min-sum alpha=%g, " % args.alpha if args.alpha != 1.0 else ""),
                   "fixed iterations" if args.fixed else ("per-frame early exit" if args.per_frame else "batch-global early exit"),
