@@ -391,14 +391,10 @@ def LDPC_Decoder_GPU(code, Channel_Out, max_iter=50, length=0, exit_mode=EXIT_BA
     return dict(D=D, iteraTime=it.value, app=app, flag_hist=hist)
 
 
-def LDPC_Decoder_Layered_GPU(code, Channel_Out, max_iter=25, alpha=1.0, length=0, exit_mode=EXIT_FIXED, stop_rule=STOP_PREFIX, D=None,
-                             want_app=False, stream=None):
-    """bldpc_decode_layered: row-layered normalised min-sum (semantics in include/bldpc.h), codes made from block shifts only.
-
-    Channel_Out: CUDA float32 tensor [N, F] (frame-fastest).  alpha in (0, 1] scales every check message (1.0 = plain min-sum).
-    stop_rule: STOP_PREFIX (first `length` bits zero, the flooding decoders' rule) or STOP_SYNDROME (H d = 0, any codeword);
-    it is what row N of D means and what EXIT_PER_FRAME tests.  EXIT_BATCH_GLOBAL is refused.
-    Returns dict(D=int32 [N+1, F], app=float32 [N, F] or None, iters=int32 [F]: iterations run by each frame)."""
+def _layered_device(what, fn, code, Channel_Out, max_iter, param, length, exit_mode, stop_rule, D, want_app, app_dtype, stream):
+    """What the device wrappers of the row-layered decoders share: the checks of Channel_Out and D, the allocation of D, app and iters,
+    the stream, the C call `fn` (all three take the same arguments around the decoder's own parameter, which param() makes once the
+    inputs are checked) and the result dict."""
     if not (torch.is_tensor(Channel_Out) and Channel_Out.is_cuda and Channel_Out.dtype == torch.float32 and Channel_Out.is_contiguous()):
         raise ValueError("Channel_Out must be a contiguous CUDA float32 tensor")
     if Channel_Out.dim() != 2 or Channel_Out.shape[0] != code.N or Channel_Out.shape[1] <= 0:
@@ -409,17 +405,18 @@ def LDPC_Decoder_Layered_GPU(code, Channel_Out, max_iter=25, alpha=1.0, length=0
         D = torch.empty((code.N + 1, F), dtype=torch.int32, device=dev)
     else:
         _check_D(D, code.N, F, dev)
-    app = torch.empty((code.N, F), dtype=torch.float32, device=dev) if want_app else None
+    app = torch.empty((code.N, F), dtype=app_dtype, device=dev) if want_app else None
     iters = torch.empty(F, dtype=torch.int32, device=dev)
     st = ctypes.c_void_p((stream or torch.cuda.current_stream(dev)).cuda_stream)
-    check(lib.bldpc_decode_layered(code._h, _dev_ptr(Channel_Out), F, int(max_iter), ctypes.c_float(alpha), int(length), int(exit_mode),
-                                   int(stop_rule), _dev_ptr(D), _dev_ptr(app), _dev_ptr(iters), st), "LDPC_Decoder_Layered_GPU")
+    check(fn(code._h, _dev_ptr(Channel_Out), F, int(max_iter), param(), int(length), int(exit_mode), int(stop_rule), _dev_ptr(D), _dev_ptr(app),
+             _dev_ptr(iters), st), what)
     return dict(D=D, app=app, iters=iters)
 
 
-def layered_host(H, J, L, Z, y, max_iter=25, alpha=1.0, length=0, exit_mode=EXIT_FIXED, stop_rule=STOP_PREFIX, want_app=True):
-    """bldpc_decode_layered_host: the layered decoder on the host (no device), the statement of its semantics.  y: float32
-    [N, F] host array (frame-fastest).  Returns dict(D=int32 [N+1, F], app=float32 [N, F] or None, iters=int32 [F])."""
+def _host_statement(what, fn, H, J, L, Z, y, max_iter, param, length, exit_mode, stop_rule, want_app, app_dtype):
+    """What the wrappers of the host statements share: the checks of H and y, the allocation of D, app and iters, the C call `fn` (all
+    four take the same arguments around the decoder's own parameter, made by param(); stop_rule None: `fn` takes none) and the
+    result dict."""
     H = np.ascontiguousarray(H, np.int32)
     if H.size != J * L:
         raise ValueError("H must hold J*L shifts")
@@ -429,11 +426,31 @@ def layered_host(H, J, L, Z, y, max_iter=25, alpha=1.0, length=0, exit_mode=EXIT
         raise ValueError("y must be [N=%d, F]" % N)
     F = y.shape[1]
     D = np.zeros((N + 1, F), np.int32)
-    app = np.zeros((N, F), np.float32) if want_app else None
+    app = np.zeros((N, F), app_dtype) if want_app else None
     iters = np.zeros(F, np.int32)
-    check(lib.bldpc_decode_layered_host(J, L, Z, _np_ptr(H), _np_ptr(y), F, int(max_iter), ctypes.c_float(alpha), int(length), int(exit_mode),
-                                        int(stop_rule), _np_ptr(D), None if app is None else _np_ptr(app), _np_ptr(iters)), "layered_host")
+    rule = () if stop_rule is None else (int(stop_rule),)
+    check(fn(J, L, Z, _np_ptr(H), _np_ptr(y), F, int(max_iter), param(), int(length), int(exit_mode), *rule, _np_ptr(D),
+             None if app is None else _np_ptr(app), _np_ptr(iters)), what)
     return dict(D=D, app=app, iters=iters)
+
+
+def LDPC_Decoder_Layered_GPU(code, Channel_Out, max_iter=25, alpha=1.0, length=0, exit_mode=EXIT_FIXED, stop_rule=STOP_PREFIX, D=None,
+                             want_app=False, stream=None):
+    """bldpc_decode_layered: row-layered normalised min-sum (semantics in include/bldpc.h), codes made from block shifts only.
+
+    Channel_Out: CUDA float32 tensor [N, F] (frame-fastest).  alpha in (0, 1] scales every check message (1.0 = plain min-sum).
+    stop_rule: STOP_PREFIX (first `length` bits zero, the flooding decoders' rule) or STOP_SYNDROME (H d = 0, any codeword);
+    it is what row N of D means and what EXIT_PER_FRAME tests.  EXIT_BATCH_GLOBAL is refused.
+    Returns dict(D=int32 [N+1, F], app=float32 [N, F] or None, iters=int32 [F]: iterations run by each frame)."""
+    return _layered_device("LDPC_Decoder_Layered_GPU", lib.bldpc_decode_layered, code, Channel_Out, max_iter, lambda: ctypes.c_float(alpha), length,
+                           exit_mode, stop_rule, D, want_app, torch.float32, stream)
+
+
+def layered_host(H, J, L, Z, y, max_iter=25, alpha=1.0, length=0, exit_mode=EXIT_FIXED, stop_rule=STOP_PREFIX, want_app=True):
+    """bldpc_decode_layered_host: the layered decoder on the host (no device), the statement of its semantics.  y: float32
+    [N, F] host array (frame-fastest).  Returns dict(D=int32 [N+1, F], app=float32 [N, F] or None, iters=int32 [F])."""
+    return _host_statement("layered_host", lib.bldpc_decode_layered_host, H, J, L, Z, y, max_iter, lambda: ctypes.c_float(alpha), length, exit_mode,
+                           stop_rule, want_app, np.float32)
 
 
 def LDPC_Decoder_BP_GPU(code, Channel_Out, max_iter=25, llr_scale=1.0, length=0, exit_mode=EXIT_FIXED, stop_rule=STOP_PREFIX, D=None,
@@ -444,42 +461,15 @@ def LDPC_Decoder_BP_GPU(code, Channel_Out, max_iter=25, llr_scale=1.0, length=0,
     Channel_Out: CUDA float32 tensor [N, F] (frame-fastest).  llr_scale turns it into true LLRs: 2 / sigma^2 for the BPSK channels,
     1.0 after Demodulate_QAM with scale 1 / (2 sigma^2).  stop_rule, exit_mode, length and D as in LDPC_Decoder_Layered_GPU.
     Returns dict(D=int32 [N+1, F], app=float32 [N, F] or None, iters=int32 [F]: iterations run by each frame)."""
-    if not (torch.is_tensor(Channel_Out) and Channel_Out.is_cuda and Channel_Out.dtype == torch.float32 and Channel_Out.is_contiguous()):
-        raise ValueError("Channel_Out must be a contiguous CUDA float32 tensor")
-    if Channel_Out.dim() != 2 or Channel_Out.shape[0] != code.N or Channel_Out.shape[1] <= 0:
-        raise ValueError("Channel_Out must be [N=%d, F]" % code.N)
-    F = int(Channel_Out.shape[1])
-    dev = Channel_Out.device
-    if D is None:
-        D = torch.empty((code.N + 1, F), dtype=torch.int32, device=dev)
-    else:
-        _check_D(D, code.N, F, dev)
-    app = torch.empty((code.N, F), dtype=torch.float32, device=dev) if want_app else None
-    iters = torch.empty(F, dtype=torch.int32, device=dev)
-    st = ctypes.c_void_p((stream or torch.cuda.current_stream(dev)).cuda_stream)
-    check(lib.bldpc_decode_layered_bp(code._h, _dev_ptr(Channel_Out), F, int(max_iter), ctypes.c_float(llr_scale), int(length), int(exit_mode),
-                                      int(stop_rule), _dev_ptr(D), _dev_ptr(app), _dev_ptr(iters), st), "LDPC_Decoder_BP_GPU")
-    return dict(D=D, app=app, iters=iters)
+    return _layered_device("LDPC_Decoder_BP_GPU", lib.bldpc_decode_layered_bp, code, Channel_Out, max_iter, lambda: ctypes.c_float(llr_scale), length,
+                           exit_mode, stop_rule, D, want_app, torch.float32, stream)
 
 
 def bp_host(H, J, L, Z, y, max_iter=25, llr_scale=1.0, length=0, exit_mode=EXIT_FIXED, stop_rule=STOP_PREFIX, want_app=True):
     """bldpc_decode_layered_bp_host: the sum-product decoder on the host (no device), the statement of its semantics.  y: float32
     [N, F] host array (frame-fastest).  Returns dict(D=int32 [N+1, F], app=float32 [N, F] or None, iters=int32 [F])."""
-    H = np.ascontiguousarray(H, np.int32)
-    if H.size != J * L:
-        raise ValueError("H must hold J*L shifts")
-    y = np.ascontiguousarray(y, np.float32)
-    N = L * Z
-    if y.ndim != 2 or y.shape[0] != N or y.shape[1] <= 0:
-        raise ValueError("y must be [N=%d, F]" % N)
-    F = y.shape[1]
-    D = np.zeros((N + 1, F), np.int32)
-    app = np.zeros((N, F), np.float32) if want_app else None
-    iters = np.zeros(F, np.int32)
-    check(lib.bldpc_decode_layered_bp_host(J, L, Z, _np_ptr(H), _np_ptr(y), F, int(max_iter), ctypes.c_float(llr_scale), int(length),
-                                           int(exit_mode), int(stop_rule), _np_ptr(D), None if app is None else _np_ptr(app), _np_ptr(iters)),
-          "bp_host")
-    return dict(D=D, app=app, iters=iters)
+    return _host_statement("bp_host", lib.bldpc_decode_layered_bp_host, H, J, L, Z, y, max_iter, lambda: ctypes.c_float(llr_scale), length, exit_mode,
+                           stop_rule, want_app, np.float32)
 
 
 def BP_Table():
@@ -564,61 +554,23 @@ def LDPC_Decoder_Quant_GPU(code, Channel_Out, quant, max_iter=25, length=0, exit
 
     Channel_Out: CUDA float32 tensor [N, F] (frame-fastest).  stop_rule, exit_mode, length and D as in LDPC_Decoder_Layered_GPU.
     Returns dict(D=int32 [N+1, F], app=int32 [N, F] or None: the a-posteriori words, iters=int32 [F]: iterations run by each frame)."""
-    if not (torch.is_tensor(Channel_Out) and Channel_Out.is_cuda and Channel_Out.dtype == torch.float32 and Channel_Out.is_contiguous()):
-        raise ValueError("Channel_Out must be a contiguous CUDA float32 tensor")
-    if Channel_Out.dim() != 2 or Channel_Out.shape[0] != code.N or Channel_Out.shape[1] <= 0:
-        raise ValueError("Channel_Out must be [N=%d, F]" % code.N)
-    F = int(Channel_Out.shape[1])
-    dev = Channel_Out.device
-    if D is None:
-        D = torch.empty((code.N + 1, F), dtype=torch.int32, device=dev)
-    else:
-        _check_D(D, code.N, F, dev)
-    app = torch.empty((code.N, F), dtype=torch.int32, device=dev) if want_app else None
-    iters = torch.empty(F, dtype=torch.int32, device=dev)
-    st = ctypes.c_void_p((stream or torch.cuda.current_stream(dev)).cuda_stream)
-    check(lib.bldpc_decode_layered_quant(code._h, _dev_ptr(Channel_Out), F, int(max_iter), _quant_ref(quant), int(length), int(exit_mode),
-                                         int(stop_rule), _dev_ptr(D), _dev_ptr(app), _dev_ptr(iters), st), "LDPC_Decoder_Quant_GPU")
-    return dict(D=D, app=app, iters=iters)
+    return _layered_device("LDPC_Decoder_Quant_GPU", lib.bldpc_decode_layered_quant, code, Channel_Out, max_iter, lambda: _quant_ref(quant), length,
+                           exit_mode, stop_rule, D, want_app, torch.int32, stream)
 
 
 def quant_host(H, J, L, Z, y, quant, max_iter=25, length=0, exit_mode=EXIT_FIXED, stop_rule=STOP_PREFIX, want_app=True):
     """bldpc_decode_layered_quant_host: the quantised layered decoder on the host (no device), the statement of its semantics.
     y: float32 [N, F] host array (frame-fastest).  Returns dict(D=int32 [N+1, F], app=int32 [N, F] or None, iters=int32 [F])."""
-    H = np.ascontiguousarray(H, np.int32)
-    if H.size != J * L:
-        raise ValueError("H must hold J*L shifts")
-    y = np.ascontiguousarray(y, np.float32)
-    N = L * Z
-    if y.ndim != 2 or y.shape[0] != N or y.shape[1] <= 0:
-        raise ValueError("y must be [N=%d, F]" % N)
-    F = y.shape[1]
-    D = np.zeros((N + 1, F), np.int32)
-    app = np.zeros((N, F), np.int32) if want_app else None
-    iters = np.zeros(F, np.int32)
-    check(lib.bldpc_decode_layered_quant_host(J, L, Z, _np_ptr(H), _np_ptr(y), F, int(max_iter), _quant_ref(quant), int(length), int(exit_mode),
-                                              int(stop_rule), _np_ptr(D), None if app is None else _np_ptr(app), _np_ptr(iters)), "quant_host")
-    return dict(D=D, app=app, iters=iters)
+    return _host_statement("quant_host", lib.bldpc_decode_layered_quant_host, H, J, L, Z, y, max_iter, lambda: _quant_ref(quant), length, exit_mode,
+                           stop_rule, want_app, np.int32)
 
 
 def normalised_host(H, J, L, Z, y, max_iter=50, alpha=1.0, length=0, exit_mode=EXIT_FIXED, want_app=True):
     """bldpc_decode_normalised_host: the flooding decoder with normalised min-sum on the host (no device), the statement of its
     semantics.  y: float32 [N, F] host array (frame-fastest).  Returns dict(D=int32 [N+1, F], app=float32 [N, F] or None,
     iters=int32 [F]: iterations run by each frame)."""
-    H = np.ascontiguousarray(H, np.int32)
-    if H.size != J * L:
-        raise ValueError("H must hold J*L shifts")
-    y = np.ascontiguousarray(y, np.float32)
-    N = L * Z
-    if y.ndim != 2 or y.shape[0] != N or y.shape[1] <= 0:
-        raise ValueError("y must be [N=%d, F]" % N)
-    F = y.shape[1]
-    D = np.zeros((N + 1, F), np.int32)
-    app = np.zeros((N, F), np.float32) if want_app else None
-    iters = np.zeros(F, np.int32)
-    check(lib.bldpc_decode_normalised_host(J, L, Z, _np_ptr(H), _np_ptr(y), F, int(max_iter), ctypes.c_float(alpha), int(length), int(exit_mode),
-                                           _np_ptr(D), None if app is None else _np_ptr(app), _np_ptr(iters)), "normalised_host")
-    return dict(D=D, app=app, iters=iters)
+    return _host_statement("normalised_host", lib.bldpc_decode_normalised_host, H, J, L, Z, y, max_iter, lambda: ctypes.c_float(alpha), length,
+                           exit_mode, None, want_app, np.float32)
 
 
 def _qam_bits(q):

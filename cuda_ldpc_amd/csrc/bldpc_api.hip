@@ -12,11 +12,9 @@
 #include <new>
 #include <vector>
 
-#include "bldpc_bp.hpp"
 #include "bldpc_encode.hpp"
-#include "bldpc_layered.hpp"
+#include "bldpc_layer_plan.hpp"
 #include "bldpc_norm.hpp"
-#include "bldpc_quant.hpp"
 #include "bldpc_qc_kernel.hpp"
 #include "bldpc_table_kernels.hpp"
 #include "common.hpp"
@@ -43,24 +41,15 @@ struct bldpc_code {
     unsigned ev_n = 0; // decode calls recorded since the last bldpc_kernel_ms_mean
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     EncState *enc = nullptr; // systematic encoder and syndrome tables (bldpc_encode.hip), built on first use
-    LayPlan *lay = nullptr;  // layered decoder: edge tables and its own scratch (bldpc_layered.hip), built on first use
-    BpPlan *bp = nullptr;    // layered sum-product decoder: the same of its own (bldpc_bp.hip), built on first use
-    QuantPlan *quant = nullptr; // quantised layered min-sum decoder: the same of its own (bldpc_quant.hip), built on first use
+    // the row-layered decoders (bldpc_layered.hip, bldpc_bp.hip, bldpc_quant.hip): per decoder the edge tables, the tier choice and its own
+    // scratch, built on first use
+    LayerPlan *lay = nullptr, *bp = nullptr, *quant = nullptr;
 };
 
-LayView cldpc::lay_view(bldpc_code *c)
+LayerView cldpc::layer_view(bldpc_code *c, LayerSlot slot)
 {
-    return LayView{c->J, c->L, c->Z, c->N, c->M, c->K, c->has_qc ? c->H.data() : nullptr, &c->lay, &c->last_kernel};
-}
-
-BpView cldpc::bp_view(bldpc_code *c)
-{
-    return BpView{c->J, c->L, c->Z, c->N, c->M, c->K, c->has_qc ? c->H.data() : nullptr, &c->bp, &c->last_kernel};
-}
-
-QuantView cldpc::quant_view(bldpc_code *c)
-{
-    return QuantView{c->J, c->L, c->Z, c->N, c->M, c->K, c->has_qc ? c->H.data() : nullptr, &c->quant, &c->last_kernel};
+    LayerPlan **plan = slot == kSlotMinSum ? &c->lay : slot == kSlotBp ? &c->bp : &c->quant;
+    return LayerView{c->J, c->L, c->Z, c->N, c->M, c->K, c->has_qc ? c->H.data() : nullptr, plan, &c->last_kernel};
 }
 
 CodeView cldpc::code_view(const bldpc_code *c)
@@ -241,9 +230,9 @@ extern "C" int bldpc_code_destroy(bldpc_code *c)
     c->rq.release(); c->bad.release(); c->cnt.release(); c->bits.release(); c->yg.release(); c->errs.release(); c->itw.release();
     qc_plan_release(&c->qc);
     enc_state_free(c->enc);
-    lay_plan_free(c->lay);
-    bp_plan_free(c->bp);
-    quant_plan_free(c->quant);
+    delete c->lay;
+    delete c->bp;
+    delete c->quant;
     for (hipEvent_t e : c->evr)
         if (e) (void)hipEventDestroy(e);
     delete c;

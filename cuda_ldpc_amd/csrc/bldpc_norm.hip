@@ -9,11 +9,11 @@
 #include <cmath>
 #include <cstdint>
 #include <new>
-#include <thread>
 #include <vector>
 
 #define BLDPC_QC_KERNELS_ONLY
 #include "bldpc_qc_kernel.hpp"
+#include "bldpc_layer_host.hpp"
 #include "bldpc_norm.hpp"
 #include "common.hpp"
 
@@ -170,20 +170,11 @@ extern "C" int bldpc_decode_normalised_host(int J, int L, int Z, const int *H, c
             e.max_w = std::max(e.max_w, w);
             e.rowptr.push_back((int)e.col.size());
         }
-        const bool pf = exit_mode == BLDPC_EXIT_PER_FRAME;
-        const int T = (int)std::max(1u, std::min({16u, std::thread::hardware_concurrency(), (unsigned)F}));
-        auto work = [&](int a, int b) {
-            for (int f = a; f < b; f++) host_frame(e, J, L, Z, y, F, f, max_iter, alpha, length, pf, D, app, iters);
-        };
-        if (T <= 1) {
-            work(0, F);
-        } else {
-            std::vector<std::thread> th;
-            for (int t = 0; t < T; t++) th.emplace_back(work, (int)((long long)F * t / T), (int)((long long)F * (t + 1) / T));
-            for (auto &x : th) x.join();
-        }
     } catch (const std::bad_alloc &) {
         return fail(BLDPC_ENOMEM, "out of host memory");
     }
-    return BLDPC_OK;
+    const bool pf = exit_mode == BLDPC_EXIT_PER_FRAME;
+    return layer::for_frames(F, [&](int a, int b) {
+        for (int f = a; f < b; f++) host_frame(e, J, L, Z, y, F, f, max_iter, alpha, length, pf, D, app, iters);
+    });
 }

@@ -20,6 +20,22 @@ from .bldpc import (EXIT_BATCH_GLOBAL, EXIT_FIXED, EXIT_PER_FRAME, KERNEL_AUTO, 
 from .nbldpc import sigma_of as nb_sigma_of
 
 
+def _check_schedule(schedule, alpha, quant):
+    """The schedule of a sweep against its alpha and quant, as Simulation_GPU and Simulation_HARQ_GPU both refuse them.  Returns
+    (bp, layered): sum-product, any of the row-layered decoders."""
+    if schedule not in ("flooding", "layered", "bp", "quant"):
+        raise ValueError("schedule must be 'flooding', 'layered', 'bp' or 'quant'")
+    bp = schedule == "bp"
+    layered = schedule in ("layered", "bp", "quant")  # the row-layered decoders share modes, rules and outputs
+    if bp and alpha != 1.0:
+        raise ValueError("alpha belongs to the min-sum decoders: schedule='bp' has no normalisation factor")
+    if (schedule == "quant") != (quant is not None) or not isinstance(quant, (Quant, type(None))):
+        raise ValueError("schedule='quant' needs quant (a Quant), and quant belongs to schedule='quant'")
+    if quant is not None and alpha != 1.0:
+        raise ValueError("schedule='quant' takes its correction from quant.norm8 and quant.offset, not from alpha")
+    return bp, layered
+
+
 def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, exit_mode=EXIT_BATCH_GLOBAL, kernel=KERNEL_AUTO,
                    leastErrorFrames=50, leastTestFrames=10000, displayStep=40960, dist=None, device=None, max_batches=None,
                    log=print, device_channel=False, PN_Message=0, pn_seed=0, schedule="flooding", alpha=1.0, stop_rule=None,
@@ -62,16 +78,7 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
     device_channel=True."""
     if PN_Message not in (0, 1):
         raise ValueError("PN_Message must be 0 (all-zero codeword) or 1 (random codewords)")
-    if schedule not in ("flooding", "layered", "bp", "quant"):
-        raise ValueError("schedule must be 'flooding', 'layered', 'bp' or 'quant'")
-    bp = schedule == "bp"
-    layered = schedule in ("layered", "bp", "quant")  # the row-layered decoders share modes, rules and outputs
-    if bp and alpha != 1.0:
-        raise ValueError("alpha belongs to the min-sum decoders: schedule='bp' has no normalisation factor")
-    if (schedule == "quant") != (quant is not None) or not isinstance(quant, (Quant, type(None))):
-        raise ValueError("schedule='quant' needs quant (a Quant), and quant belongs to schedule='quant'")
-    if quant is not None and alpha != 1.0:
-        raise ValueError("schedule='quant' takes its correction from quant.norm8 and quant.offset, not from alpha")
+    bp, layered = _check_schedule(schedule, alpha, quant)
     if not layered and stop_rule is not None:
         raise ValueError("stop_rule belongs to schedule='layered', schedule='bp' and schedule='quant'")
     norm = not layered and alpha != 1.0  # normalised min-sum on the flooding decoders (LDPC_Decoder_GPU(alpha=...))
@@ -247,16 +254,7 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
     into each.  One all-reduce of the counters per batch.  keep_D (a list) receives this rank's final D of every batch."""
     if PN_Message not in (0, 1):
         raise ValueError("PN_Message must be 0 (all-zero codeword) or 1 (random codewords)")
-    if schedule not in ("flooding", "layered", "bp", "quant"):
-        raise ValueError("schedule must be 'flooding', 'layered', 'bp' or 'quant'")
-    bp = schedule == "bp"
-    layered = schedule in ("layered", "bp", "quant")  # the row-layered decoders share modes, rules and outputs
-    if bp and alpha != 1.0:
-        raise ValueError("alpha belongs to the min-sum decoders: schedule='bp' has no normalisation factor")
-    if (schedule == "quant") != (quant is not None) or not isinstance(quant, (Quant, type(None))):
-        raise ValueError("schedule='quant' needs quant (a Quant), and quant belongs to schedule='quant'")
-    if quant is not None and alpha != 1.0:
-        raise ValueError("schedule='quant' takes its correction from quant.norm8 and quant.offset, not from alpha")
+    bp, layered = _check_schedule(schedule, alpha, quant)
     if exit_mode not in (EXIT_FIXED, EXIT_PER_FRAME):
         raise ValueError("HARQ takes EXIT_FIXED or EXIT_PER_FRAME: the results of EXIT_BATCH_GLOBAL depend on the batch")
     if not layered and stop_rule is not None:

@@ -12,7 +12,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_layered_cpu import EXIT_BATCH_GLOBAL, EXIT_FIXED, EXIT_PER_FRAME, STOP_PREFIX, STOP_SYNDROME, read_H, same_bits, special_inputs
+from test_layered_cpu import (EXIT_BATCH_GLOBAL, EXIT_FIXED, EXIT_PER_FRAME, STOP_PREFIX, STOP_SYNDROME, raw_host_call, read_H, same_bits,
+                              special_inputs)
 from test_layered_shapes_cpu import F_RAMP, SHAPES, matrix_of, np_outputs, ramp_input, shape_id
 
 FIXED_ITER, MAX_ITER = 5, 10
@@ -273,10 +274,21 @@ def test_refusals(C):
     H1 = H.copy()
     H1[2, 1:] = -1  # a block row of weight 1
     refused(-5, H=H1)
+    with pytest.raises(LdpcError, match=r"\(-5\): .*weight 1 sends nothing back \(the sum-product row update needs weight >= 2\)$"):
+        C.bp_host(H1, J, L, Z, y)
     H0 = H.copy()
     H0[1, :] = -1  # and of weight 0
     refused(-5, H=H0)
+    with pytest.raises(LdpcError, match=r"\(-5\): .*weight 0\b"):
+        C.bp_host(H0, J, L, Z, y)
     import ctypes
+    # two faults at once: the first one in the order of the checks is the one reported (F, max_iter, llr_scale, length, stop_rule, exit_mode)
+    who = "bldpc_decode_layered_bp_host"
+    assert raw_host_call(C, who, J, L, Z, H, y, 0, 5, ctypes.c_float(0.0), 0) == (-1, who + ": F=0 must be positive")
+    assert raw_host_call(C, who, J, L, Z, H, y, 2, 5, ctypes.c_float(0.0), -1) == (-1, who + ": llr_scale=0 must be finite and positive")
+    assert raw_host_call(C, who, J, L, Z, H, y, 2, 0, ctypes.c_float(0.0), -1) == (-1, who + ": max_iter=0 must be at least 1")
+    assert raw_host_call(C, who, J, L, Z, H, y, 2, 5, ctypes.c_float(1.0), -1, stop_rule=2) == (-1, who + ": length=-1 outside [0,2304]")
+    assert raw_host_call(C, who, J, L, Z, H1, y, 0, 5, ctypes.c_float(0.0), 0)[0] == -5  # the rows come before the arguments
     D = np.zeros((L * Z + 1, 2), np.int32)
     for _ in range(2):
         rc = C._lib.lib.bldpc_decode_layered_bp_host(J, L, Z, H.ctypes.data_as(ctypes.c_void_p), y.ctypes.data_as(ctypes.c_void_p), 2, 5,

@@ -289,6 +289,18 @@ def test_refusals_on_the_device(C):
     rc = C._lib.lib.bldpc_decode_layered_bp(code._h, ctypes.c_void_p(y.data_ptr()), 4, 5, ctypes.c_float(1.0), 0, C.EXIT_PER_FRAME, C.STOP_PREFIX,
                                             ctypes.c_void_p(D.data_ptr()), None, None, st)
     assert rc == -1 and b"iters" in C._lib.lib.bldpc_last_error()
+    it = torch.empty(4, dtype=torch.int32, device="cuda")
+
+    def raw(F, max_iter, llr_scale, length):  # past the wrapper's own checks: F = 0 never reaches C through it
+        rc = C._lib.lib.bldpc_decode_layered_bp(code._h, ctypes.c_void_p(y.data_ptr()), F, max_iter, ctypes.c_float(llr_scale), length, C.EXIT_FIXED,
+                                                C.STOP_PREFIX, ctypes.c_void_p(D.data_ptr()), None, ctypes.c_void_p(it.data_ptr()), st)
+        return rc, C._lib.lib.bldpc_last_error().decode()
+
+    # two faults at once: the first one in the order of the checks is the one reported (F, max_iter, llr_scale, length)
+    who = "bldpc_decode_layered_bp"
+    assert raw(0, 5, 0.0, 0) == (-1, who + ": F=0 must be positive")
+    assert raw(4, 5, 0.0, -1) == (-1, who + ": llr_scale=0 must be finite and positive")
+    assert raw(4, 0, 0.0, -1) == (-1, who + ": max_iter=0 must be at least 1")
     name, J, L, Z = "J4_L24_Z96_BlockH.txt", 4, 24, 96
     H, wc, wv = C.Get_H(os.path.join(BL, name), J, L)
     table = C.BinaryCode.from_table(J, L, Z, wc, wv, C.Transform_H(H, J, L, Z, wc, wv))

@@ -202,14 +202,32 @@ def test_refusals_on_the_device(C):
     J, L, Z = _dims(fn)
     _, wc, wv = C.Get_H(os.path.join(BL, fn), J, L)
     table = C.BinaryCode.from_table(J, L, Z, wc, wv, C.Transform_H(H, J, L, Z, wc, wv))
-    with pytest.raises(LdpcError, match=r"\(-5\)"):
-        C.LDPC_Decoder_Layered_GPU(table, y)
     H1 = H.copy().reshape(J, L)
     H1[2, 1:] = -1
     H1[2, 0] = 0  # block row 2: weight 1
     thin = C.BinaryCode.from_shifts(H1.reshape(-1), J, L, Z)
-    with pytest.raises(LdpcError, match=r"\(-5\)"):
-        C.LDPC_Decoder_Layered_GPU(thin, y)
+    for bad, text in ((table, "address table"), (thin, r"weight 1\b")):  # the same answer on the second call
+        said = []
+        for _ in range(2):
+            with pytest.raises(LdpcError, match=r"\(-5\): .*" + text) as e:
+                C.LDPC_Decoder_Layered_GPU(bad, y)
+            said.append(str(e.value))
+        assert said[0] == said[1]
+    import ctypes
+    D = torch.empty((code.N + 1, 4), dtype=torch.int32, device="cuda")
+    it = torch.empty(4, dtype=torch.int32, device="cuda")
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def raw(F, max_iter, alpha, length):  # past the wrapper's own checks: F = 0 never reaches C through it
+        rc = C._lib.lib.bldpc_decode_layered(code._h, ctypes.c_void_p(y.data_ptr()), F, max_iter, ctypes.c_float(alpha), length, C.EXIT_FIXED,
+                                             C.STOP_PREFIX, ctypes.c_void_p(D.data_ptr()), None, ctypes.c_void_p(it.data_ptr()), st)
+        return rc, C._lib.lib.bldpc_last_error().decode()
+
+    # two faults at once: the first one in the order of the checks is the one reported (F, max_iter, alpha, length)
+    who = "bldpc_decode_layered"
+    assert raw(0, 5, 0.0, 0) == (-1, who + ": F=0 must be positive")
+    assert raw(4, 5, 2.0, -1) == (-1, who + ": alpha=2 outside (0, 1]")
+    assert raw(4, 0, 2.0, -1) == (-1, who + ": max_iter=0 must be at least 1")
     with pytest.raises(ValueError):
         C.LDPC_Decoder_Layered_GPU(code, y, D=torch.empty((code.N, 4), dtype=torch.int32, device="cuda"))
 

@@ -15,7 +15,7 @@ import pytest
 from quant_cases import (ACCEPTED, BY_DIMS, CLAMPS, F_PAIR, FIXED_ITER, INPUT, MAX_ITER, PARAMS, TIER, app_clamp_possible, input_for, np_quant_history,
                          np_quantise, pair_history, pair_input, special_input, tier_by_rule)
 from test_bp_cpu import fnv64, generated_input
-from test_layered_cpu import EXIT_BATCH_GLOBAL, EXIT_FIXED, EXIT_PER_FRAME, STOP_PREFIX, STOP_SYNDROME, read_H
+from test_layered_cpu import EXIT_BATCH_GLOBAL, EXIT_FIXED, EXIT_PER_FRAME, STOP_PREFIX, STOP_SYNDROME, raw_host_call, read_H
 from test_layered_shapes_cpu import SHAPES, matrix_of, np_outputs, shape_id
 
 GPU_PARAMS = ("P0", "P3")  # what test_quant_gpu.py runs on the random shapes
@@ -267,6 +267,16 @@ def test_refusals(C):
     H0[1, :] = -1  # and of weight 0
     with pytest.raises(LdpcError, match=r"\(-5\): .*weight 0\b"):
         C.quant_host(H0, J, L, Z, y, good)
+    # two faults at once: the quantiser's parameters are checked first, before the rows; then F, max_iter, length, stop_rule, exit_mode
+    who = "bldpc_decode_layered_quant_host"
+    ref = lambda **kw: ctypes.byref(raw(**kw))  # noqa: E731
+    assert raw_host_call(C, who, J, L, Z, H, y, 0, 5, ref(llr_scale=0.0), 0) == (-1, who + ": llr_scale=0 must be finite and positive")
+    assert raw_host_call(C, who, J, L, Z, H, y, 2, 5, ref(bits_msg=1), -1) == (-1, who + ": bits_msg=1 outside [2,8]")
+    assert raw_host_call(C, who, J, L, Z, H1, y, 2, 5, ref(norm8=9), 0) == (-1, who + ": norm8=9 outside [1,8]")
+    assert raw_host_call(C, who, J, L, Z, H, y, 0, 0, ref(), -1) == (-1, who + ": F=0 must be positive")
+    assert raw_host_call(C, who, J, L, Z, H, y, 2, 0, ref(), -1) == (-1, who + ": max_iter=0 must be at least 1")
+    assert raw_host_call(C, who, J, L, Z, H, y, 2, 5, ref(), -1, stop_rule=2) == (-1, who + ": length=-1 outside [0,2304]")
+    assert raw_host_call(C, who, J, L, Z, H1, y, 0, 5, ref(), 0)[0] == -5  # the rows come before the arguments
     D = np.zeros((L * Z + 1, 2), np.int32)
     for _ in range(2):
         rc = C._lib.lib.bldpc_decode_layered_quant_host(J, L, Z, H.ctypes.data_as(ctypes.c_void_p), y.ctypes.data_as(ctypes.c_void_p), 2, 5,

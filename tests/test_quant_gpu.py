@@ -238,6 +238,19 @@ def test_refusals_on_the_device(C):
     rc = C._lib.lib.bldpc_decode_layered_quant(code._h, ctypes.c_void_p(y.data_ptr()), 4, 5, ctypes.byref(good.c_struct()), 0, C.EXIT_PER_FRAME,
                                                C.STOP_PREFIX, ctypes.c_void_p(D.data_ptr()), None, None, st)
     assert rc == -1 and b"iters" in C._lib.lib.bldpc_last_error()
+    it = torch.empty(4, dtype=torch.int32, device="cuda")
+
+    def raw(F, max_iter, q, length):  # past the wrapper's own checks: F = 0 never reaches C through it
+        rc = C._lib.lib.bldpc_decode_layered_quant(code._h, ctypes.c_void_p(y.data_ptr()), F, max_iter, ctypes.byref(q), length, C.EXIT_FIXED,
+                                                   C.STOP_PREFIX, ctypes.c_void_p(D.data_ptr()), None, ctypes.c_void_p(it.data_ptr()), st)
+        return rc, C._lib.lib.bldpc_last_error().decode()
+
+    # two faults at once: the quantiser's parameters are checked first, then F, max_iter, length
+    who = "bldpc_decode_layered_quant"
+    assert raw(0, 5, bldpc_quant(0.0, 6, 8, 6, 6, 0), 0) == (-1, who + ": llr_scale=0 must be finite and positive")
+    assert raw(4, 5, bldpc_quant(16.0, 6, 8, 1, 6, 0), -1) == (-1, who + ": bits_msg=1 outside [2,8]")
+    assert raw(0, 5, good.c_struct(), -1) == (-1, who + ": F=0 must be positive")
+    assert raw(4, 0, good.c_struct(), -1) == (-1, who + ": max_iter=0 must be at least 1")
     name, J, L, Z = "J4_L24_Z96_BlockH.txt", 4, 24, 96
     H, wc, wv = C.Get_H(os.path.join(BL, name), J, L)
     table = C.BinaryCode.from_table(J, L, Z, wc, wv, C.Transform_H(H, J, L, Z, wc, wv))
