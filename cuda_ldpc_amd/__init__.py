@@ -13,7 +13,8 @@ from .bldpc import (BinaryCode, Get_H, Transform_H, LDPC_Decoder_GPU, Decode_Sta
                     Modulate_QAM, AWGNChannel_QAM_GPU, Demodulate_QAM, Modulate_QAM_host, Demodulate_QAM_host, Get_CONSTELLATION, qc_variants, qc_plan_host,
                     RateMatch, RM_Select, RM_Recover, AWGNChannel_RM_GPU, RM_Select_host, RM_Recover_host, AWGNChannel_RM_CPU,
                     RM_Combine, AWGNChannel_RM_Combine_GPU, Frames_Gather, Frames_Scatter, RM_Combine_host, AWGNChannel_RM_Combine_CPU,
-                    Frames_Gather_host, Frames_Scatter_host,
+                    Frames_Gather_host, Frames_Scatter_host, RM_Modulate_QAM, RM_Demodulate_QAM_Recover, RM_Demodulate_QAM_Combine,
+                    RM_Modulate_QAM_host, RM_Demodulate_QAM_Recover_host, RM_Demodulate_QAM_Combine_host, IL_NONE, IL_ROWCOL,
                     STOP_PREFIX, STOP_SYNDROME, EXIT_FIXED, EXIT_BATCH_GLOBAL, EXIT_PER_FRAME, KERNEL_AUTO, KERNEL_TABLE, KERNEL_QC_LDS)
 
 __all__ = ["BinaryCode", "Get_H", "Transform_H", "LDPC_Decoder_GPU", "Decode_Statistic", "Statistic", "SimCounters", "AWGNChannel_CPU", "AWGNChannel_GPU", "sigma_of",
@@ -22,6 +23,7 @@ __all__ = ["BinaryCode", "Get_H", "Transform_H", "LDPC_Decoder_GPU", "Decode_Sta
            "Modulate_QAM", "AWGNChannel_QAM_GPU", "Demodulate_QAM", "Modulate_QAM_host", "Demodulate_QAM_host", "Get_CONSTELLATION", "qc_variants", "qc_plan_host",
            "RateMatch", "RM_Select", "RM_Recover", "AWGNChannel_RM_GPU", "RM_Select_host", "RM_Recover_host", "AWGNChannel_RM_CPU",
            "RM_Combine", "AWGNChannel_RM_Combine_GPU", "Frames_Gather", "Frames_Scatter", "RM_Combine_host", "AWGNChannel_RM_Combine_CPU",
-           "Frames_Gather_host", "Frames_Scatter_host",
+           "Frames_Gather_host", "Frames_Scatter_host", "RM_Modulate_QAM", "RM_Demodulate_QAM_Recover", "RM_Demodulate_QAM_Combine",
+           "RM_Modulate_QAM_host", "RM_Demodulate_QAM_Recover_host", "RM_Demodulate_QAM_Combine_host", "IL_NONE", "IL_ROWCOL",
            "STOP_PREFIX", "STOP_SYNDROME",
            "EXIT_FIXED", "EXIT_BATCH_GLOBAL", "EXIT_PER_FRAME", "KERNEL_AUTO", "KERNEL_TABLE", "KERNEL_QC_LDS"]

@@ -77,7 +77,17 @@ lib.bldpc_qam_map.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
 lib.bldpc_qam_demap.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_float, c_int, c_int, c_void_p, c_void_p]
 lib.bldpc_qam_map_host.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p]
 lib.bldpc_qam_demap_host.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_float, c_int, c_int, c_void_p]
-lib.bldpc_rm_create.argtypes = [c_int, c_void_p, c_int, c_void_p, c_int, ctypes.POINTER(c_void_p)]
+lib.bldpc_qam_map_il.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
+lib.bldpc_qam_demap_il.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_float, c_int, c_int, c_int, c_void_p, c_void_p]
+lib.bldpc_qam_map_il_host.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_void_p]
+lib.bldpc_qam_demap_il_host.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_float, c_int, c_int, c_int, c_void_p]
+lib.bldpc_rm_qam_map.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
+lib.bldpc_rm_qam_recover.argtypes = [c_void_p, c_void_p, c_void_p, c_int, ctypes.c_float, c_int, c_int, ctypes.c_float, c_void_p, c_void_p]
+lib.bldpc_rm_qam_combine.argtypes = [c_void_p, c_void_p, c_void_p, c_int, ctypes.c_float, c_int, c_int, ctypes.c_float, c_void_p, c_void_p, c_void_p]
+lib.bldpc_rm_qam_map_host.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]
+lib.bldpc_rm_qam_recover_host.argtypes = [c_void_p, c_void_p, c_void_p, c_int, ctypes.c_float, c_int, c_int, ctypes.c_float, c_void_p]
+lib.bldpc_rm_qam_combine_host.argtypes = [c_void_p, c_void_p, c_void_p, c_int, ctypes.c_float, c_int, c_int, ctypes.c_float, c_void_p, c_void_p]
+lib.bldpc_rm_create.argtypes =[c_int, c_void_p, c_int, c_void_p, c_int, ctypes.POINTER(c_void_p)]
 lib.bldpc_rm_destroy.argtypes = [c_void_p]
 lib.bldpc_rm_dims.argtypes = [c_void_p, c_void_p]
 lib.bldpc_rm_tx_pos.argtypes = [c_void_p, c_void_p]

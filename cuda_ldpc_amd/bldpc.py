@@ -18,6 +18,7 @@ from .nbldpc import Get_CONSTELLATION  # noqa: F401  -- the constellation files 
 EXIT_FIXED, EXIT_BATCH_GLOBAL, EXIT_PER_FRAME = 0, 1, 2
 KERNEL_AUTO, KERNEL_TABLE, KERNEL_QC_LDS = 0, 1, 2
 STOP_PREFIX, STOP_SYNDROME = 0, 1  # stop rules of the layered decoder (bldpc.h)
+IL_NONE, IL_ROWCOL = 0, 1  # index rules of the QAM modem (bldpc.h): bit b of symbol s is bit s*m + b, or b*Ns + s (row-column interleaver)
 
 
 def _np_ptr(a):
@@ -594,11 +595,19 @@ def _check_con(constellation, dev=None):
     return constellation, _qam_bits(constellation.shape[0])
 
 
-def Modulate_QAM(CodeWord, N, m, F=None, device=None, stream=None):
-    """bldpc_qam_map: CodeWord CUDA int32 [N, F] (frame-fastest) -> constellation indices sym int32 [F, Ns], Ns = ceil(N / m); bit b
-    of sym[f, s] is codeword bit s*m + b, pad bits 0 (include/bldpc.h).  CodeWord=None sends the all-zero word and needs F."""
+def _check_il(interleave):
+    if interleave not in (IL_NONE, IL_ROWCOL):
+        raise ValueError("interleave must be IL_NONE (0) or IL_ROWCOL (1), not %r" % (interleave,))
+    return int(interleave)
+
+
+def Modulate_QAM(CodeWord, N, m, F=None, device=None, stream=None, interleave=IL_NONE):
+    """bldpc_qam_map_il: CodeWord CUDA int32 [N, F] (frame-fastest) -> constellation indices sym int32 [F, Ns], Ns = ceil(N / m); bit b
+    of sym[f, s] is codeword bit s*m + b (IL_NONE) or b*Ns + s (IL_ROWCOL), pad bits 0 (include/bldpc.h).  CodeWord=None sends the
+    all-zero word and needs F."""
     if not 1 <= int(m) <= 8:
         raise ValueError("m must be in 1..8")
+    il = _check_il(interleave)
     if CodeWord is None:
         if F is None or F <= 0 or N <= 0:
             raise ValueError("CodeWord=None (the all-zero word) needs positive N and F")
@@ -610,7 +619,7 @@ def Modulate_QAM(CodeWord, N, m, F=None, device=None, stream=None):
         _check_cw(CodeWord, N, F, device)
     sym = torch.empty((F, (N + m - 1) // m), dtype=torch.int32, device=device)
     st = ctypes.c_void_p((stream or torch.cuda.current_stream(device)).cuda_stream)
-    check(lib.bldpc_qam_map(_dev_ptr(CodeWord), N, F, int(m), _dev_ptr(sym), st), "Modulate_QAM")
+    check(lib.bldpc_qam_map_il(_dev_ptr(CodeWord), N, F, int(m), il, _dev_ptr(sym), st), "Modulate_QAM")
     return sym
 
 
@@ -633,10 +642,12 @@ def AWGNChannel_QAM_GPU(seed, sigma, sym, constellation, stream=None):
     return rx
 
 
-def Demodulate_QAM(rx, constellation, scale, N, stream=None):
-    """bldpc_qam_demap: max-log soft values of the N codeword bits of every frame.  rx CUDA float32 [F, Ns, 2] with
+def Demodulate_QAM(rx, constellation, scale, N, stream=None, interleave=IL_NONE):
+    """bldpc_qam_demap_il: max-log soft values of the N codeword bits of every frame.  rx CUDA float32 [F, Ns, 2] with
     Ns = ceil(N / log2 q), constellation CUDA float32 [q, 2] -> Channel_Out CUDA float32 [N, F] (frame-fastest, positive = bit 0),
-    (m1 - m0) * scale: scale = 1 / (2 sigma^2) for LLRs, 1.0 is as good for the min-sum decoders."""
+    (m1 - m0) * scale: scale = 1 / (2 sigma^2) for LLRs, 1.0 is as good for the min-sum decoders.  interleave: the rule Modulate_QAM
+    was given."""
+    il = _check_il(interleave)
     if not (torch.is_tensor(rx) and rx.is_cuda and rx.dtype == torch.float32 and rx.is_contiguous() and rx.dim() == 3 and rx.shape[2] == 2):
         raise ValueError("rx must be a contiguous CUDA float32 tensor [F, Ns, 2]")
     con, m = _check_con(constellation, rx.device)
@@ -645,14 +656,15 @@ def Demodulate_QAM(rx, constellation, scale, N, stream=None):
         raise ValueError("rx must hold ceil(N / m) = %d symbols per frame, not %d" % ((N + m - 1) // m, rx.shape[1]))
     out = torch.empty((N, F), dtype=torch.float32, device=rx.device)
     st = ctypes.c_void_p((stream or torch.cuda.current_stream(rx.device)).cuda_stream)
-    check(lib.bldpc_qam_demap(_dev_ptr(rx), _dev_ptr(con), int(con.shape[0]), ctypes.c_float(scale), N, F, _dev_ptr(out), st), "Demodulate_QAM")
+    check(lib.bldpc_qam_demap_il(_dev_ptr(rx), _dev_ptr(con), int(con.shape[0]), ctypes.c_float(scale), N, F, il, _dev_ptr(out), st), "Demodulate_QAM")
     return out
 
 
-def Modulate_QAM_host(CodeWord, N, m, F=None):
-    """bldpc_qam_map_host: Modulate_QAM on host arrays, no device needed (the statement of the semantics).  -> int32 [F, Ns]."""
+def Modulate_QAM_host(CodeWord, N, m, F=None, interleave=IL_NONE):
+    """bldpc_qam_map_il_host: Modulate_QAM on host arrays, no device needed (the statement of the semantics).  -> int32 [F, Ns]."""
     if not 1 <= int(m) <= 8:
         raise ValueError("m must be in 1..8")
+    il = _check_il(interleave)
     if CodeWord is None:
         if F is None or F <= 0 or N <= 0:
             raise ValueError("CodeWord=None (the all-zero word) needs positive N and F")
@@ -663,19 +675,20 @@ def Modulate_QAM_host(CodeWord, N, m, F=None):
             raise ValueError("CodeWord must be [N=%d, F]" % N)
         F = cw.shape[1]
     sym = np.empty((F, (N + m - 1) // m), np.int32)
-    check(lib.bldpc_qam_map_host(None if cw is None else _np_ptr(cw), N, F, int(m), _np_ptr(sym)), "Modulate_QAM_host")
+    check(lib.bldpc_qam_map_il_host(None if cw is None else _np_ptr(cw), N, F, int(m), il, _np_ptr(sym)), "Modulate_QAM_host")
     return sym
 
 
-def Demodulate_QAM_host(rx, constellation, scale, N):
-    """bldpc_qam_demap_host: Demodulate_QAM on host arrays, no device needed.  rx float32 [F, Ns, 2] -> float32 [N, F]."""
+def Demodulate_QAM_host(rx, constellation, scale, N, interleave=IL_NONE):
+    """bldpc_qam_demap_il_host: Demodulate_QAM on host arrays, no device needed.  rx float32 [F, Ns, 2] -> float32 [N, F]."""
+    il = _check_il(interleave)
     con, m = _check_con(constellation)
     rx = np.ascontiguousarray(rx, np.float32)
     if N <= 0 or rx.ndim != 3 or rx.shape[0] <= 0 or rx.shape[1] != (N + m - 1) // m or rx.shape[2] != 2:
         raise ValueError("rx must be float32 [F, ceil(N / m) = %d, 2]" % ((N + m - 1) // m))
     F = rx.shape[0]
     out = np.empty((N, F), np.float32)
-    check(lib.bldpc_qam_demap_host(_np_ptr(rx), _np_ptr(con), con.shape[0], ctypes.c_float(scale), N, F, _np_ptr(out)), "Demodulate_QAM_host")
+    check(lib.bldpc_qam_demap_il_host(_np_ptr(rx), _np_ptr(con), con.shape[0], ctypes.c_float(scale), N, F, il, _np_ptr(out)), "Demodulate_QAM_host")
     return out
 
 
@@ -900,6 +913,119 @@ def AWGNChannel_RM_Combine_CPU(rm, seed, sigma, Channel_Acc, done=None, CodeWord
     done = _host_done(done, F)
     check(lib.bldpc_rm_awgn_combine_host(rm._h, _np_ptr(seed), ctypes.c_float(sigma), None if cw is None else _np_ptr(cw), F,
                                          ctypes.c_float(short_llr), None if done is None else _np_ptr(done), _np_ptr(acc)), "AWGNChannel_RM_Combine_CPU")
+    return acc
+
+# ---- rate matching over QAM: the fused calls (include/bldpc.h, "rate matching over QAM") ----
+def _check_rm_rx(rm, rx, m, dev=None):
+    """rx [F, ceil(E / m), 2] float32: a contiguous CUDA tensor (dev: True), or anything numpy reads.  Returns (rx, F)."""
+    Ns = (rm.E + m - 1) // m
+    if dev:
+        if not (torch.is_tensor(rx) and rx.is_cuda and rx.dtype == torch.float32 and rx.is_contiguous() and rx.dim() == 3
+                and rx.shape[0] > 0 and rx.shape[1] == Ns and rx.shape[2] == 2):
+            raise ValueError("rx must be a contiguous CUDA float32 tensor [F, ceil(E / m) = %d, 2]" % Ns)
+    else:
+        rx = np.ascontiguousarray(rx, np.float32)
+        if rx.ndim != 3 or rx.shape[0] <= 0 or rx.shape[1] != Ns or rx.shape[2] != 2:
+            raise ValueError("rx must be float32 [F, ceil(E / m) = %d, 2]" % Ns)
+    return rx, int(rx.shape[0])
+
+
+def RM_Modulate_QAM(rm, CodeWord, m, F=None, device=None, stream=None, interleave=IL_NONE):
+    """bldpc_rm_qam_map: Modulate_QAM(RM_Select(rm, CodeWord), rm.E, m, interleave=...) in one pass, no [E, F] array.  CodeWord CUDA
+    int32 [N, F] -> sym int32 [F, ceil(E / m)].  CodeWord=None sends the all-zero word and needs F."""
+    if not 1 <= int(m) <= 8:
+        raise ValueError("m must be in 1..8")
+    il = _check_il(interleave)
+    if CodeWord is None:
+        if F is None or F <= 0:
+            raise ValueError("CodeWord=None (the all-zero word) needs a positive F")
+        device = device or torch.device("cuda", torch.cuda.current_device())
+    else:
+        if not (torch.is_tensor(CodeWord) and CodeWord.dim() == 2 and CodeWord.shape[0] == rm.N and CodeWord.shape[1] > 0):
+            raise ValueError("CodeWord must be [N=%d, F]" % rm.N)
+        F, device = int(CodeWord.shape[1]), CodeWord.device
+        _check_cw(CodeWord, rm.N, F, device)
+    sym = torch.empty((F, (rm.E + m - 1) // m), dtype=torch.int32, device=device)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(device)).cuda_stream)
+    check(lib.bldpc_rm_qam_map(rm._h, _dev_ptr(CodeWord), F, int(m), il, _dev_ptr(sym), st), "RM_Modulate_QAM")
+    return sym
+
+
+def RM_Demodulate_QAM_Recover(rm, rx, constellation, scale, short_llr=1.0e4, stream=None, interleave=IL_NONE):
+    """bldpc_rm_qam_recover: RM_Recover(rm, Demodulate_QAM(rx, constellation, scale, rm.E, interleave=...), short_llr) in one pass.
+    rx CUDA float32 [F, ceil(E / m), 2] -> Channel_Out [N, F]."""
+    il = _check_il(interleave)
+    _check_short_llr(short_llr)
+    if not (torch.is_tensor(rx) and rx.is_cuda):
+        raise ValueError("rx must be a contiguous CUDA float32 tensor [F, Ns, 2]")
+    con, m = _check_con(constellation, rx.device)
+    rx, F = _check_rm_rx(rm, rx, m, dev=True)
+    out = torch.empty((rm.N, F), dtype=torch.float32, device=rx.device)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(rx.device)).cuda_stream)
+    check(lib.bldpc_rm_qam_recover(rm._h, _dev_ptr(rx), _dev_ptr(con), int(con.shape[0]), ctypes.c_float(scale), il, F, ctypes.c_float(short_llr),
+                                   _dev_ptr(out), st), "RM_Demodulate_QAM_Recover")
+    return out
+
+
+def RM_Demodulate_QAM_Combine(rm, rx, constellation, scale, Channel_Acc, done=None, short_llr=1.0e4, stream=None, interleave=IL_NONE):
+    """bldpc_rm_qam_combine: RM_Combine(rm, Demodulate_QAM(rx, constellation, scale, rm.E, interleave=...), Channel_Acc, done, short_llr)
+    in one pass: Channel_Acc [N, F] is updated in place and returned; the columns of frames with done[f] != 0 keep their bits."""
+    il = _check_il(interleave)
+    _check_short_llr(short_llr)
+    _check_acc(rm, Channel_Acc)
+    F, dev = int(Channel_Acc.shape[1]), Channel_Acc.device
+    con, m = _check_con(constellation, dev)
+    rx, Frx = _check_rm_rx(rm, rx, m, dev=True)
+    if Frx != F or rx.device != dev:
+        raise ValueError("rx holds %d frames, Channel_Acc %d (both on %s)" % (Frx, F, dev))
+    _check_done(done, F, dev)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(dev)).cuda_stream)
+    check(lib.bldpc_rm_qam_combine(rm._h, _dev_ptr(rx), _dev_ptr(con), int(con.shape[0]), ctypes.c_float(scale), il, F, ctypes.c_float(short_llr),
+                                   _dev_ptr(done), _dev_ptr(Channel_Acc), st), "RM_Demodulate_QAM_Combine")
+    return Channel_Acc
+
+
+def RM_Modulate_QAM_host(rm, CodeWord, m, F=None, interleave=IL_NONE):
+    """bldpc_rm_qam_map_host: RM_Modulate_QAM on host arrays, no device needed.  -> int32 [F, ceil(E / m)]."""
+    if not 1 <= int(m) <= 8:
+        raise ValueError("m must be in 1..8")
+    il = _check_il(interleave)
+    if CodeWord is None:
+        if F is None or F <= 0:
+            raise ValueError("CodeWord=None (the all-zero word) needs a positive F")
+        cw = None
+    else:
+        cw = np.ascontiguousarray(CodeWord, np.int32)
+        if cw.ndim != 2 or cw.shape[0] != rm.N or cw.shape[1] <= 0:
+            raise ValueError("CodeWord must be [N=%d, F]" % rm.N)
+        F = cw.shape[1]
+    sym = np.empty((F, (rm.E + m - 1) // m), np.int32)
+    check(lib.bldpc_rm_qam_map_host(rm._h, None if cw is None else _np_ptr(cw), F, int(m), il, _np_ptr(sym)), "RM_Modulate_QAM_host")
+    return sym
+
+
+def RM_Demodulate_QAM_Recover_host(rm, rx, constellation, scale, short_llr=1.0e4, interleave=IL_NONE):
+    """bldpc_rm_qam_recover_host: RM_Demodulate_QAM_Recover on host arrays, no device needed.  -> float32 [N, F]."""
+    il = _check_il(interleave)
+    con, m = _check_con(constellation)
+    rx, F = _check_rm_rx(rm, rx, m)
+    out = np.empty((rm.N, F), np.float32)
+    check(lib.bldpc_rm_qam_recover_host(rm._h, _np_ptr(rx), _np_ptr(con), con.shape[0], ctypes.c_float(scale), il, F, ctypes.c_float(short_llr),
+                                        _np_ptr(out)), "RM_Demodulate_QAM_Recover_host")
+    return out
+
+
+def RM_Demodulate_QAM_Combine_host(rm, rx, constellation, scale, Channel_Acc, done=None, short_llr=1.0e4, interleave=IL_NONE):
+    """bldpc_rm_qam_combine_host: RM_Demodulate_QAM_Combine on host arrays; Channel_Acc float32 [N, F] (C-contiguous) is updated in place."""
+    il = _check_il(interleave)
+    acc, F = _host_acc(rm, Channel_Acc)
+    con, m = _check_con(constellation)
+    rx, Frx = _check_rm_rx(rm, rx, m)
+    if Frx != F:
+        raise ValueError("rx holds %d frames, Channel_Acc %d" % (Frx, F))
+    done = _host_done(done, F)
+    check(lib.bldpc_rm_qam_combine_host(rm._h, _np_ptr(rx), _np_ptr(con), con.shape[0], ctypes.c_float(scale), il, F, ctypes.c_float(short_llr),
+                                        None if done is None else _np_ptr(done), _np_ptr(acc)), "RM_Demodulate_QAM_Combine_host")
     return acc
 
 

@@ -283,6 +283,14 @@ int launch_awgn_circ(const bldpc_rm *rm, const int seed[3], float sigma, const i
 
 } // namespace
 
+int cldpc::rm_view(const bldpc_rm *rm, bool device, RmView *v)
+{
+    if (device)
+        if (int r = device_tables(rm)) return r;
+    *v = RmView{rm->N, rm->E, rm->Ncb, rm->k0, laps_of(rm), rm->n_short, rm->n_punct, rm->d_map, rm->d_tx};
+    return BLDPC_OK;
+}
+
 // ------------------------------------------------------------------------------------------------------------ profile
 // what bldpc_rm_create and bldpc_rm_create_circular share: the checks, map[] and the buffer (tx_pos ascending); `who` names the entry
 static int rm_build(const char *who, int N, const int *short_pos, int n_short, const int *punct_pos, int n_punct, bldpc_rm **out)

@@ -2,8 +2,18 @@
 #pragma once
 
 struct bldpc_code;
+struct bldpc_rm;
 
 namespace cldpc {
+
+// What bldpc_modem.hip reads of a profile for the fused modem calls ("rate matching over QAM" in include/bldpc.h).  d_map [N] and
+// d_tx [E] are the profile's device tables; they stay NULL unless rm_view was asked to upload them.
+struct RmView {
+    int N, E, Ncb, k0, laps, n_short, n_punct;
+    const int *d_map, *d_tx;
+};
+// bldpc_ratematch.hip: device = true uploads the tables on first use, as every device call on a profile does (BLDPC_ENOMEM / _EHIP)
+int rm_view(const bldpc_rm *rm, bool device, RmView *v);
 
 // The profile's one table, int [N]: the rank b >= 0 of a position in the buffer (the positions neither shortened nor punctured,
 // ascending; a linear profile transmits them in this order, so b is its e), or one of these.

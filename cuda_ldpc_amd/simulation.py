@@ -15,8 +15,9 @@ from . import sharding
 from ._lib import check, lib
 from .bldpc import (EXIT_BATCH_GLOBAL, EXIT_FIXED, EXIT_PER_FRAME, KERNEL_AUTO, STOP_PREFIX, STOP_SYNDROME, AWGNChannel_CPU, AWGNChannel_GPU,
                     AWGNChannel_QAM_GPU, AWGNChannel_RM_Combine_GPU, AWGNChannel_RM_GPU, Decode_Statistic, Demodulate_QAM, Frames_Gather,
-                    Frames_Scatter, LDPC_Decoder_BP_GPU, LDPC_Decoder_GPU, LDPC_Decoder_Layered_GPU, LDPC_Decoder_Quant_GPU, Modulate_QAM, PN_CodeWords,
-                    Quant, RM_Recover, RM_Select, SimCounters, Syndrome, _dev_ptr, sigma_of)
+                    Frames_Scatter, IL_NONE, IL_ROWCOL, LDPC_Decoder_BP_GPU, LDPC_Decoder_GPU, LDPC_Decoder_Layered_GPU, LDPC_Decoder_Quant_GPU,
+                    Modulate_QAM, PN_CodeWords, Quant, RM_Combine, RM_Demodulate_QAM_Recover, RM_Modulate_QAM, RM_Recover, SimCounters, Syndrome,
+                    _dev_ptr, sigma_of)
 from .nbldpc import sigma_of as nb_sigma_of
 
 
@@ -36,10 +37,46 @@ def _check_schedule(schedule, alpha, quant):
     return bp, layered
 
 
+def _check_qam(n_QAM, CONSTELLATION, PN_Message, interleave):
+    """The QAM arguments of a sweep, as Simulation_GPU and Simulation_HARQ_GPU both refuse them, before anything touches the device.
+    Returns (bits per symbol or 0 for BPSK, the constellation as a host float32 [n_QAM, 2] or None)."""
+    if interleave not in (IL_NONE, IL_ROWCOL):
+        raise ValueError("interleave must be IL_NONE (0) or IL_ROWCOL (1), not %r" % (interleave,))
+    if n_QAM == 2:
+        if CONSTELLATION is not None:
+            raise ValueError("CONSTELLATION belongs to n_QAM != 2")
+        if interleave != IL_NONE:
+            raise ValueError("interleave belongs to n_QAM != 2: the BPSK channel has one bit per symbol and nothing to interleave")
+        return 0, None
+    if PN_Message != 1:
+        raise ValueError("n_QAM=%r needs PN_Message=1: a QAM channel is not symmetric in the bits, so the all-zero word (always the "
+                         "same constellation point) is not representative of a random codeword" % (n_QAM,))
+    if CONSTELLATION is None:
+        raise ValueError("n_QAM=%r needs CONSTELLATION (float32 [n_QAM, 2], Get_CONSTELLATION)" % (n_QAM,))
+    con = np.ascontiguousarray(CONSTELLATION, np.float32)
+    if not isinstance(n_QAM, (int, np.integer)) or n_QAM < 2 or n_QAM > 256 or n_QAM & (n_QAM - 1) or con.shape != (n_QAM, 2):
+        raise ValueError("CONSTELLATION must be float32 [n_QAM, 2] with n_QAM a power of two in 2..256, not %s for n_QAM=%r"
+                         % (con.shape, n_QAM))
+    return int(n_QAM).bit_length() - 1, con
+
+
+def _qam_receive(rm, rx, con_dev, scale, short_llr, interleave, acc=None, done=None):
+    """The decoder input of one rate-matched transmission over QAM: recover (acc None) or combine into acc under done.  The fused
+    call and its two-call composition give the same bits; which one runs follows profiles/harq_qam_time.txt: the fused
+    recover is the faster one at one lap of the buffer (0.75 to 0.97 of the composition), everything else is not (a combine with no
+    whole wavefront of done frames 1.00 to 1.21, two laps 1.17 to 1.98)."""
+    if acc is None and rm.laps == 1:
+        return RM_Demodulate_QAM_Recover(rm, rx, con_dev, scale, short_llr, interleave=interleave)
+    llr = Demodulate_QAM(rx, con_dev, scale, rm.E, interleave=interleave)
+    if acc is None:
+        return RM_Recover(rm, llr, short_llr)
+    return RM_Combine(rm, llr, acc, done=done, short_llr=short_llr)
+
+
 def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, exit_mode=EXIT_BATCH_GLOBAL, kernel=KERNEL_AUTO,
                    leastErrorFrames=50, leastTestFrames=10000, displayStep=40960, dist=None, device=None, max_batches=None,
                    log=print, device_channel=False, PN_Message=0, pn_seed=0, schedule="flooding", alpha=1.0, stop_rule=None,
-                   n_QAM=2, CONSTELLATION=None, rate_match=None, short_llr=1.0e4, quant=None):
+                   n_QAM=2, CONSTELLATION=None, rate_match=None, short_llr=1.0e4, quant=None, interleave=IL_NONE):
     """One SNR point (Simulation.cu:12-171).  `seed` (int32[3]) is the AWGN->seed state, advanced in place by the
     WHOLE batch on every rank so that all ranks stay on the reference's single noise stream.
 
@@ -67,13 +104,16 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
     n_QAM != 2 sends the codewords over n_QAM-QAM instead of BPSK: CONSTELLATION (host float32 [n_QAM, 2], Get_CONSTELLATION) labels
     log2(n_QAM) consecutive codeword bits per point; a batch is encode -> Modulate_QAM -> AWGNChannel_QAM_GPU (four draws per symbol
     of the same noise stream) -> Demodulate_QAM with scale 1 / (2 sigma^2) -> the chosen decoder, and the caller passes the sigma of
-    that n_QAM (nbldpc.sigma_of).  Needs PN_Message=1 (a QAM channel is not symmetric) and device_channel=True.
+    that n_QAM (nbldpc.sigma_of).  Needs PN_Message=1 (a QAM channel is not symmetric) and device_channel=True.  interleave=IL_ROWCOL
+    puts the row-column bit interleaver between the bits and the points (the modem's index rule, include/bldpc.h); it belongs to
+    n_QAM != 2.
 
     rate_match (a RateMatch over code.N) simulates the shortened and punctured code: only its E transmitted bits go over the channel,
     2 E draws per frame (4 ceil(E / m) over QAM), and the decoder's input is short_llr on the shortened positions and +0.0 on the punctured
-    ones.  BPSK: the fused channel AWGNChannel_RM_GPU.  QAM: RM_Select -> Modulate_QAM with E bits -> channel -> Demodulate_QAM with E ->
-    RM_Recover.  Random codewords keep the shortened bits 0 (PN_CodeWords(rate_match=...)).  The decoder and Statistic calls, `length`
-    included, are those of the mother code: a shortened bit inside the prefix is 0 on both sides and adds no error; the printed BER divides
+    ones.  BPSK: the fused channel AWGNChannel_RM_GPU.  QAM: RM_Modulate_QAM -> channel -> RM_Demodulate_QAM_Recover, the bits of
+    RM_Select -> Modulate_QAM with E bits -> channel -> Demodulate_QAM with E -> RM_Recover without the two [E, F] arrays.  Random
+    codewords keep the shortened bits 0 (PN_CodeWords(rate_match=...)).  The decoder and Statistic calls, `length` included, are those of
+    the mother code: a shortened bit inside the prefix is 0 on both sides and adds no error; the printed BER divides
     by the prefix bits that are not shortened.  The caller passes the sigma of the derived rate, rate_match.rate(code.K).  Needs
     device_channel=True."""
     if PN_Message not in (0, 1):
@@ -95,22 +135,9 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
             raise ValueError("PN_Message=1 with per-frame exit needs stop_rule=STOP_SYNDROME: STOP_PREFIX tests for the all-zero word")
     elif PN_Message == 1 and exit_mode != EXIT_FIXED:
         raise ValueError("PN_Message=1 needs exit_mode=EXIT_FIXED: the decoders' early exit tests for the all-zero word")
-    qam_m = 0
-    if n_QAM != 2:  # every refusal before anything touches the device
-        if PN_Message != 1:
-            raise ValueError("n_QAM=%r needs PN_Message=1: a QAM channel is not symmetric in the bits, so the all-zero word (always the "
-                             "same constellation point) is not representative of a random codeword" % (n_QAM,))
-        if not device_channel:
-            raise ValueError("n_QAM != 2 needs device_channel=True: there is no host QAM channel on this path")
-        if CONSTELLATION is None:
-            raise ValueError("n_QAM=%r needs CONSTELLATION (float32 [n_QAM, 2], Get_CONSTELLATION)" % (n_QAM,))
-        con = np.ascontiguousarray(CONSTELLATION, np.float32)
-        if not isinstance(n_QAM, (int, np.integer)) or n_QAM < 2 or n_QAM > 256 or n_QAM & (n_QAM - 1) or con.shape != (n_QAM, 2):
-            raise ValueError("CONSTELLATION must be float32 [n_QAM, 2] with n_QAM a power of two in 2..256, not %s for n_QAM=%r"
-                             % (con.shape, n_QAM))
-        qam_m = int(n_QAM).bit_length() - 1
-    elif CONSTELLATION is not None:
-        raise ValueError("CONSTELLATION belongs to n_QAM != 2")
+    if n_QAM != 2 and PN_Message == 1 and not device_channel:  # every refusal before anything touches the device
+        raise ValueError("n_QAM != 2 needs device_channel=True: there is no host QAM channel on this path")
+    qam_m, con = _check_qam(n_QAM, CONSTELLATION, PN_Message, interleave)
     rm = rate_match
     if rm is not None:
         if not device_channel:
@@ -144,13 +171,13 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
         if not count:
             yd = None
         elif rm is not None and qam_m:  # the modem sees the E transmitted bits only
-            rx = AWGNChannel_QAM_GPU(my_seed, sigma, Modulate_QAM(RM_Select(rm, cw), rm.E, qam_m), con_dev)
-            yd = RM_Recover(rm, Demodulate_QAM(rx, con_dev, 1.0 / (2.0 * sigma * sigma), rm.E), short_llr)
+            rx = AWGNChannel_QAM_GPU(my_seed, sigma, RM_Modulate_QAM(rm, cw, qam_m, interleave=interleave), con_dev)
+            yd = _qam_receive(rm, rx, con_dev, 1.0 / (2.0 * sigma * sigma), short_llr, interleave)
         elif rm is not None:
             yd = AWGNChannel_RM_GPU(rm, my_seed, sigma, count, device=device, CodeWord=cw, short_llr=short_llr)
         elif qam_m:  # bits -> points -> noisy points -> max-log LLRs, all on the device
-            rx = AWGNChannel_QAM_GPU(my_seed, sigma, Modulate_QAM(cw, code.N, qam_m), con_dev)
-            yd = Demodulate_QAM(rx, con_dev, 1.0 / (2.0 * sigma * sigma), code.N)
+            rx = AWGNChannel_QAM_GPU(my_seed, sigma, Modulate_QAM(cw, code.N, qam_m, interleave=interleave), con_dev)
+            yd = Demodulate_QAM(rx, con_dev, 1.0 / (2.0 * sigma * sigma), code.N, interleave=interleave)
         elif device_channel:  # same draws, generated on the GPU (device libm in the Box-Muller transform)
             yd = AWGNChannel_GPU(my_seed, sigma, code.N, count, device=device, CodeWord=cw)
         else:
@@ -229,8 +256,9 @@ def format_harq_row(SIM, info_bits):
 
 def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, maxIT=50, exit_mode=EXIT_FIXED, kernel=KERNEL_AUTO,
                         leastErrorFrames=50, leastTestFrames=10000, dist=None, device=None, max_batches=None, log=print, PN_Message=0,
-                        pn_seed=0, schedule="flooding", alpha=1.0, stop_rule=None, short_llr=1.0e4, compact=True, keep_D=None, quant=None):
-    """One SNR point of incremental-redundancy HARQ over BPSK on the device channel.  rvs = [rm_0, ..., rm_{T-1}]: the profile of
+                        pn_seed=0, schedule="flooding", alpha=1.0, stop_rule=None, short_llr=1.0e4, compact=True, keep_D=None, quant=None,
+                        n_QAM=2, CONSTELLATION=None, interleave=IL_NONE):
+    """One SNR point of incremental-redundancy HARQ over BPSK, or over n_QAM-QAM, on the device channel.  rvs = [rm_0, ..., rm_{T-1}]: the profile of
     each transmission (RateMatch.circular or RateMatch, all over code.N with the same shortened positions).  SIM is a HarqCounters.
 
     A batch: rvs[0] is sent for all F frames (AWGNChannel_RM_GPU: recover semantics) and decoded; row N of D is the ACK.  For
@@ -251,7 +279,14 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
 
     Draws: transmission t of a batch owns 2 * E_t * F draws of the noise stream, used or not -- `seed` (int32[3]) is advanced by the
     sum over all T transmissions after every batch on every rank, whatever was acknowledged, and rank r jumps first_r * 2 * E_t draws
-    into each.  One all-reduce of the counters per batch.  keep_D (a list) receives this rank's final D of every batch."""
+    into each.  One all-reduce of the counters per batch.  keep_D (a list) receives this rank's final D of every batch.
+
+    n_QAM != 2 (with CONSTELLATION, host float32 [n_QAM, 2], and PN_Message=1, as for Simulation_GPU): transmission t is RM_Modulate_QAM ->
+    AWGNChannel_QAM_GPU -> the bits of RM_Demodulate_QAM_Recover (t = 0) or RM_Demodulate_QAM_Combine under done = D[N], with scale
+    1 / (2 sigma^2) and the index rule `interleave` (IL_ROWCOL: the row-column bit interleaver); the receive side runs the fused call or
+    Demodulate_QAM -> RM_Recover / RM_Combine, whichever was measured faster (_qam_receive).  It owns 4 * ceil(E_t / m) * F draws, and the channel draws
+    for acknowledged frames too: their points are made and never read.  The accumulated values are max-log LLRs already, so
+    schedule="bp" decodes with llr_scale = 1.0.  The caller passes the sigma of that n_QAM (nbldpc.sigma_of; sweep_harq does)."""
     if PN_Message not in (0, 1):
         raise ValueError("PN_Message must be 0 (all-zero codeword) or 1 (random codewords)")
     bp, layered = _check_schedule(schedule, alpha, quant)
@@ -269,6 +304,7 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
             raise ValueError("PN_Message=1 with per-frame exit needs stop_rule=STOP_SYNDROME: STOP_PREFIX tests for the all-zero word")
     elif PN_Message == 1 and exit_mode != EXIT_FIXED:
         raise ValueError("PN_Message=1 needs exit_mode=EXIT_FIXED: the flooding decoders' early exit tests for the all-zero word")
+    qam_m, con = _check_qam(n_QAM, CONSTELLATION, PN_Message, interleave)
     rvs = list(rvs) if rvs is not None else []
     if not rvs:
         raise ValueError("rvs must hold at least one profile")
@@ -295,13 +331,15 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
     N, K = code.N, code.K
     info_bits = K - rvs[0].n_short
     cnt = torch.zeros(2 * T + 3, dtype=torch.int64, device=device)  # acked[T], undetected[T], never, bits, iterations
+    con_dev = torch.from_numpy(con).to(device) if qam_m else None
+    llr_scale = 1.0 if qam_m else 2.0 / (sigma * sigma)  # schedule="bp": what makes the accumulated values true LLRs
+    qam_scale = 1.0 / (2.0 * sigma * sigma)
 
     def decode(y, D):
         """Decode y into D, leave the ACK in row N, return the iterations of every frame (int32 [F'])."""
         if layered:
             if bp:
-                r = LDPC_Decoder_BP_GPU(code, y, max_iter=maxIT, llr_scale=2.0 / (sigma * sigma), length=K, exit_mode=exit_mode, stop_rule=stop_rule,
-                                        D=D)
+                r = LDPC_Decoder_BP_GPU(code, y, max_iter=maxIT, llr_scale=llr_scale, length=K, exit_mode=exit_mode, stop_rule=stop_rule, D=D)
             elif quant is not None:
                 r = LDPC_Decoder_Quant_GPU(code, y, quant, max_iter=maxIT, length=K, exit_mode=exit_mode, stop_rule=stop_rule, D=D)
             else:
@@ -325,17 +363,25 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
             D = torch.empty((N + 1, count), dtype=torch.int32, device=device)
             acked = torch.zeros(count, dtype=torch.bool, device=device)
         for t, rm in enumerate(rvs):
-            per_frame = sharding.binary_draws_per_frame(rm.E)
+            per_frame = sharding.qam_draws_per_frame(rm.E, qam_m) if qam_m else sharding.binary_draws_per_frame(rm.E)
             my_seed = sharding.lcg_jump(seed, first * per_frame)
             seed[:] = sharding.lcg_jump(seed, F * per_frame)  # owned by this transmission whether it is used or not
             if not count or (t and bool(acked.all())):
                 continue
             active = ~acked
+            if qam_m:  # the points of every frame, acknowledged or not: the QAM channel has no done mask
+                rx = AWGNChannel_QAM_GPU(my_seed, sigma, RM_Modulate_QAM(rm, cw, qam_m, interleave=interleave), con_dev)
             if t == 0:
-                acc = AWGNChannel_RM_GPU(rm, my_seed, sigma, count, device=device, CodeWord=cw, short_llr=short_llr)
+                if qam_m:
+                    acc = _qam_receive(rm, rx, con_dev, qam_scale, short_llr, interleave)
+                else:
+                    acc = AWGNChannel_RM_GPU(rm, my_seed, sigma, count, device=device, CodeWord=cw, short_llr=short_llr)
                 iters = decode(acc, D)
             else:
-                AWGNChannel_RM_Combine_GPU(rm, my_seed, sigma, acc, done=D[N], CodeWord=cw, short_llr=short_llr)
+                if qam_m:
+                    _qam_receive(rm, rx, con_dev, qam_scale, short_llr, interleave, acc=acc, done=D[N])
+                else:
+                    AWGNChannel_RM_Combine_GPU(rm, my_seed, sigma, acc, done=D[N], CodeWord=cw, short_llr=short_llr)
                 if compact:
                     idx = torch.nonzero(active).view(-1).to(torch.int32)
                     Da = torch.empty((N + 1, idx.numel()), dtype=torch.int32, device=device)
@@ -373,17 +419,21 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
             return 1 if stop else 0
 
 
-def sweep_harq(code, rvs, startSNR=0.0, stopSNR=13.0, stepSNR=0.2, snrtype=1, seeds=(173, 173, 173), dist=None, log=print, **kw):
+def sweep_harq(code, rvs, startSNR=0.0, stopSNR=13.0, stepSNR=0.2, snrtype=1, seeds=(173, 173, 173), dist=None, log=print, n_QAM=2, **kw):
     """The sweep of `sweep` over Simulation_HARQ_GPU: a list of HarqCounters, one per SNR point.  Under Eb/N0 (snrtype 0) sigma comes
     from the rate of the FIRST transmission, rvs[0].rate(code.K): the operating point is named by what is sent when nothing goes wrong,
-    and the later transmissions run over the same channel."""
+    and the later transmissions run over the same channel.  With n_QAM != 2 (pass the constellation itself as CONSTELLATION=...) sigma
+    is the GF(q) program's at that rate, nbldpc_sigma(SNR, snrtype, n_QAM, rate), as in `sweep`."""
     out = []
     rate = rvs[0].rate(code.K)
+    if n_QAM != 2:
+        kw["n_QAM"] = n_QAM
     for snr in snr_grid(startSNR, stopSNR, stepSNR):
         seed = np.array(seeds, np.int32)
         SIM = HarqCounters()
         SIM.SNR = snr
-        Simulation_HARQ_GPU(code, seed, sigma_of(snr, snrtype, rate), SIM, rvs, dist=dist, log=log, **kw)
+        sigma = nb_sigma_of(snr, rate, snrtype, n_QAM) if n_QAM != 2 else sigma_of(snr, snrtype, rate)
+        Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, dist=dist, log=log, **kw)
         out.append(SIM)
     return out
 

@@ -408,7 +408,8 @@ int bldpc_decode_normalised_host(int J, int L, int Z, const int *H, const float 
  *   index: idx = sum_b bit[s*m + b] << b (only bit 0 of a CodeWord entry is read, as in bldpc_encode).  This is the order in which
  *   the GF(q) channels read a symbol's bits (nbldpc_awgn_channel_device[_qam]_frames); the shipped GRAY_*QAM.txt files are Gray in
  *   these index bits.  Positions n >= N of the last symbol are pad bits: they are sent as 0, the demapper writes nothing for them
- *   and makes no use of knowing them.  There is NO interleaver: neighbouring codeword bits share a symbol.
+ *   and makes no use of knowing them.  These two calls have NO interleaver: neighbouring codeword bits share a symbol.  The _il
+ *   calls below take the index rule as an argument.
  *
  *   map:    sym[f][s] = idx, int32 [F][Ns] -- what nbldpc_awgn_channel_device_qam_frames takes as CodeWord_sym with its N := Ns.
  *           CodeWord == NULL is the all-zero word: every index is 0.
@@ -435,9 +436,24 @@ int bldpc_decode_normalised_host(int J, int L, int Z, const int *H, const float 
  * Both calls are asynchronous on `stream` and allocate nothing.  BLDPC_EINVAL: a null pointer (but CodeWord), N or F <= 0, m
  * outside 1..8, q not a power of two in 2..256, scale not finite.
  * Out of scope: the exact log-sum-exp demapper (its expf / logf differ between device and host libm in the last ulp, which would end
- * bit-exact testing for a small gain under Gray labelling), bit interleavers, iterative demapping. */
+ * bit-exact testing for a small gain under Gray labelling), interleavers other than the row-column one below, iterative demapping. */
 int bldpc_qam_map(const int *CodeWord, int N, int F, int m, int *sym, void *stream);
 int bldpc_qam_demap(const float *rx, const float *constellation, int q, float scale, int N, int F, float *Channel_Out, void *stream);
+
+/* The bit interleaver, as an index rule inside the modem: which of the N bits is bit b of symbol s (Ns = ceil(N / m)).
+ *   BLDPC_IL_NONE    e = s*m + b    the rule of bldpc_qam_map / bldpc_qam_demap; the _il calls then give their bits
+ *   BLDPC_IL_ROWCOL  e = b*Ns + s   the row-column interleaver: the bits are written row by row into m rows of Ns and read column by
+ *                                   column, so that the m bits of a symbol lie Ns positions apart in the word
+ * In both rules e >= N is a pad bit: sent as 0, no output.  With N % m != 0 the pads of ROWCOL are the upper bits of the last
+ * symbols, one per symbol, not the tail of the last symbol; this keeps every N legal.  Index bit b keeps its meaning (bit b of the
+ * point index), and everything else is as said above, argument checks included; interleave outside {0, 1} is BLDPC_EINVAL. */
+#define BLDPC_IL_NONE 0
+#define BLDPC_IL_ROWCOL 1
+int bldpc_qam_map_il(const int *CodeWord, int N, int F, int m, int interleave, int *sym, void *stream);
+int bldpc_qam_demap_il(const float *rx, const float *constellation, int q, float scale, int N, int F, int interleave, float *Channel_Out,
+                       void *stream);
+int bldpc_qam_map_il_host(const int *CodeWord, int N, int F, int m, int interleave, int *sym);
+int bldpc_qam_demap_il_host(const float *rx, const float *constellation, int q, float scale, int N, int F, int interleave, float *Channel_Out);
 
 /* The same on host pointers, no device needed (and so no stream: they return when done): plain C++ that follows the steps above
  * literally.  They are the statement of the semantics inside the product, as bldpc_decode_layered_host is for the layered decoder,
@@ -474,8 +490,8 @@ int bldpc_qam_demap_host(const float *rx, const float *constellation, int q, flo
  *   rx           device float [E][F]                                                Channel_Out  device float [N][F]
  * All arrays frame-fastest.  The device calls are asynchronous on `stream` and allocate nothing per call (the profile's device
  * tables are uploaded by the first of them: use a profile from one host thread at a time, like a code object).
- * Out of scope: hard-decision (BSC) input, the position lists of any standard, HARQ over QAM in the sweep (the primitives compose
- * with bldpc_qam_demap through bldpc_rm_combine, see "HARQ" below), the GF(q) half. */
+ * Out of scope: hard-decision (BSC) input, the position lists of any standard, the GF(q) half.  (Rate matching and HARQ over QAM:
+ * "rate matching over QAM" below.) */
 typedef struct bldpc_rm bldpc_rm; /* opaque: the kind of every position, its rank among the transmitted ones, tx_pos; host + device */
 
 /* Positions are codeword positions in [0, N), in any order.  BLDPC_EINVAL: a position out of range, a position repeated or present
@@ -534,7 +550,7 @@ int bldpc_rm_encode_random(bldpc_code *code, const bldpc_rm *rm, unsigned long l
  *             bldpc_syndrome (or a decoder with BLDPC_STOP_SYNDROME) wrote the flag there.
  *             The first transmission of a codeword is recover, every later one is combine.  The same profile twice is Chase
  *             combining, profiles of different k0 are incremental redundancy.  rx may come from any source: with bldpc_qam_demap
- *             run at N := E on the selected bits, combine is HARQ over QAM.
+ *             run at N := E on the selected bits, combine is HARQ over QAM ("rate matching over QAM" below does it in one pass).
  *   channel:  bldpc_rm_awgn_channel_device / _host on a circular profile: sample (f, e) uses draws 2(f*E + e) and 2(f*E + e) + 1 in the
  *             arithmetic of bldpc_awgn_channel_device / _host, seed[3] advances by 2*E*F draws, the output is recover of those samples.
  *   channel + combine:  the same samples combined into Channel_Acc under done, ONE kernel, no [E][F] intermediate.  The draws of a done
@@ -562,6 +578,41 @@ int bldpc_rm_awgn_combine_device(const bldpc_rm *rm, int seed[3], float sigma, c
 int bldpc_rm_combine_host(const bldpc_rm *rm, const float *rx, int F, float short_llr, const int *done, float *Channel_Acc);
 int bldpc_rm_awgn_combine_host(const bldpc_rm *rm, int seed[3], float sigma, const int *CodeWord, int F, float short_llr, const int *done,
                                float *Channel_Acc);
+
+/* -- rate matching over QAM: select + interleave + map, and demap + de-interleave + recover / combine, one pass each -- */
+
+/* A rate-matched transmission over QAM sends the profile's E bits through the modem at N := E.  Each call below is, bit for bit, a
+ * composition of calls above, without the [E][F] array between them:
+ *
+ *   bldpc_rm_qam_map:      bldpc_rm_select into tx[E][F], then bldpc_qam_map_il(tx, E, F, m, interleave, sym).  Bit b of symbol s is
+ *                          read at CodeWord[tx_pos[e]][f], e by the index rule.  CodeWord == NULL is the all-zero word.
+ *   bldpc_rm_qam_recover:  bldpc_qam_demap_il(rx, ..., N := E, ..., tmp), then bldpc_rm_recover(rm, tmp, F, short_llr, Channel_Out).
+ *   bldpc_rm_qam_combine:  the same demap, then bldpc_rm_combine(rm, tmp, F, short_llr, done, Channel_Acc).
+ *
+ * with everything "rate matching" and "HARQ" say of recover and combine: a position's contributions are added in fp32 in ascending
+ * e, not contracted; recover starts from the first sample's bits; a position without a contribution is 0x00000000 (recover) or is
+ * not touched (combine); shortened positions are short_llr; a frame with done[f] != 0 keeps every bit of its column.  The three take
+ * linear and circular profiles.  On the device a profile of several laps is one launch of the demapper per lap, in stream order
+ * (launch l commits the bits l*Ncb <= e < (l+1)*Ncb, inside which no position comes twice; under BLDPC_IL_ROWCOL every launch walks
+ * all symbols); one lap is one launch, after one small launch that fills the rows the demapper does not reach when there are any.
+ * With scale = 1 / (2 sigma^2) the accumulated values are true max-log LLRs of the combined transmissions.
+ *
+ *   sym          device int32 [F][Ns], Ns = ceil(E / m)      rx   device float [F][Ns][2], as nbldpc_awgn_channel_device_qam_frames writes it
+ *   Channel_Out, Channel_Acc  device float [N][F]             done device int32 [F] or NULL       constellation device float [q][2]
+ * Asynchronous on `stream`, nothing allocated per call (the profile's tables are uploaded by its first device call).  BLDPC_EINVAL:
+ * what the modem calls and bldpc_rm_recover / bldpc_rm_combine refuse, and interleave outside {0, 1}; a refused call launches nothing.
+ * The _host twins ARE the compositions, on the host statements (bldpc_rm_select_host, bldpc_qam_map_il_host, bldpc_qam_demap_il_host,
+ * bldpc_rm_recover_host, bldpc_rm_combine_host); they allocate the [E][F] array (BLDPC_ENOMEM). */
+int bldpc_rm_qam_map(const bldpc_rm *rm, const int *CodeWord, int F, int m, int interleave, int *sym, void *stream);
+int bldpc_rm_qam_recover(const bldpc_rm *rm, const float *rx, const float *constellation, int q, float scale, int interleave, int F,
+                         float short_llr, float *Channel_Out, void *stream);
+int bldpc_rm_qam_combine(const bldpc_rm *rm, const float *rx, const float *constellation, int q, float scale, int interleave, int F,
+                         float short_llr, const int *done, float *Channel_Acc, void *stream);
+int bldpc_rm_qam_map_host(const bldpc_rm *rm, const int *CodeWord, int F, int m, int interleave, int *sym);
+int bldpc_rm_qam_recover_host(const bldpc_rm *rm, const float *rx, const float *constellation, int q, float scale, int interleave, int F,
+                              float short_llr, float *Channel_Out);
+int bldpc_rm_qam_combine_host(const bldpc_rm *rm, const float *rx, const float *constellation, int q, float scale, int interleave, int F,
+                              float short_llr, const int *done, float *Channel_Acc);
 
 /* Frame compaction: the columns idx[0] < idx[1] < ... < idx[Fa-1] of an array [rows][F] of 32-bit words of any meaning (a decoder's
  * float input, its int32 D with rows = N + 1, iters with rows = 1):

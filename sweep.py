@@ -4,6 +4,7 @@
     python sweep.py binary --matrix data/bldpc/J4_L24_Z96_BlockH.txt --J 4 --L 24 --Z 96 --start 0 --stop 4.4 --step 0.2
     python sweep.py nb     --start 0 --stop 5 --step 0.5
     python sweep.py binary --device-channel --layered --per-frame --pn-message --harq 0:2160,2160:144,500:2400 --start 2 --stop 3 --step 0.5
+    python sweep.py binary --device-channel --layered --per-frame --pn-message --qam 64 --interleave rowcol --snrtype 0 --harq 0:2160,2160:144,500:2400 --start 8 --stop 9 --step 0.5
     python sweep.py binary --device-channel --bp --per-frame --stop-rule syndrome --pn-message --start 2 --stop 3 --step 0.2
     python sweep.py binary --device-channel --quant 6,8,6 --norm8 6 --llr-scale 16 --per-frame --stop-rule syndrome --pn-message --start 2 --stop 3 --step 0.2
     python -m torch.distributed.run --nproc-per-node N sweep.py binary ...      (frames sharded over N GPUs)
@@ -66,6 +67,8 @@ def main():
     ap.add_argument("--qam", type=int, default=2, choices=[2, 64, 256],
                     help="n_QAM (define.h:25): 2 = BPSK, q = Constellation/GRAY_<q>QAM.txt; nb: one point per GF(q) symbol; binary: log2 q "
                          "codeword bits per point, max-log demapper, Eb/N0 as in the nb sweep (needs --pn-message --device-channel)")
+    ap.add_argument("--interleave", choices=["none", "rowcol"], default="none", help="binary --qam: the bit interleaver between the codeword (or "
+                    "the rate-matched bits) and the points: none = consecutive bits share a point, rowcol = the row-column interleaver")
     ap.add_argument("--nb-matrix", default="BDS.576.288.GF.64.txt", help="nb: matrix file (under data/nb or a path); q from its header")
     ap.add_argument("--method", type=int, default=0, choices=[0, 1, 2, 3], help="NB decoder_method (define.h:37): 0 EMS, 1 TMM, 2 log-QSPA, 3 layered TMM")
     ap.add_argument("--device-channel", action="store_true", help="generate the AWGN samples on the GPU (same RNG draws, device libm)")
@@ -90,7 +93,7 @@ def main():
                     "ranges a:b (information positions; needs --device-channel)")
     ap.add_argument("--puncture", metavar="SPEC", default=None, help="binary: codeword positions not sent, same SPEC (needs --device-channel)")
     ap.add_argument("--short-llr", type=float, default=1.0e4, help="--shorten: the decoder's input on a shortened position")
-    ap.add_argument("--harq", metavar="K0:E[,K0:E...]", default=None, help="binary: incremental-redundancy HARQ over BPSK, one circular-buffer "
+    ap.add_argument("--harq", metavar="K0:E[,K0:E...]", default=None, help="binary: incremental-redundancy HARQ over BPSK or --qam, one circular-buffer "
                     "transmission per K0:E (start in the buffer of the positions left by --shorten / --puncture, length; E above the buffer "
                     "repeats); only unacknowledged frames are sent and decoded again; --snrtype applies, sigma under Eb/N0 from the FIRST "
                     "transmission's rate (needs --device-channel and --fixed or --per-frame)")
@@ -98,14 +101,16 @@ def main():
     ap.add_argument("--no-compact", action="store_true", help="--harq: decode the whole batch after every transmission (timing and checking)")
     args = ap.parse_args()
     if args.harq is not None:
-        if args.which != "binary" or not args.device_channel or args.qam != 2 or args.as_written or not (args.fixed or args.per_frame):
-            ap.error("--harq belongs to the binary sweep over BPSK with --device-channel and --fixed or --per-frame")
+        if args.which != "binary" or not args.device_channel or args.as_written or not (args.fixed or args.per_frame):
+            ap.error("--harq belongs to the binary sweep with --device-channel and --fixed or --per-frame")
         try:
             harq = parse_harq(args.harq)
         except ValueError as e:
             ap.error(str(e))
     elif args.snrtype is not None or args.no_compact:
         ap.error("--snrtype and --no-compact belong to --harq")
+    if args.interleave != "none" and (args.which != "binary" or args.qam == 2):
+        ap.error("--interleave belongs to the binary sweep with --qam")
     if args.bp and (args.which != "binary" or args.layered or args.alpha != 1.0):
         ap.error("--bp belongs to the binary sweep, without --layered and without --alpha (sum-product has no normalisation factor)")
     quant = None
@@ -188,13 +193,16 @@ def main():
                     ap.error("--quant: %s" % e)
         mod = {}
         if args.qam != 2:  # the GF(q) half's constellation file and sigma (Eb/N0, n_QAM in the formula): the two sweeps share both
-            mod = dict(n_QAM=args.qam, CONSTELLATION=C.Get_CONSTELLATION(os.path.join(nbd, "Constellation", "GRAY_%dQAM.txt" % args.qam), args.qam))
+            mod = dict(n_QAM=args.qam, CONSTELLATION=C.Get_CONSTELLATION(os.path.join(nbd, "Constellation", "GRAY_%dQAM.txt" % args.qam), args.qam),
+                       interleave=C.IL_ROWCOL if args.interleave == "rowcol" else C.IL_NONE)
         if args.harq is not None:
             from cuda_ldpc_amd.simulation import sweep_harq
             rvs = [C.RateMatch.circular(code.N, shorten, puncture, k0, E) for k0, E in harq]
             if rank == 0:
-                print("# %s N=%d K=%d, HARQ over BPSK: buffer Ncb=%d (%d shortened, %d punctured), transmissions K0:E %s, first rate %.4f, %s, %s, "
-                      "maxIT=%d, batch=%d x %d GPU(s)%s" % (os.path.basename(args.matrix), code.N, code.K, rvs[0].Ncb, rvs[0].n_short, rvs[0].n_punct,
+                print("# %s N=%d K=%d, HARQ over %s: buffer Ncb=%d (%d shortened, %d punctured), transmissions K0:E %s, first rate %.4f, %s, %s, "
+                      "maxIT=%d, batch=%d x %d GPU(s)%s" % (os.path.basename(args.matrix), code.N, code.K,
+                                                          "BPSK" if args.qam == 2 else "%d-QAM (Gray), interleaver %s" % (args.qam, args.interleave),
+                                                          rvs[0].Ncb, rvs[0].n_short, rvs[0].n_punct,
                                                           args.harq, rvs[0].rate(code.K), "layered sum-product" if args.bp else
                                                           "quantised layered min-sum %r" % lay["quant"] if quant is not None else
                                                           "layered alpha=%g" % args.alpha if args.layered else
@@ -205,7 +213,7 @@ def main():
             sweep_harq(code, rvs, args.start, args.stop, args.step, snrtype=1 if args.snrtype is None else args.snrtype, dist=dist,
                        Num_Frames_OneTime=args.batch, maxIT=args.iters or (25 if rows else 50),
                        exit_mode=C.EXIT_FIXED if args.fixed else C.EXIT_PER_FRAME, max_batches=args.max_batches, PN_Message=1 if args.pn_message else 0,
-                       pn_seed=args.pn_seed, log=print if rank == 0 else None, short_llr=args.short_llr, compact=not args.no_compact, **lay)
+                       pn_seed=args.pn_seed, log=print if rank == 0 else None, short_llr=args.short_llr, compact=not args.no_compact, **lay, **mod)
             if world > 1:
                 dist.destroy_process_group()
             return
@@ -217,7 +225,8 @@ def main():
                     rm.n_short, rm.n_punct, rm.E, rm.rate(code.K)))
         if rank == 0:
             print("# %s N=%d K=%d, %s%s%s, maxIT=%d, batch=%d x %d GPU(s)%s" % (os.path.basename(args.matrix), code.N, code.K,
-                  "" if args.qam == 2 else "%d-QAM (Gray) %d bits per point, max-log demapper, Eb/N0, " % (args.qam, args.qam.bit_length() - 1),
+                  "" if args.qam == 2 else "%d-QAM (Gray) %d bits per point, interleaver %s, max-log demapper, Eb/N0, " % (
+                      args.qam, args.qam.bit_length() - 1, args.interleave),
                   "layered sum-product llr_scale=%s stop=%s, " % ("2/sigma^2" if args.qam == 2 else "1", stop) if args.bp else
                   "quantised layered min-sum %r stop=%s, " % (lay["quant"], stop) if quant is not None else
                   "layered min-sum alpha=%g stop=%s, " % (args.alpha, stop) if args.layered else
