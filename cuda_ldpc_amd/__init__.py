@@ -15,6 +15,8 @@ from .bldpc import (BinaryCode, Get_H, Transform_H, LDPC_Decoder_GPU, Decode_Sta
                     RM_Combine, AWGNChannel_RM_Combine_GPU, Frames_Gather, Frames_Scatter, RM_Combine_host, AWGNChannel_RM_Combine_CPU,
                     Frames_Gather_host, Frames_Scatter_host, RM_Modulate_QAM, RM_Demodulate_QAM_Recover, RM_Demodulate_QAM_Combine,
                     RM_Modulate_QAM_host, RM_Demodulate_QAM_Recover_host, RM_Demodulate_QAM_Combine_host, IL_NONE, IL_ROWCOL,
+                    Fading, QUASI_STATIC, Fading_Gains, Fading_Gains_host, AWGNChannel_Fading_GPU, AWGNChannel_Fading_CPU,
+                    AWGNChannel_QAM_Fading_GPU, AWGNChannel_QAM_Fading_CPU, Demodulate_QAM_Fading, Demodulate_QAM_Fading_host,
                     STOP_PREFIX, STOP_SYNDROME, EXIT_FIXED, EXIT_BATCH_GLOBAL, EXIT_PER_FRAME, KERNEL_AUTO, KERNEL_TABLE, KERNEL_QC_LDS)
 
 __all__ = ["BinaryCode", "Get_H", "Transform_H", "LDPC_Decoder_GPU", "Decode_Statistic", "Statistic", "SimCounters", "AWGNChannel_CPU", "AWGNChannel_GPU", "sigma_of",
@@ -25,5 +27,7 @@ __all__ = ["BinaryCode", "Get_H", "Transform_H", "LDPC_Decoder_GPU", "Decode_Sta
            "RM_Combine", "AWGNChannel_RM_Combine_GPU", "Frames_Gather", "Frames_Scatter", "RM_Combine_host", "AWGNChannel_RM_Combine_CPU",
            "Frames_Gather_host", "Frames_Scatter_host", "RM_Modulate_QAM", "RM_Demodulate_QAM_Recover", "RM_Demodulate_QAM_Combine",
            "RM_Modulate_QAM_host", "RM_Demodulate_QAM_Recover_host", "RM_Demodulate_QAM_Combine_host", "IL_NONE", "IL_ROWCOL",
+           "Fading", "QUASI_STATIC", "Fading_Gains", "Fading_Gains_host", "AWGNChannel_Fading_GPU", "AWGNChannel_Fading_CPU",
+           "AWGNChannel_QAM_Fading_GPU", "AWGNChannel_QAM_Fading_CPU", "Demodulate_QAM_Fading", "Demodulate_QAM_Fading_host",
            "STOP_PREFIX", "STOP_SYNDROME",
            "EXIT_FIXED", "EXIT_BATCH_GLOBAL", "EXIT_PER_FRAME", "KERNEL_AUTO", "KERNEL_TABLE", "KERNEL_QC_LDS"]

@@ -108,6 +108,17 @@ lib.bldpc_frames_gather.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int, c_v
 lib.bldpc_frames_scatter.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]
 lib.bldpc_frames_gather_host.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]
 lib.bldpc_frames_scatter_host.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]
+lib.bldpc_fading_gains_device.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
+lib.bldpc_fading_gains_host.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p]
+lib.bldpc_awgn_fading_channel_device.argtypes = [c_void_p, ctypes.c_float, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]
+lib.bldpc_awgn_fading_channel_host.argtypes = [c_void_p, ctypes.c_float, c_void_p, c_void_p, c_void_p, c_int, c_int]
+lib.bldpc_qam_demap_fading.argtypes = [c_void_p, c_void_p, c_void_p, c_int, ctypes.c_float, c_int, c_int, c_int, c_void_p, c_void_p]
+lib.bldpc_qam_demap_fading_host.argtypes = [c_void_p, c_void_p, c_void_p, c_int, ctypes.c_float, c_int, c_int, c_int, c_void_p]
+lib.nbldpc_fading_channel_device_qam_frames.argtypes = [c_void_p, ctypes.c_float, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]
+lib.nbldpc_fading_channel_host_qam_frames.argtypes = [c_void_p, ctypes.c_float, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]
+lib.nbldpc_demodulate_qam_fading.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_float, c_int, c_void_p, c_void_p]
+lib.nbldpc_demodulate_qam_fading_nq.argtypes = [c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.c_float, c_int, c_void_p, c_void_p]
+lib.nbldpc_demodulate_qam_fading_host.argtypes = [c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.c_float, c_int, c_void_p]
 lib.bldpc_sigma.restype = ctypes.c_float
 lib.bldpc_sigma.argtypes = [ctypes.c_float, c_int, ctypes.c_float]
 

@@ -692,6 +692,169 @@ def Demodulate_QAM_host(rx, constellation, scale, N, interleave=IL_NONE):
     return out
 
 
+QUASI_STATIC = 1 << 30  # a block length above every frame length: one gain per frame and transmission
+
+_LCG_M = (61967, 63443, 63599)
+
+
+class Fading:
+    """Flat Rayleigh block fading with receiver CSI (include/bldpc.h, "block fading") as the sweeps take it: gains constant over blocks
+    of Lc channel uses (1: fast fading; QUASI_STATIC, or anything not below the frame's channel uses: one gain per frame and
+    transmission), drawn from a RandomModule stream of their own.  `seed` is kept as an int32 array of 3 that the sweeps advance in
+    place like the noise seed.  A value class: check() is what the sweeps refuse it by, before anything touches the device."""
+
+    def __init__(self, Lc, seed=(4711, 4712, 4713)):
+        self.Lc = Lc
+        self.seed = seed if isinstance(seed, np.ndarray) and seed.dtype == np.int32 else np.array(seed, np.int32)
+
+    def check(self):
+        if isinstance(self.Lc, bool) or not isinstance(self.Lc, (int, np.integer)) or self.Lc < 1:
+            raise ValueError("fading.Lc must be an integer >= 1 (QUASI_STATIC for one gain per frame), not %r" % (self.Lc,))
+        if self.seed.shape != (3,) or not all(0 <= int(self.seed[i]) < _LCG_M[i] for i in range(3)):
+            raise ValueError("fading.seed must be three ints with 0 <= seed[i] < %s, not %s" % (list(_LCG_M), self.seed.tolist()))
+
+    def __repr__(self):
+        return "Fading(Lc=%r, seed=%s)" % (self.Lc, self.seed.tolist())
+
+
+def _check_seed(seed):
+    if not (isinstance(seed, np.ndarray) and seed.dtype == np.int32 and seed.size == 3):
+        raise ValueError("seed must be an int32 numpy array of 3")
+
+
+def _check_gain(gain, F, S, dev=None):
+    """gain [F, S] float32: a contiguous CUDA tensor on `dev`, or (dev None) anything numpy reads."""
+    if dev is None:
+        g = np.ascontiguousarray(gain, np.float32)
+        if g.shape != (F, S):
+            raise ValueError("gain must be float32 [F=%d, S=%d], not %s" % (F, S, g.shape))
+        return g
+    if not (torch.is_tensor(gain) and gain.is_cuda and gain.device == dev and gain.dtype == torch.float32 and gain.is_contiguous()
+            and tuple(gain.shape) == (F, S)):
+        raise ValueError("gain must be a contiguous CUDA float32 tensor [F=%d, S=%d] on %s" % (F, S, dev))
+    return gain
+
+
+def Fading_Gains(seed, Lc, S, F, device=None, stream=None):
+    """bldpc_fading_gains_device: the gains of F frames of S channel uses, constant over blocks of Lc uses, a = sqrt(-log(1 - u)) with u
+    draw f * nb + j (nb = ceil(S / Lc)) of the stream at `seed` (int32[3], advanced by nb * F draws).  -> CUDA float32 [F, S]."""
+    _check_seed(seed)
+    if Lc < 1 or S <= 0 or F <= 0:
+        raise ValueError("Fading_Gains needs Lc >= 1 and positive S and F")
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    gain = torch.empty((F, S), dtype=torch.float32, device=device)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(device)).cuda_stream)
+    check(lib.bldpc_fading_gains_device(_np_ptr(seed), int(Lc), int(S), int(F), _dev_ptr(gain), st), "Fading_Gains")
+    return gain
+
+
+def Fading_Gains_host(seed, Lc, S, F):
+    """bldpc_fading_gains_host: Fading_Gains on the host (host libm), the statement of the semantics.  -> float32 [F, S]."""
+    _check_seed(seed)
+    if Lc < 1 or S <= 0 or F <= 0:
+        raise ValueError("Fading_Gains_host needs Lc >= 1 and positive S and F")
+    gain = np.empty((F, S), np.float32)
+    check(lib.bldpc_fading_gains_host(_np_ptr(seed), int(Lc), int(S), int(F), _np_ptr(gain)), "Fading_Gains_host")
+    return gain
+
+
+def AWGNChannel_Fading_GPU(seed, sigma, gain, N, F, CodeWord=None, stream=None):
+    """bldpc_awgn_fading_channel_device: the draws of AWGNChannel_GPU, r = a (1 - 2c) + noise, and the matched-filter value a * r as the
+    decoder's input (2 / sigma^2 stays the sum-product llr_scale).  gain CUDA float32 [F, N] -> CUDA float32 [N, F]; seed advanced."""
+    _check_seed(seed)
+    if not torch.is_tensor(gain):
+        raise ValueError("gain must be a contiguous CUDA float32 tensor [F=%d, N=%d]" % (F, N))
+    _check_gain(gain, F, N, gain.device)
+    if CodeWord is not None:
+        _check_cw(CodeWord, N, F, gain.device)
+    out = torch.empty((N, F), dtype=torch.float32, device=gain.device)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(gain.device)).cuda_stream)
+    check(lib.bldpc_awgn_fading_channel_device(_np_ptr(seed), ctypes.c_float(sigma), _dev_ptr(gain), _dev_ptr(out), _dev_ptr(CodeWord), N, F, st),
+          "AWGNChannel_Fading_GPU")
+    return out
+
+
+def AWGNChannel_Fading_CPU(seed, sigma, gain, N, F, CodeWord=None):
+    """bldpc_awgn_fading_channel_host: AWGNChannel_Fading_GPU on host arrays (host libm).  -> float32 [N, F]."""
+    _check_seed(seed)
+    g = _check_gain(gain, F, N)
+    cw = None if CodeWord is None else np.ascontiguousarray(CodeWord, np.int32)
+    if cw is not None and cw.shape != (N, F):
+        raise ValueError("CodeWord must be [N=%d, F=%d]" % (N, F))
+    out = np.empty((N, F), np.float32)
+    check(lib.bldpc_awgn_fading_channel_host(_np_ptr(seed), ctypes.c_float(sigma), _np_ptr(g), _np_ptr(out), None if cw is None else _np_ptr(cw),
+                                             N, F), "AWGNChannel_Fading_CPU")
+    return out
+
+
+def AWGNChannel_QAM_Fading_GPU(seed, sigma, sym, constellation, gain, stream=None):
+    """nbldpc_fading_channel_device_qam_frames: AWGNChannel_QAM_GPU with the point of symbol (f, s) scaled by gain[f, s] before the noise
+    is added.  sym CUDA int32 [F, Ns], gain CUDA float32 [F, Ns] -> rx CUDA float32 [F, Ns, 2]; the same draws and seed advance."""
+    _check_seed(seed)
+    if not (torch.is_tensor(sym) and sym.is_cuda and sym.dtype == torch.int32 and sym.is_contiguous() and sym.dim() == 2 and sym.numel() > 0):
+        raise ValueError("sym must be a contiguous CUDA int32 tensor [F, Ns]")
+    con, _ = _check_con(constellation, sym.device)
+    F, Ns = (int(x) for x in sym.shape)
+    _check_gain(gain, F, Ns, sym.device)
+    rx = torch.empty((F, Ns, 2), dtype=torch.float32, device=sym.device)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(sym.device)).cuda_stream)
+    rc = lib.nbldpc_fading_channel_device_qam_frames(_np_ptr(seed), ctypes.c_float(sigma), _dev_ptr(sym), Ns, _dev_ptr(con), int(con.shape[0]),
+                                                     _dev_ptr(gain), F, _dev_ptr(rx), st)
+    if rc != 0:
+        raise LdpcError("AWGNChannel_QAM_Fading_GPU failed (%d): %s" % (rc, lib.nbldpc_last_error().decode(errors="replace")))
+    return rx
+
+
+def AWGNChannel_QAM_Fading_CPU(seed, sigma, sym, constellation, gain):
+    """nbldpc_fading_channel_host_qam_frames: AWGNChannel_QAM_Fading_GPU on host arrays (host libm).  -> float32 [F, Ns, 2]."""
+    _check_seed(seed)
+    sym = np.ascontiguousarray(sym, np.int32)
+    if sym.ndim != 2 or sym.size == 0:
+        raise ValueError("sym must be int32 [F, Ns]")
+    con, _ = _check_con(constellation)
+    F, Ns = sym.shape
+    g = _check_gain(gain, F, Ns)
+    rx = np.empty((F, Ns, 2), np.float32)
+    rc = lib.nbldpc_fading_channel_host_qam_frames(_np_ptr(seed), ctypes.c_float(sigma), _np_ptr(sym), Ns, _np_ptr(con), con.shape[0], _np_ptr(g), F,
+                                                   _np_ptr(rx))
+    if rc != 0:
+        raise LdpcError("AWGNChannel_QAM_Fading_CPU failed (%d): %s" % (rc, lib.nbldpc_last_error().decode(errors="replace")))
+    return rx
+
+
+def Demodulate_QAM_Fading(rx, gain, constellation, scale, N, stream=None, interleave=IL_NONE):
+    """bldpc_qam_demap_fading: Demodulate_QAM with the distances taken to the faded points a * c_p, a = gain[f, s] (CUDA float32 [F, Ns],
+    aligned with rx [F, Ns, 2]).  A gain of 0 gives +0.0 on all bits of its symbol (an erasure), a gain of 1 the bits of Demodulate_QAM."""
+    il = _check_il(interleave)
+    if not (torch.is_tensor(rx) and rx.is_cuda and rx.dtype == torch.float32 and rx.is_contiguous() and rx.dim() == 3 and rx.shape[2] == 2):
+        raise ValueError("rx must be a contiguous CUDA float32 tensor [F, Ns, 2]")
+    con, m = _check_con(constellation, rx.device)
+    F = int(rx.shape[0])
+    if N <= 0 or F <= 0 or rx.shape[1] != (N + m - 1) // m:
+        raise ValueError("rx must hold ceil(N / m) = %d symbols per frame, not %d" % ((N + m - 1) // m, rx.shape[1]))
+    _check_gain(gain, F, int(rx.shape[1]), rx.device)
+    out = torch.empty((N, F), dtype=torch.float32, device=rx.device)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(rx.device)).cuda_stream)
+    check(lib.bldpc_qam_demap_fading(_dev_ptr(rx), _dev_ptr(gain), _dev_ptr(con), int(con.shape[0]), ctypes.c_float(scale), N, F, il, _dev_ptr(out), st),
+          "Demodulate_QAM_Fading")
+    return out
+
+
+def Demodulate_QAM_Fading_host(rx, gain, constellation, scale, N, interleave=IL_NONE):
+    """bldpc_qam_demap_fading_host: Demodulate_QAM_Fading on host arrays, no device needed.  -> float32 [N, F]."""
+    il = _check_il(interleave)
+    con, m = _check_con(constellation)
+    rx = np.ascontiguousarray(rx, np.float32)
+    if N <= 0 or rx.ndim != 3 or rx.shape[0] <= 0 or rx.shape[1] != (N + m - 1) // m or rx.shape[2] != 2:
+        raise ValueError("rx must be float32 [F, ceil(N / m) = %d, 2]" % ((N + m - 1) // m))
+    F = rx.shape[0]
+    g = _check_gain(gain, F, rx.shape[1])
+    out = np.empty((N, F), np.float32)
+    check(lib.bldpc_qam_demap_fading_host(_np_ptr(rx), _np_ptr(g), _np_ptr(con), con.shape[0], ctypes.c_float(scale), N, F, il, _np_ptr(out)),
+          "Demodulate_QAM_Fading_host")
+    return out
+
+
 class RateMatch:
     """A shortening / puncturing profile over a mother code of N bits (bldpc_rm, semantics in include/bldpc.h).  shorten, puncture:
     codeword positions in [0, N), in any order, disjoint and without repeats.  E = N - n_short - n_punct bits are transmitted, in

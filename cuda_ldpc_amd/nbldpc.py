@@ -223,6 +223,63 @@ def Demodulate(code, rx, sigma, stream=None, CONSTELLATION=None):
     return Lch
 
 
+def _check_qam_fading(code, rx, gain, CONSTELLATION):
+    if not (torch.is_tensor(rx) and rx.is_cuda and rx.dtype == torch.float32 and rx.is_contiguous() and rx.dim() == 3
+            and tuple(rx.shape[1:]) == (code.N, 2) and rx.shape[0] > 0):
+        raise ValueError("rx must be a contiguous CUDA float32 tensor [B, N, 2]")
+    if not (torch.is_tensor(CONSTELLATION) and CONSTELLATION.is_cuda and CONSTELLATION.dtype == torch.float32 and CONSTELLATION.is_contiguous()
+            and tuple(CONSTELLATION.shape) == (code.q, 2)):
+        raise ValueError("CONSTELLATION must be a contiguous CUDA float32 tensor [q, 2]")
+    if not (torch.is_tensor(gain) and gain.is_cuda and gain.device == rx.device and gain.dtype == torch.float32 and gain.is_contiguous()
+            and tuple(gain.shape) == (int(rx.shape[0]), code.N)):
+        raise ValueError("gain must be a contiguous CUDA float32 tensor [B=%d, N=%d] on %s" % (rx.shape[0], code.N, rx.device))
+
+
+def Demodulate_QAM_Fading(code, rx, gain, sigma, CONSTELLATION, stream=None):
+    """nbldpc_demodulate_qam_fading: the n_QAM != 2 branch of Demodulate against the faded points gain[b, s] * c_k (receiver CSI).
+    rx CUDA float32 [B, N, 2], gain CUDA float32 [B, N], CONSTELLATION CUDA float32 [q, 2] -> L_ch [B, N, q-1]; a gain of 1 gives
+    Demodulate's bits."""
+    _check_qam_fading(code, rx, gain, CONSTELLATION)
+    B = int(rx.shape[0])
+    Lch = torch.empty((B, code.N, code.q - 1), dtype=torch.float32, device=rx.device)
+    st = c_void_p((stream or torch.cuda.current_stream(rx.device)).cuda_stream)
+    _check(lib.nbldpc_demodulate_qam_fading(code._h, _dev(rx), _dev(gain), _dev(CONSTELLATION), c_float(sigma), B, _dev(Lch), st),
+           "Demodulate_QAM_Fading")
+    return Lch
+
+
+def Demodulate_QAM_Fading_host(N, q, rx, gain, CONSTELLATION, sigma):
+    """nbldpc_demodulate_qam_fading_host: the statement of Demodulate_QAM_Fading on host arrays.  rx [B, N, 2], gain [B, N] -> [B, N, q-1]."""
+    rx = np.ascontiguousarray(rx, np.float32)
+    con = np.ascontiguousarray(CONSTELLATION, np.float32)
+    if rx.ndim != 3 or rx.shape[0] <= 0 or tuple(rx.shape[1:]) != (N, 2) or con.shape != (q, 2):
+        raise ValueError("rx must be float32 [B, N=%d, 2] and CONSTELLATION float32 [q=%d, 2]" % (N, q))
+    g = np.ascontiguousarray(gain, np.float32)
+    if g.shape != rx.shape[:2]:
+        raise ValueError("gain must be float32 [B, N]")
+    Lch = np.empty((rx.shape[0], N, q - 1), np.float32)
+    _check(lib.nbldpc_demodulate_qam_fading_host(N, q, _np(rx), _np(g), _np(con), c_float(sigma), rx.shape[0], _np(Lch)), "Demodulate_QAM_Fading_host")
+    return Lch
+
+
+def AWGNChannel_Fading_GPU(seed, sigma, code, CodeWord_sym_dev, gain, CONSTELLATION, stream=None):
+    """nbldpc_fading_channel_device_qam_frames for a GF(q) code over q-QAM: frame b sends row b of CodeWord_sym_dev (CUDA int32 [B, N]),
+    the point of symbol (b, i) scaled by gain[b, i] (CUDA float32 [B, N]) before the noise of AWGNChannel_GPU's per-frame QAM form is
+    added: the same four draws per symbol, the same seed advance.  Returns rx CUDA float32 [B, N, 2]."""
+    if not (isinstance(seed, np.ndarray) and seed.dtype == np.int32 and seed.size == 3):
+        raise ValueError("seed must be an int32 numpy array of 3")
+    if not (torch.is_tensor(CodeWord_sym_dev) and CodeWord_sym_dev.is_cuda and CodeWord_sym_dev.dtype == torch.int32 and CodeWord_sym_dev.is_contiguous()
+            and CodeWord_sym_dev.dim() == 2 and CodeWord_sym_dev.shape[1] == code.N and CodeWord_sym_dev.shape[0] > 0):
+        raise ValueError("CodeWord_sym_dev must be a contiguous CUDA int32 tensor [B, N=%d]" % code.N)
+    B = int(CodeWord_sym_dev.shape[0])
+    rx = torch.empty((B, code.N, 2), dtype=torch.float32, device=CodeWord_sym_dev.device)
+    _check_qam_fading(code, rx, gain, CONSTELLATION)
+    st = c_void_p((stream or torch.cuda.current_stream(rx.device)).cuda_stream)
+    _check(lib.nbldpc_fading_channel_device_qam_frames(_np(seed), c_float(sigma), _dev(CodeWord_sym_dev), code.N, _dev(CONSTELLATION), code.q,
+                                                       _dev(gain), B, _dev(rx), st), "AWGNChannel_Fading_GPU")
+    return rx
+
+
 def AWGNChannel_CPU(seed, sigma, code, CodeWord_sym, CONSTELLATION=None):
     """Modulate + AWGNChannel_CPU (LDPC_Encoder.cpp:18-68) for ONE frame; seed advanced.  BPSK -> host rx [N*m]; with
     CONSTELLATION (host float32 [q, 2]) the n_QAM != 2 branch -> host rx [N, 2]."""

@@ -41,6 +41,19 @@ def qam_draws_per_frame(N, m):
     return 4 * ((N + m - 1) // m)  # a binary codeword over 2^m-QAM: ceil(N/m) symbols, Real and Image part, two draws each
 
 
+def fading_uses(bits, m):
+    """Channel uses of a frame of `bits` transmitted bits: the bits themselves over BPSK (m = 0), ceil(bits / m) points over 2^m-QAM."""
+    return (bits + m - 1) // m if m else bits
+
+
+def fading_draws_per_frame(S, Lc):
+    """Draws of the FADING stream one frame of S channel uses owns: one per block of Lc uses, ceil(S / Lc) (bldpc_fading_gains_device).
+    The fading stream has its own seed; ranks jump it by first_frame * this, as they jump the noise seed."""
+    if Lc < 1 or S < 1:
+        raise ValueError("fading_draws_per_frame needs S >= 1 and Lc >= 1")
+    return (S + Lc - 1) // Lc
+
+
 def allreduce_counters(counters, dist=None):
     """Sum an int64 counter tensor over all ranks (no-op without a process group). Returns the tensor.
     A caller that passes an initialised process group gets the collective at every world size, 1 included (40 bytes: the

@@ -13,11 +13,11 @@ import torch
 
 from . import sharding
 from ._lib import check, lib
-from .bldpc import (EXIT_BATCH_GLOBAL, EXIT_FIXED, EXIT_PER_FRAME, KERNEL_AUTO, STOP_PREFIX, STOP_SYNDROME, AWGNChannel_CPU, AWGNChannel_GPU,
-                    AWGNChannel_QAM_GPU, AWGNChannel_RM_Combine_GPU, AWGNChannel_RM_GPU, Decode_Statistic, Demodulate_QAM, Frames_Gather,
-                    Frames_Scatter, IL_NONE, IL_ROWCOL, LDPC_Decoder_BP_GPU, LDPC_Decoder_GPU, LDPC_Decoder_Layered_GPU, LDPC_Decoder_Quant_GPU,
-                    Modulate_QAM, PN_CodeWords, Quant, RM_Combine, RM_Demodulate_QAM_Recover, RM_Modulate_QAM, RM_Recover, SimCounters, Syndrome,
-                    _dev_ptr, sigma_of)
+from .bldpc import (EXIT_BATCH_GLOBAL, EXIT_FIXED, EXIT_PER_FRAME, KERNEL_AUTO, STOP_PREFIX, STOP_SYNDROME, AWGNChannel_CPU, AWGNChannel_Fading_GPU,
+                    AWGNChannel_GPU, AWGNChannel_QAM_Fading_GPU, AWGNChannel_QAM_GPU, AWGNChannel_RM_Combine_GPU, AWGNChannel_RM_GPU,
+                    Decode_Statistic, Demodulate_QAM, Demodulate_QAM_Fading, Fading, Fading_Gains, Frames_Gather, Frames_Scatter, IL_NONE, IL_ROWCOL,
+                    LDPC_Decoder_BP_GPU, LDPC_Decoder_GPU, LDPC_Decoder_Layered_GPU, LDPC_Decoder_Quant_GPU, Modulate_QAM, PN_CodeWords, Quant,
+                    RM_Combine, RM_Demodulate_QAM_Recover, RM_Modulate_QAM, RM_Recover, RM_Select, SimCounters, Syndrome, _dev_ptr, sigma_of)
 from .nbldpc import sigma_of as nb_sigma_of
 
 
@@ -60,6 +60,39 @@ def _check_qam(n_QAM, CONSTELLATION, PN_Message, interleave):
     return int(n_QAM).bit_length() - 1, con
 
 
+def _check_fading(fading, device_channel, exit_mode):
+    """The fading argument of a sweep, as the three drivers refuse it before anything touches the device."""
+    if fading is None:
+        return
+    if not isinstance(fading, Fading):
+        raise ValueError("fading must be a Fading (block length and the seed of the fading stream), not %r" % (fading,))
+    if not device_channel:
+        raise ValueError("fading needs device_channel=True: the gains and the channels that apply them run on the device")
+    if exit_mode == EXIT_BATCH_GLOBAL:
+        raise ValueError("fading takes EXIT_FIXED or EXIT_PER_FRAME: the results of EXIT_BATCH_GLOBAL depend on the batch")
+    fading.check()
+
+
+def _fading_gains(fading, S, F, first, count, device):
+    """The gains of this rank's `count` frames (global frames first .. first + count - 1 of a batch of F) for one transmission of S
+    channel uses, CUDA float32 [count, S] (None without frames), and the fading seed advanced by the WHOLE batch, as the noise seed is."""
+    per_frame = sharding.fading_draws_per_frame(S, fading.Lc)
+    my_seed = sharding.lcg_jump(fading.seed, first * per_frame)
+    fading.seed[:] = sharding.lcg_jump(fading.seed, F * per_frame)
+    return Fading_Gains(my_seed, fading.Lc, S, count, device=device) if count else None
+
+
+def _fading_transmit(fading_gain, my_seed, sigma, cw, n_bits, count, qam_m, con_dev, interleave, rm=None):
+    """One transmission over the fading channel as the composition include/bldpc.h names: the matched-filter values (BPSK) or max-log
+    values with CSI (QAM) of the n_bits transmitted bits, CUDA float32 [n_bits, count].  rm: the profile that selects them from cw."""
+    if qam_m:
+        sym = RM_Modulate_QAM(rm, cw, qam_m, interleave=interleave) if rm is not None else Modulate_QAM(cw, n_bits, qam_m, interleave=interleave)
+        rx = AWGNChannel_QAM_Fading_GPU(my_seed, sigma, sym, con_dev, fading_gain)
+        return Demodulate_QAM_Fading(rx, fading_gain, con_dev, 1.0 / (2.0 * sigma * sigma), n_bits, interleave=interleave)
+    tx = RM_Select(rm, cw) if (rm is not None and cw is not None) else cw
+    return AWGNChannel_Fading_GPU(my_seed, sigma, fading_gain, n_bits, count, CodeWord=tx)
+
+
 def _qam_receive(rm, rx, con_dev, scale, short_llr, interleave, acc=None, done=None):
     """The decoder input of one rate-matched transmission over QAM: recover (acc None) or combine into acc under done.  The fused
     call and its two-call composition give the same bits; which one runs follows profiles/harq_qam_time.txt: the fused
@@ -76,7 +109,7 @@ def _qam_receive(rm, rx, con_dev, scale, short_llr, interleave, acc=None, done=N
 def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, exit_mode=EXIT_BATCH_GLOBAL, kernel=KERNEL_AUTO,
                    leastErrorFrames=50, leastTestFrames=10000, displayStep=40960, dist=None, device=None, max_batches=None,
                    log=print, device_channel=False, PN_Message=0, pn_seed=0, schedule="flooding", alpha=1.0, stop_rule=None,
-                   n_QAM=2, CONSTELLATION=None, rate_match=None, short_llr=1.0e4, quant=None, interleave=IL_NONE):
+                   n_QAM=2, CONSTELLATION=None, rate_match=None, short_llr=1.0e4, quant=None, interleave=IL_NONE, fading=None):
     """One SNR point (Simulation.cu:12-171).  `seed` (int32[3]) is the AWGN->seed state, advanced in place by the
     WHOLE batch on every rank so that all ranks stay on the reference's single noise stream.
 
@@ -115,7 +148,16 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
     codewords keep the shortened bits 0 (PN_CodeWords(rate_match=...)).  The decoder and Statistic calls, `length` included, are those of
     the mother code: a shortened bit inside the prefix is 0 on both sides and adds no error; the printed BER divides
     by the prefix bits that are not shortened.  The caller passes the sigma of the derived rate, rate_match.rate(code.K).  Needs
-    device_channel=True."""
+    device_channel=True.
+
+    fading (a Fading) puts flat Rayleigh block fading with receiver CSI on the channel (include/bldpc.h, "block fading"): every batch
+    draws the gains of its S channel uses per frame (S = the transmitted bits over BPSK, ceil(bits / m) points over QAM) from the fading
+    stream, fading.seed, which is advanced in place by the whole batch on every rank, ceil(S / Lc) draws per frame, while the noise
+    stream and its draws stay what they are without fading.  BPSK: AWGNChannel_Fading_GPU (a * r, so that 2 / sigma^2 stays the
+    sum-product scale); QAM: AWGNChannel_QAM_Fading_GPU -> Demodulate_QAM_Fading; with rate_match the compositions RM_Select ->
+    channel at E -> RM_Recover and RM_Modulate_QAM -> channel -> Demodulate_QAM_Fading at E -> RM_Recover.  E[a^2] = 1, so the caller
+    passes the sigma of the AWGN sweep.  Needs device_channel=True and EXIT_FIXED or EXIT_PER_FRAME; fading=None is the AWGN sweep,
+    call for call."""
     if PN_Message not in (0, 1):
         raise ValueError("PN_Message must be 0 (all-zero codeword) or 1 (random codewords)")
     bp, layered = _check_schedule(schedule, alpha, quant)
@@ -138,6 +180,7 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
     if n_QAM != 2 and PN_Message == 1 and not device_channel:  # every refusal before anything touches the device
         raise ValueError("n_QAM != 2 needs device_channel=True: there is no host QAM channel on this path")
     qam_m, con = _check_qam(n_QAM, CONSTELLATION, PN_Message, interleave)
+    _check_fading(fading, device_channel, exit_mode)
     rm = rate_match
     if rm is not None:
         if not device_channel:
@@ -168,8 +211,14 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
         SIM.num_Frames += F  # Simulation.cu:113
         my_seed = sharding.lcg_jump(seed, first * per_frame)
         cw = PN_CodeWords(code, pn_seed, count, first_frame=batches * F + first, device=device, rate_match=rm) if (PN_Message and count) else None
+        if fading is not None:  # the gains of this batch, then the composition of the header over them
+            gain = _fading_gains(fading, sharding.fading_uses(n_tx, qam_m), F, first, count, device)
         if not count:
             yd = None
+        elif fading is not None:
+            yd = _fading_transmit(gain, my_seed, sigma, cw, n_tx, count, qam_m, con_dev, interleave, rm)
+            if rm is not None:
+                yd = RM_Recover(rm, yd, short_llr)
         elif rm is not None and qam_m:  # the modem sees the E transmitted bits only
             rx = AWGNChannel_QAM_GPU(my_seed, sigma, RM_Modulate_QAM(rm, cw, qam_m, interleave=interleave), con_dev)
             yd = _qam_receive(rm, rx, con_dev, 1.0 / (2.0 * sigma * sigma), short_llr, interleave)
@@ -257,7 +306,7 @@ def format_harq_row(SIM, info_bits):
 def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, maxIT=50, exit_mode=EXIT_FIXED, kernel=KERNEL_AUTO,
                         leastErrorFrames=50, leastTestFrames=10000, dist=None, device=None, max_batches=None, log=print, PN_Message=0,
                         pn_seed=0, schedule="flooding", alpha=1.0, stop_rule=None, short_llr=1.0e4, compact=True, keep_D=None, quant=None,
-                        n_QAM=2, CONSTELLATION=None, interleave=IL_NONE):
+                        n_QAM=2, CONSTELLATION=None, interleave=IL_NONE, fading=None):
     """One SNR point of incremental-redundancy HARQ over BPSK, or over n_QAM-QAM, on the device channel.  rvs = [rm_0, ..., rm_{T-1}]: the profile of
     each transmission (RateMatch.circular or RateMatch, all over code.N with the same shortened positions).  SIM is a HarqCounters.
 
@@ -286,7 +335,13 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
     1 / (2 sigma^2) and the index rule `interleave` (IL_ROWCOL: the row-column bit interleaver); the receive side runs the fused call or
     Demodulate_QAM -> RM_Recover / RM_Combine, whichever was measured faster (_qam_receive).  It owns 4 * ceil(E_t / m) * F draws, and the channel draws
     for acknowledged frames too: their points are made and never read.  The accumulated values are max-log LLRs already, so
-    schedule="bp" decodes with llr_scale = 1.0.  The caller passes the sigma of that n_QAM (nbldpc.sigma_of; sweep_harq does)."""
+    schedule="bp" decodes with llr_scale = 1.0.  The caller passes the sigma of that n_QAM (nbldpc.sigma_of; sweep_harq does).
+
+    fading (a Fading): every transmission sees a fading realisation of its own.  Transmission t draws the gains of its S_t channel uses
+    (E_t over BPSK, ceil(E_t / m) over QAM) for all F frames of the batch from the fading stream, fading.seed -- ceil(S_t / Lc) draws
+    per frame, owned whether a frame is acknowledged or not, so the stream's position after a batch depends on nothing that happened in
+    it -- and runs as the composition RM_Select (or RM_Modulate_QAM) -> the fading channel -> (Demodulate_QAM_Fading ->) RM_Recover
+    for t = 0, RM_Combine under done = D[N] after it.  The noise stream is used exactly as without fading."""
     if PN_Message not in (0, 1):
         raise ValueError("PN_Message must be 0 (all-zero codeword) or 1 (random codewords)")
     bp, layered = _check_schedule(schedule, alpha, quant)
@@ -305,6 +360,7 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
     elif PN_Message == 1 and exit_mode != EXIT_FIXED:
         raise ValueError("PN_Message=1 needs exit_mode=EXIT_FIXED: the flooding decoders' early exit tests for the all-zero word")
     qam_m, con = _check_qam(n_QAM, CONSTELLATION, PN_Message, interleave)
+    _check_fading(fading, True, exit_mode)
     rvs = list(rvs) if rvs is not None else []
     if not rvs:
         raise ValueError("rvs must hold at least one profile")
@@ -366,19 +422,28 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
             per_frame = sharding.qam_draws_per_frame(rm.E, qam_m) if qam_m else sharding.binary_draws_per_frame(rm.E)
             my_seed = sharding.lcg_jump(seed, first * per_frame)
             seed[:] = sharding.lcg_jump(seed, F * per_frame)  # owned by this transmission whether it is used or not
-            if not count or (t and bool(acked.all())):
+            skip = not count or (t and bool(acked.all()))
+            if fading is not None:  # and so are its gains: the fading seed moves before anything can skip the transmission
+                gain = _fading_gains(fading, sharding.fading_uses(rm.E, qam_m), F, first, 0 if skip else count, device)
+            if skip:
                 continue
             active = ~acked
-            if qam_m:  # the points of every frame, acknowledged or not: the QAM channel has no done mask
+            if fading is not None:
+                llr = _fading_transmit(gain, my_seed, sigma, cw, rm.E, count, qam_m, con_dev, interleave, rm)
+            elif qam_m:  # the points of every frame, acknowledged or not: the QAM channel has no done mask
                 rx = AWGNChannel_QAM_GPU(my_seed, sigma, RM_Modulate_QAM(rm, cw, qam_m, interleave=interleave), con_dev)
             if t == 0:
-                if qam_m:
+                if fading is not None:
+                    acc = RM_Recover(rm, llr, short_llr)
+                elif qam_m:
                     acc = _qam_receive(rm, rx, con_dev, qam_scale, short_llr, interleave)
                 else:
                     acc = AWGNChannel_RM_GPU(rm, my_seed, sigma, count, device=device, CodeWord=cw, short_llr=short_llr)
                 iters = decode(acc, D)
             else:
-                if qam_m:
+                if fading is not None:
+                    RM_Combine(rm, llr, acc, done=D[N], short_llr=short_llr)
+                elif qam_m:
                     _qam_receive(rm, rx, con_dev, qam_scale, short_llr, interleave, acc=acc, done=D[N])
                 else:
                     AWGNChannel_RM_Combine_GPU(rm, my_seed, sigma, acc, done=D[N], CodeWord=cw, short_llr=short_llr)
@@ -428,8 +493,11 @@ def sweep_harq(code, rvs, startSNR=0.0, stopSNR=13.0, stepSNR=0.2, snrtype=1, se
     rate = rvs[0].rate(code.K)
     if n_QAM != 2:
         kw["n_QAM"] = n_QAM
+    fading_seed0 = kw["fading"].seed.tolist() if kw.get("fading") is not None else None
     for snr in snr_grid(startSNR, stopSNR, stepSNR):
         seed = np.array(seeds, np.int32)
+        if fading_seed0 is not None:  # the fading stream restarts at every point, as the noise stream does
+            kw["fading"] = Fading(kw["fading"].Lc, fading_seed0)
         SIM = HarqCounters()
         SIM.SNR = snr
         sigma = nb_sigma_of(snr, rate, snrtype, n_QAM) if n_QAM != 2 else sigma_of(snr, snrtype, rate)
@@ -463,8 +531,11 @@ def sweep(code, startSNR=0.0, stopSNR=13.0, stepSNR=0.2, snrtype=1, seeds=(173, 
     rate = kw["rate_match"].rate(code.K) if kw.get("rate_match") is not None else code.K / code.N
     if n_QAM != 2:
         kw["n_QAM"] = n_QAM
+    fading_seed0 = kw["fading"].seed.tolist() if kw.get("fading") is not None else None
     for snr in snr_grid(startSNR, stopSNR, stepSNR):
         seed = np.array(seeds, np.int32)  # reset at every point (main.cu:117-119)
+        if fading_seed0 is not None:  # and so is the fading stream
+            kw["fading"] = Fading(kw["fading"].Lc, fading_seed0)
         SIM = SimCounters()
         SIM.SNR = snr
         sigma = nb_sigma_of(snr, rate, snrtype, n_QAM) if n_QAM != 2 else sigma_of(snr, snrtype, rate)

@@ -461,6 +461,57 @@ int bldpc_qam_demap_il_host(const float *rx, const float *constellation, int q, 
 int bldpc_qam_map_host(const int *CodeWord, int N, int F, int m, int *sym);
 int bldpc_qam_demap_host(const float *rx, const float *constellation, int q, float scale, int N, int F, float *Channel_Out);
 
+/* -- block fading with receiver CSI (not in the reference, whose channels are memoryless AWGN) ----------------------------- */
+
+/* Model: flat Rayleigh block fading, perfect receiver CSI, coherent detection.  A channel use is a bit over BPSK and a constellation
+ * point over QAM.  Use s of frame f has a real gain a[f][s] >= 0 that the receiver knows; it receives r = a * x + n with n exactly the
+ * noise the AWGN channels draw.  E[a^2] = 1, so sigma under Es/N0 and Eb/N0 stays what bldpc_sigma / nbldpc_sigma give.
+ *
+ * The gain array is always float [F][S], frame outer, one entry per channel use.  The block structure lives in the generator below
+ * only: every consumer reads a plain per-use gain, so a caller may supply any other fading process.  A consumer requires finite
+ * gains >= 0 and nothing else; other values are undefined, as NaN inputs are.
+ *
+ * (a) Gains.  nb = ceil(S / Lc) blocks per frame.  Block j of frame f takes draw number f * nb + j of the RandomModule stream at
+ * `seed`, one draw u, and a = sqrtf(-logf(1.0f - u)) is written to gain[f*S + s] for every s with s / Lc == j.  seed advances by
+ * nb * F draws.  Lc >= 1; Lc = 1 is fast fading; Lc >= S (Lc > S is legal) is one block, quasi-static fading.  1 - u >= 2^-24, so
+ * 0 <= a <= 4.08.  The fading stream has a seed triple of its own, separate from the noise seed: a frame's gains and a frame's noise
+ * then depend on the frame's global index only, not on the batch size or on the number of ranks.  The device call jumps
+ * every thread to its first draw as bldpc_awgn_channel_device does (same draws; device libm, so a gain is the host's or an ulp away).
+ *   gain  device (host: host) float [F][S]      BLDPC_EINVAL: a null pointer, Lc < 1, S or F <= 0, a seed outside its modulus */
+int bldpc_fading_gains_device(int seed[3], int Lc, int S, int F, float *gain, void *stream);
+int bldpc_fading_gains_host(int seed[3], int Lc, int S, int F, float *gain);
+
+/* (b) BPSK channel.  The draws, their indexing (2 (f*N + n)) and the seed advance are those of bldpc_awgn_channel_device.  With
+ * a = gain[f*N + n]:
+ *     r = (float)((double)sigma * sin(two_pi * (double)u2) * (double)amp + (double)a * (1.0 - (double)(2*c)))
+ *     Channel_Out[n*F + f] = a * r            one fp32 multiplication: the matched-filter value
+ * so that 2 / sigma^2 stays the sum-product decoder's llr_scale.  gain [F][N]; CodeWord == NULL is the all-zero word.  With
+ * a == 1.0f this is bldpc_awgn_channel_device's value bit for bit.  BLDPC_EINVAL: a null seed, gain or Channel_Out, N or F <= 0, a
+ * seed outside its modulus (the host statement included). */
+int bldpc_awgn_fading_channel_device(int seed[3], float sigma, const float *gain, float *Channel_Out, const int *CodeWord, int N, int F,
+                                     void *stream);
+int bldpc_awgn_fading_channel_host(int seed[3], float sigma, const float *gain, float *Channel_Out, const int *CodeWord, int N, int F);
+
+/* (d) The max-log demapper with CSI: everything bldpc_qam_demap_il says, with the distances taken to the faded points,
+ *     dx = x - a*cx_p;  dy = y - a*cy_p;  d_p = dx*dx + dy*dy         a = gain[f*Ns + s], aligned with rx [F][Ns][2]
+ * two more fp32 multiplications per point, no fused multiply-add, no division, no special case.  a == 0 makes all distances equal and
+ * every output +0.0f: an erasure.  a == 1.0f gives bldpc_qam_demap_il's bits.  The equalised form (divide the point by a, weight the
+ * result by a^2) is deliberately not the specification: it overflows for small gains and needs a special case at 0.
+ * The QAM channel that applies the gains is nbldpc_fading_channel_device_qam_frames (include/nbldpc.h).  Same argument checks as
+ * bldpc_qam_demap_il, and gain != NULL.
+ *
+ * Rate matching and HARQ over a fading channel are compositions, through an [E][F] array:
+ *     BPSK   bldpc_rm_select -> bldpc_awgn_fading_channel_device at N := E -> bldpc_rm_recover / bldpc_rm_combine
+ *            (sample (f, e) uses the draws 2 (f E + e), as the fused rate-matched channel does)
+ *     QAM    bldpc_rm_qam_map -> nbldpc_fading_channel_device_qam_frames -> bldpc_qam_demap_fading at N := E with the interleave rule
+ *            -> bldpc_rm_recover / bldpc_rm_combine       (the composition bldpc_rm_qam_recover is defined by)
+ * Fused fading forms of bldpc_rm_awgn_* and bldpc_rm_qam_* are out of scope, as are complex gains, phase errors, imperfect CSI and
+ * correlated (Doppler) processes -- the last can be had by passing a gain array of one's own. */
+int bldpc_qam_demap_fading(const float *rx, const float *gain, const float *constellation, int q, float scale, int N, int F, int interleave,
+                           float *Channel_Out, void *stream);
+int bldpc_qam_demap_fading_host(const float *rx, const float *gain, const float *constellation, int q, float scale, int N, int F, int interleave,
+                                float *Channel_Out);
+
 /* -- rate matching: shortened and punctured codes (not in the reference, which transmits every bit of the mother code) -- */
 
 /* A profile over a mother code of N bits names two disjoint sets of codeword positions.  Semantics:

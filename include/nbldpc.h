@@ -222,6 +222,29 @@ int nbldpc_awgn_channel_device_frames(int seed[3], float sigma, const int *CodeW
 int nbldpc_awgn_channel_device_qam_frames(int seed[3], float sigma, const int *CodeWord_sym, int N, const float *constellation, int q, int B,
                                           float *rx, void *stream);
 
+/* Block fading with receiver CSI (the model, the gain array float [B][N] and its generator: include/bldpc.h, "block fading").
+ * nbldpc_fading_channel_device_qam_frames is nbldpc_awgn_channel_device_qam_frames in every respect -- four draws per symbol at
+ * 4 (b*N + i), the q - 1 mask, the seed advance -- but for the transmitted part, which is (double)a * (double)constellation[2*sym + c]
+ * with a = gain[b*N + i] instead of (double)constellation[2*sym + c]; a == 1.0f gives that call's bits.  It serves the binary QAM
+ * chain (N := symbols per frame) and the GF(q) QAM chain alike.  gain: DEVICE float [B][N].  The _host form is the statement: host
+ * pointers, the serial stream, host libm.  NBLDPC_EINVAL: a null pointer, N or B <= 0, q not a power of two, a seed outside its modulus. */
+int nbldpc_fading_channel_device_qam_frames(int seed[3], float sigma, const int *CodeWord_sym, int N, const float *constellation, int q,
+                                            const float *gain, int B, float *rx, void *stream);
+int nbldpc_fading_channel_host_qam_frames(int seed[3], float sigma, const int *CodeWord_sym, int N, const float *constellation, int q,
+                                          const float *gain, int B, float *rx);
+
+/* nbldpc_demodulate_qam with CSI: with a = gain[b*N + s] the four products a*c0r, a*c0i, a*ckr, a*cki are formed first, each one fp32
+ * multiplication, and then used in the expression of nbldpc_demodulate_qam, in its order, in place of c0r, c0i, ckr, cki:
+ *     L_ch[b][s][k-1] = ((2*yr - c0r - ckr) * (ckr - c0r) + (2*yi - c0i - cki) * (cki - c0i)) / (2 * sigma * sigma)
+ * a == 1.0f gives nbldpc_demodulate_qam's bits.  gain DEVICE float [B][N] (host for _host, which is the statement).  The GF(q) BPSK
+ * path has no fading form.  Argument checks as nbldpc_demodulate_qam_nq, and gain != NULL. */
+int nbldpc_demodulate_qam_fading_nq(int N, int q, const float *rx, const float *gain, const float *constellation, float sigma, int B,
+                                    float *L_ch, void *stream);
+int nbldpc_demodulate_qam_fading(const nbldpc_code *code, const float *rx, const float *gain, const float *constellation, float sigma, int B,
+                                 float *L_ch, void *stream);
+int nbldpc_demodulate_qam_fading_host(int N, int q, const float *rx, const float *gain, const float *constellation, float sigma, int B,
+                                      float *L_ch);
+
 /* nbldpc_statistic / nbldpc_frame_errors against one word per frame: CodeWord_sym DEVICE int32 [B][N]. */
 int nbldpc_statistic_frames(const nbldpc_code *code, const int *DecodeOutput, const int *iter_number, const int *ok, const int *CodeWord_sym,
                             int B, long long *counters, void *stream);

@@ -7,6 +7,8 @@
     python sweep.py binary --device-channel --layered --per-frame --pn-message --qam 64 --interleave rowcol --snrtype 0 --harq 0:2160,2160:144,500:2400 --start 8 --stop 9 --step 0.5
     python sweep.py binary --device-channel --bp --per-frame --stop-rule syndrome --pn-message --start 2 --stop 3 --step 0.2
     python sweep.py binary --device-channel --quant 6,8,6 --norm8 6 --llr-scale 16 --per-frame --stop-rule syndrome --pn-message --start 2 --stop 3 --step 0.2
+    python sweep.py binary --device-channel --per-frame --layered --pn-message --qam 64 --interleave rowcol --fading 16 --harq 0:2160,2160:48,500:2300
+    python sweep.py nb --pn-message --qam 64 --fading 16
     python -m torch.distributed.run --nproc-per-node N sweep.py binary ...      (frames sharded over N GPUs)
 
 binary: rows `SNR NTF NEF FER BER AverIT FER_F FER_A` as Simulation.cu:272 prints them (Es/N0, seeds 173/173/173,
@@ -99,7 +101,27 @@ def main():
                     "transmission's rate (needs --device-channel and --fixed or --per-frame)")
     ap.add_argument("--snrtype", type=int, default=None, choices=[0, 1], help="--harq: 0 = Eb/N0 on the first transmission's rate, 1 = Es/N0 (default)")
     ap.add_argument("--no-compact", action="store_true", help="--harq: decode the whole batch after every transmission (timing and checking)")
+    ap.add_argument("--fading", metavar="LC", type=int, default=None, help="flat Rayleigh block fading with receiver CSI: gains constant over LC "
+                    "channel uses (bits over BPSK, points over QAM), 1 = fast fading, 0 = quasi-static (one gain per frame and transmission); "
+                    "binary: needs --device-channel and --fixed or --per-frame, combines with --qam, --interleave, --shorten / --puncture, "
+                    "--harq and every decoder; nb: needs --qam 64/256 and runs on the device channel")
+    ap.add_argument("--fade-seed", metavar="A,B,C", default=None, help="--fading: the seed of the fading stream (default 4711,4712,4713)")
     args = ap.parse_args()
+    fade = None
+    if args.fading is not None:
+        try:
+            fade_seed = tuple(int(x) for x in (args.fade_seed or "4711,4712,4713").split(","))
+        except ValueError:
+            ap.error("--fade-seed takes three integers A,B,C")
+        if args.fading < 0 or len(fade_seed) != 3:
+            ap.error("--fading takes LC >= 0 and --fade-seed three integers A,B,C")
+        if args.which == "binary" and (not args.device_channel or not (args.fixed or args.per_frame) or args.as_written):
+            ap.error("binary --fading needs --device-channel and --fixed or --per-frame (the batch-global exit depends on the batch)")
+        if args.which == "nb" and args.qam == 2:
+            ap.error("nb --fading needs --qam 64 or 256: the GF(q) BPSK path has no fading channel")
+        fade = (args.fading, fade_seed)  # becomes a Fading once the package is imported
+    elif args.fade_seed is not None:
+        ap.error("--fade-seed belongs to --fading")
     if args.harq is not None:
         if args.which != "binary" or not args.device_channel or args.as_written or not (args.fixed or args.per_frame):
             ap.error("--harq belongs to the binary sweep with --device-channel and --fixed or --per-frame")
@@ -170,6 +192,15 @@ def main():
         dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
     rank = int(os.environ.get("RANK", "0"))
     import cuda_ldpc_amd as C
+    fad = {}
+    if fade is not None:
+        fad = dict(fading=C.Fading(fade[0] or C.QUASI_STATIC, fade[1]))
+        try:
+            fad["fading"].check()
+        except ValueError as e:
+            ap.error("--fade-seed: %s" % e)
+        fade_words = ", Rayleigh block fading %s (seed %s), receiver CSI" % (
+            "Lc=%d" % fade[0] if fade[0] else "quasi-static", ",".join(str(x) for x in fade[1]))
 
     if args.which == "binary":
         from cuda_ldpc_amd.simulation import sweep
@@ -208,12 +239,13 @@ def main():
                                                           "layered alpha=%g" % args.alpha if args.layered else
                                                           "flooding alpha=%g" % args.alpha, "fixed iterations" if args.fixed else "per-frame early exit",
                                                           args.iters or (25 if rows else 50), args.batch, world,
-                                                          ", random codewords (PN seed %d)" % args.pn_seed if args.pn_message else ""))
+                                                          ", random codewords (PN seed %d)" % args.pn_seed if args.pn_message else "")
+                      + (fade_words if fade is not None else ""))
                 print("# SNR      NTF  FER after each transmission ...  mean transmissions  throughput (information bits per bit sent)  AverIT")
             sweep_harq(code, rvs, args.start, args.stop, args.step, snrtype=1 if args.snrtype is None else args.snrtype, dist=dist,
                        Num_Frames_OneTime=args.batch, maxIT=args.iters or (25 if rows else 50),
                        exit_mode=C.EXIT_FIXED if args.fixed else C.EXIT_PER_FRAME, max_batches=args.max_batches, PN_Message=1 if args.pn_message else 0,
-                       pn_seed=args.pn_seed, log=print if rank == 0 else None, short_llr=args.short_llr, compact=not args.no_compact, **lay, **mod)
+                       pn_seed=args.pn_seed, log=print if rank == 0 else None, short_llr=args.short_llr, compact=not args.no_compact, **lay, **mod, **fad)
             if world > 1:
                 dist.destroy_process_group()
             return
@@ -233,11 +265,12 @@ def main():
                   ("normalised flooding min-sum alpha=%g, " % args.alpha if args.alpha != 1.0 else ""),
                   "fixed iterations" if args.fixed else ("per-frame early exit" if args.per_frame else "batch-global early exit"),
                   args.iters or (25 if rows else 50), args.batch, world,
-                  ", random codewords (PN seed %d, K'=%d), syndrome flag" % (args.pn_seed, code.K_info) if args.pn_message else ""))
+                  ", random codewords (PN seed %d, K'=%d), syndrome flag" % (args.pn_seed, code.K_info) if args.pn_message else "")
+                  + (fade_words if fade is not None else ""))
             print("# SNR      NTF   NEF         FER         BER  AverIT       FER_F      FER_A")
         sweep(code, args.start, args.stop, args.step, snrtype=1 if args.qam == 2 else 0, dist=dist, Num_Frames_OneTime=args.batch, maxIT=args.iters or (25 if rows else 50),
               exit_mode=C.EXIT_FIXED if args.fixed else (C.EXIT_PER_FRAME if args.per_frame else C.EXIT_BATCH_GLOBAL), max_batches=args.max_batches, displayStep=10 ** 12, device_channel=args.device_channel,
-              PN_Message=1 if args.pn_message else 0, pn_seed=args.pn_seed, log=print if rank == 0 else None, **lay, **mod)
+              PN_Message=1 if args.pn_message else 0, pn_seed=args.pn_seed, log=print if rank == 0 else None, **lay, **mod, **fad)
     else:
         from cuda_ldpc_amd import nbldpc as nb
         from cuda_ldpc_amd.nb_simulation import sweep
@@ -253,12 +286,13 @@ def main():
             words = "" if bds else ", all-zero codeword"
         print("# %s N=%d symbols GF(%d), %s, maxIT=%d, %s%s" % (os.path.basename(mpath).replace(".txt", ""), code.N, code.q,
               ["EMS(2,2)", "trellis min-max", "log-QSPA = EMS(q,dc-1)", "layered trellis min-max"][args.method], args.iters or 20,
-              "BPSK" if args.qam == 2 else "%d-QAM (Gray), one point per symbol" % args.qam, words))
+              "BPSK" if args.qam == 2 else "%d-QAM (Gray), one point per symbol" % args.qam, words) + (fade_words if fade is not None else ""))
         print("# SNR      NTF   NEF         FER         BER  AverIT")
-        nbatch = args.batch if args.device_channel else min(args.batch, 1024)  # the host channel is serial: keep its batches small
+        dev_ch = args.device_channel or fade is not None  # the fading channel exists on the device only
+        nbatch = args.batch if dev_ch else min(args.batch, 1024)  # the host channel is serial: keep its batches small
         sweep(code, cw, args.start, args.stop, args.step, maxIT=args.iters or 20, batch=nbatch,
-              max_frames=None if args.max_batches is None else args.max_batches * nbatch, device_channel=args.device_channel,
-              decoder_method=args.method, n_QAM=args.qam, CONSTELLATION=con, PN_Message=1 if args.pn_message else 0, pn_seed=args.pn_seed)
+              max_frames=None if args.max_batches is None else args.max_batches * nbatch, device_channel=dev_ch,
+              decoder_method=args.method, n_QAM=args.qam, CONSTELLATION=con, PN_Message=1 if args.pn_message else 0, pn_seed=args.pn_seed, **fad)
     if world > 1:
         dist.destroy_process_group()
 
