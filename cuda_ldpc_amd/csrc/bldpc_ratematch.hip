@@ -287,7 +287,8 @@ int cldpc::rm_view(const bldpc_rm *rm, bool device, RmView *v)
 {
     if (device)
         if (int r = device_tables(rm)) return r;
-    *v = RmView{rm->N, rm->E, rm->Ncb, rm->k0, laps_of(rm), rm->n_short, rm->n_punct, rm->d_map, rm->d_tx};
+    *v = RmView{rm->N, rm->E, rm->Ncb, rm->k0, laps_of(rm), rm->n_short, rm->n_punct, rm->d_map, rm->d_tx,
+                rm->map.data(), rm->tx_pos.data(), rm->short_pos.data()};
     return BLDPC_OK;
 }
 

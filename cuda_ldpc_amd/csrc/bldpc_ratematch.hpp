@@ -7,10 +7,12 @@ struct bldpc_rm;
 namespace cldpc {
 
 // What bldpc_modem.hip reads of a profile for the fused modem calls ("rate matching over QAM" in include/bldpc.h).  d_map [N] and
-// d_tx [E] are the profile's device tables; they stay NULL unless rm_view was asked to upload them.
+// d_tx [E] are the profile's device tables; they stay NULL unless rm_view was asked to upload them.  map, tx_pos and short_pos
+// [n_short] are the host tables, owned by the profile (nbldpc_ratematch.hip: the GF(q) half reads a profile over symbols through them).
 struct RmView {
     int N, E, Ncb, k0, laps, n_short, n_punct;
     const int *d_map, *d_tx;
+    const int *map, *tx_pos, *short_pos;
 };
 // bldpc_ratematch.hip: device = true uploads the tables on first use, as every device call on a profile does (BLDPC_ENOMEM / _EHIP)
 int rm_view(const bldpc_rm *rm, bool device, RmView *v);

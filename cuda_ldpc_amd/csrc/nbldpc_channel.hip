@@ -11,6 +11,7 @@
 #include "common.hpp"
 #include "common_lcg.hpp"
 #include "nbldpc_code.hpp"
+#include "nbldpc_demod.hpp"
 
 using namespace cldpc;
 
@@ -25,12 +26,7 @@ __global__ __launch_bounds__(256) void k_nb_demod_bpsk(const float *rx, float si
     if (id >= total) return;
     const int k = (int)(id % (q - 1)) + 1;
     const size_t bs = id / (q - 1); // b*N + s
-    const float *r = rx + bs * m;
-    const float s2 = sigma * sigma;
-    float acc = 0.0f;
-    for (int b = 0; b < m; b++)
-        if ((k & (1 << b)) != 0) acc += (float)(-2) * r[b] / s2;
-    Lch[id] = acc;
+    Lch[id] = nb_demod_bpsk_entry(rx + bs * m, k, m, sigma);
 }
 
 // Demodulate, n_QAM != 2 branch (LDPC_Decoder.cpp:160-169): one received point per code symbol, float arithmetic in the
@@ -44,7 +40,7 @@ __global__ __launch_bounds__(256) void k_nb_demod_qam(const float *rx, const flo
     const size_t bs = id / (q - 1); // b*N + s
     const float yr = rx[2 * bs], yi = rx[2 * bs + 1];
     const float c0r = con[0], c0i = con[1], ckr = con[2 * k], cki = con[2 * k + 1];
-    Lch[id] = ((2 * yr - c0r - ckr) * (ckr - c0r) + (2 * yi - c0i - cki) * (cki - c0i)) / (2 * sigma * sigma);
+    Lch[id] = nb_demod_qam_entry(yr, yi, c0r, c0i, ckr, cki, sigma);
 }
 
 // Statistic (Simulation.cpp:256-279): one thread per frame.  Frame f is compared with cw + f * cw_stride (0: one word for all frames).

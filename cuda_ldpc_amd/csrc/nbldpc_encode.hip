@@ -242,6 +242,17 @@ extern "C" int nbldpc_encoder_info(nbldpc_code *code, int *K_info, int *rank, in
     return NBLDPC_OK;
 }
 
+int cldpc::nb_enc_info(nbldpc_code *code, const char *who, int *K_info, const int **info_pos, const int **d_info_pos)
+{
+    NbCodeView v;
+    NbEncState *s = nullptr;
+    if (int r = ensure_generator(code, who, v, s)) return r;
+    *K_info = s->g.K;
+    *info_pos = s->g.info_pos.data();
+    *d_info_pos = s->d_info;
+    return NBLDPC_OK;
+}
+
 static int encode_impl(nbldpc_code *code, const int *msg, int *msg_out, bool random, u64 seed, long long first_frame, int B, int *cw,
                        void *stream, const char *who)
 {

@@ -19,4 +19,8 @@ struct NbCodeView {
 NbCodeView nb_code_view(const nbldpc_code *c); // nbldpc_api.hip
 void nb_enc_state_free(NbEncState *s);         // nbldpc_encode.hip
 
+// nbldpc_encode.hip: the information set of the code's generator (built on first use, as nbldpc_encoder_info does): K', info_pos on
+// the host and on the device, both owned by the code object.  For nbldpc_ratematch.hip (nbldpc_rm_encode_random).
+int nb_enc_info(nbldpc_code *code, const char *who, int *K_info, const int **info_pos, const int **d_info_pos);
+
 } // namespace cldpc

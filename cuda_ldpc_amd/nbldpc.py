@@ -42,6 +42,26 @@ lib.nbldpc_syndrome.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c
 lib.nbldpc_awgn_channel_device_frames.argtypes = [c_void_p, c_float, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
 lib.nbldpc_awgn_channel_device_qam_frames.argtypes = [c_void_p, c_float, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]
 lib.nbldpc_statistic_frames.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
+lib.nbldpc_demodulate_bpsk_nq.argtypes = [c_int, c_int, c_void_p, c_float, c_int, c_void_p, c_void_p]
+lib.nbldpc_demodulate_qam_nq.argtypes = [c_int, c_int, c_void_p, c_void_p, c_float, c_int, c_void_p, c_void_p]
+lib.nbldpc_demodulate_bpsk_nq_host.argtypes = [c_int, c_int, c_void_p, c_float, c_int, c_void_p]
+lib.nbldpc_demodulate_qam_nq_host.argtypes = [c_int, c_int, c_void_p, c_void_p, c_float, c_int, c_void_p]
+lib.nbldpc_rm_select.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p]
+lib.nbldpc_rm_recover.argtypes = [c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p]
+lib.nbldpc_rm_combine.argtypes = [c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p]
+lib.nbldpc_rm_demodulate_qam_recover.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_float, c_int, c_float, c_void_p, c_void_p]
+lib.nbldpc_rm_demodulate_qam_combine.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_float, c_int, c_float, c_void_p, c_void_p, c_void_p]
+lib.nbldpc_rm_demodulate_bpsk_recover.argtypes = [c_void_p, c_int, c_void_p, c_float, c_int, c_float, c_void_p, c_void_p]
+lib.nbldpc_rm_demodulate_bpsk_combine.argtypes = [c_void_p, c_int, c_void_p, c_float, c_int, c_float, c_void_p, c_void_p, c_void_p]
+lib.nbldpc_rm_encode_random.argtypes = [c_void_p, c_void_p, ctypes.c_ulonglong, ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p]
+lib.nbldpc_rm_select_host.argtypes = [c_void_p, c_void_p, c_int, c_void_p]
+lib.nbldpc_rm_recover_host.argtypes = [c_void_p, c_int, c_void_p, c_int, c_float, c_void_p]
+lib.nbldpc_rm_combine_host.argtypes = [c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p]
+lib.nbldpc_rm_demodulate_qam_recover_host.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_float, c_int, c_float, c_void_p]
+lib.nbldpc_rm_demodulate_qam_combine_host.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_float, c_int, c_float, c_void_p, c_void_p]
+lib.nbldpc_rm_demodulate_bpsk_recover_host.argtypes = [c_void_p, c_int, c_void_p, c_float, c_int, c_float, c_void_p]
+lib.nbldpc_rm_demodulate_bpsk_combine_host.argtypes = [c_void_p, c_int, c_void_p, c_float, c_int, c_float, c_void_p, c_void_p]
+lib.nbldpc_rm_force_shortened_host.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p]
 
 
 def _check(rc, what):
@@ -330,10 +350,11 @@ def AWGNChannel_GPU(seed, sigma, code, CodeWord_sym_dev, B, stream=None, CONSTEL
     return rx
 
 
-def seed_after(seed, frames, code, qam=False):
-    """The RandomModule state after `frames` more frames (4 draws per bit; per symbol with a QAM constellation)."""
+def seed_after(seed, frames, code, qam=False, E=None):
+    """The RandomModule state after `frames` more frames (4 draws per bit; per symbol with a QAM constellation).  E: the transmitted
+    symbols per frame of a rate-matched transmission, in place of code.N."""
     a, m = (249, 251, 252), (61967, 63443, 63599)
-    k = 4 * code.N * (1 if qam else code.m) * int(frames)
+    k = 4 * (code.N if E is None else int(E)) * (1 if qam else code.m) * int(frames)
     return np.array([(int(seed[i]) * pow(a[i], k, m[i])) % m[i] for i in range(3)], np.int32)
 
 
@@ -395,10 +416,12 @@ def Encode(code, msg, CodeWord_sym=None, stream=None):
     return CodeWord_sym
 
 
-def PN_CodeWords(code, seed, B, first_frame=0, want_msg=False, device=None, CodeWord_sym=None, stream=None):
+def PN_CodeWords(code, seed, B, first_frame=0, want_msg=False, device=None, CodeWord_sym=None, stream=None, rate_match=None):
     """nbldpc_encode_random: the codewords of frames first_frame .. first_frame+B-1 of the message stream `seed` (counter-based
     rule of nbldpc.h, mirrored by pn_messages below).  Returns CodeWord_sym int32 [B, N] on the device, or (CodeWord_sym,
-    msg [B, K']) with want_msg."""
+    msg [B, K']) with want_msg.  rate_match (a RateMatch over code.N symbols): nbldpc_rm_encode_random -- the message symbols at the
+    profile's shortened positions are forced to 0 before encoding (msg: after the forcing); the shortened positions must lie in the
+    information set."""
     if B <= 0 or first_frame < 0:
         raise ValueError("B must be positive and first_frame >= 0")
     device = device or torch.device("cuda", torch.cuda.current_device())
@@ -406,8 +429,12 @@ def PN_CodeWords(code, seed, B, first_frame=0, want_msg=False, device=None, Code
         CodeWord_sym = torch.empty((B, code.N), dtype=torch.int32, device=device)
     else:
         _check_cw(CodeWord_sym, B, code.N, device)
-    msg = torch.empty((B, code.K_info), dtype=torch.int32, device=device) if want_msg else None
+    msg = torch.empty((B, code.K_info), dtype=torch.int32, device=device) if (want_msg or rate_match is not None) else None
     st = c_void_p((stream or torch.cuda.current_stream(device)).cuda_stream)
+    if rate_match is not None:
+        _check(lib.nbldpc_rm_encode_random(code._h, rate_match._h, ctypes.c_ulonglong(int(seed) % (1 << 64)), int(first_frame), B, _dev(msg),
+                                           _dev(CodeWord_sym), st), "PN_CodeWords")
+        return (CodeWord_sym, msg) if want_msg else CodeWord_sym
     _check(lib.nbldpc_encode_random(code._h, ctypes.c_ulonglong(int(seed) % (1 << 64)), int(first_frame), B, _dev(msg), _dev(CodeWord_sym), st),
            "PN_CodeWords")
     return (CodeWord_sym, msg) if want_msg else CodeWord_sym
@@ -439,3 +466,253 @@ def Syndrome(code, DecodeOutput, stream=None):
     st = c_void_p((stream or torch.cuda.current_stream(dev)).cuda_stream)
     _check(lib.nbldpc_syndrome(code._h, _dev(DecodeOutput), B, _dev(flag), _dev(unsat), st), "Syndrome")
     return dict(flag=flag, unsat=unsat)
+
+
+# ---- rate matching over symbol LLR vectors (include/nbldpc.h, "rate matching").  A profile is a bldpc.RateMatch made with N = code.N
+# symbols; q is the field size (an int, or anything with a .q: a code); every array is frame-outer. ----
+def _q_of(q):
+    q = int(getattr(q, "q", q))
+    if q < 2 or q > 256 or q & (q - 1):
+        raise ValueError("q=%d is not a power of two in 2 .. 256" % q)
+    return q, q.bit_length() - 1
+
+
+def _check_short_llr(short_llr):
+    if not (np.isfinite(short_llr) and short_llr > 0):
+        raise ValueError("short_llr must be finite and > 0, not %r" % (short_llr,))
+
+
+def _rm_dev(t, shape_tail, dtype, what, B=None, dev=None):
+    """t: a contiguous CUDA tensor [B, *shape_tail] of dtype (on dev, with B frames, when given).  Returns (B, device)."""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.dim() == 1 + len(shape_tail)
+            and tuple(t.shape[1:]) == tuple(shape_tail) and t.shape[0] > 0 and (B is None or t.shape[0] == B) and (dev is None or t.device == dev)):
+        raise ValueError("%s must be a contiguous CUDA %s tensor [B%s, %s]%s" % (what, str(dtype).split(".")[-1], "" if B is None else "=%d" % B,
+                                                                               ", ".join(str(s) for s in shape_tail), "" if dev is None else " on %s" % dev))
+    return int(t.shape[0]), t.device
+
+
+def _rm_host(a, shape_tail, dtype, what, B=None):
+    a = np.ascontiguousarray(a, dtype)
+    if a.ndim != 1 + len(shape_tail) or tuple(a.shape[1:]) != tuple(shape_tail) or a.shape[0] <= 0 or (B is not None and a.shape[0] != B):
+        raise ValueError("%s must be %s [B%s, %s]" % (what, np.dtype(dtype).name, "" if B is None else "=%d" % B, ", ".join(str(s) for s in shape_tail)))
+    return a
+
+
+def _rm_done(done, B, dev):
+    if done is not None and not (torch.is_tensor(done) and done.is_cuda and done.device == dev and done.dtype == torch.int32 and done.dim() == 1
+                                 and done.is_contiguous() and done.shape[0] == B):
+        raise ValueError("done must be a contiguous CUDA int32 tensor [B=%d] on %s (a decoder's ok will do)" % (B, dev))
+
+
+def _rm_done_host(done, B):
+    if done is None:
+        return None
+    done = np.ascontiguousarray(done, np.int32)
+    if done.shape != (B,):
+        raise ValueError("done must be int32 [B=%d]" % B)
+    return done
+
+
+def _rm_acc_host(acc, N, V):
+    if not (isinstance(acc, np.ndarray) and acc.dtype == np.float32 and acc.flags.c_contiguous and acc.ndim == 3 and acc.shape[0] > 0
+            and acc.shape[1:] == (N, V)):
+        raise ValueError("L_acc must be a C-contiguous float32 array [B, N=%d, q-1=%d], updated in place" % (N, V))
+    return acc
+
+
+def _rm_con(CONSTELLATION, q, dev=None):
+    if dev is None:
+        con = np.ascontiguousarray(CONSTELLATION, np.float32)
+        if con.shape != (q, 2):
+            raise ValueError("CONSTELLATION must be float32 [q=%d, 2]" % q)
+        return con
+    if not (torch.is_tensor(CONSTELLATION) and CONSTELLATION.is_cuda and CONSTELLATION.device == dev and CONSTELLATION.dtype == torch.float32
+            and CONSTELLATION.is_contiguous() and tuple(CONSTELLATION.shape) == (q, 2)):
+        raise ValueError("CONSTELLATION must be a contiguous CUDA float32 tensor [q=%d, 2] on %s" % (q, dev))
+    return CONSTELLATION
+
+
+def _stream(stream, dev):
+    return c_void_p((stream or torch.cuda.current_stream(dev)).cuda_stream)
+
+
+def RM_Select(rm, CodeWord_sym, stream=None):
+    """nbldpc_rm_select: CodeWord_sym CUDA int32 [B, N] -> the transmitted symbols int32 [B, E], tx[b, e] = CodeWord_sym[b, tx_pos[e]]."""
+    B, dev = _rm_dev(CodeWord_sym, (rm.N,), torch.int32, "CodeWord_sym")
+    tx = torch.empty((B, rm.E), dtype=torch.int32, device=dev)
+    _check(lib.nbldpc_rm_select(rm._h, _dev(CodeWord_sym), B, _dev(tx), _stream(stream, dev)), "RM_Select")
+    return tx
+
+
+def RM_Select_host(rm, CodeWord_sym):
+    """nbldpc_rm_select_host: RM_Select on a host array int32 [B, N], no device needed."""
+    cw = _rm_host(CodeWord_sym, (rm.N,), np.int32, "CodeWord_sym")
+    tx = np.empty((cw.shape[0], rm.E), np.int32)
+    _check(lib.nbldpc_rm_select_host(rm._h, _np(cw), cw.shape[0], _np(tx)), "RM_Select_host")
+    return tx
+
+
+def RM_Recover(rm, q, Lrx, short_llr=1.0e4, stream=None):
+    """nbldpc_rm_recover: received vectors Lrx CUDA float32 [B, E, q-1] -> L_ch [B, N, q-1]: a position's contributions added in
+    ascending e (one contribution: the same bits), +0.0 on punctured and unreached positions, -short_llr on shortened ones."""
+    q, _ = _q_of(q)
+    B, dev = _rm_dev(Lrx, (rm.E, q - 1), torch.float32, "Lrx")
+    _check_short_llr(short_llr)
+    Lch = torch.empty((B, rm.N, q - 1), dtype=torch.float32, device=dev)
+    _check(lib.nbldpc_rm_recover(rm._h, q, _dev(Lrx), B, c_float(short_llr), _dev(Lch), _stream(stream, dev)), "RM_Recover")
+    return Lch
+
+
+def RM_Recover_host(rm, q, Lrx, short_llr=1.0e4):
+    """nbldpc_rm_recover_host: RM_Recover on a host array float32 [B, E, q-1], no device needed."""
+    q, _ = _q_of(q)
+    Lrx = _rm_host(Lrx, (rm.E, q - 1), np.float32, "Lrx")
+    Lch = np.empty((Lrx.shape[0], rm.N, q - 1), np.float32)
+    _check(lib.nbldpc_rm_recover_host(rm._h, q, _np(Lrx), Lrx.shape[0], c_float(short_llr), _np(Lch)), "RM_Recover_host")
+    return Lch
+
+
+def RM_Combine(rm, q, Lrx, L_acc, done=None, short_llr=1.0e4, stream=None):
+    """nbldpc_rm_combine: add one more transmission Lrx CUDA float32 [B, E, q-1] into L_acc [B, N, q-1] in place (and return it):
+    ((acc + Lrx[e_0]) + Lrx[e_1]) + ...; shortened positions become -short_llr; positions without a contribution and the frames with
+    done[b] != 0 (CUDA int32 [B], e.g. a decoder's ok) keep their bits."""
+    q, _ = _q_of(q)
+    B, dev = _rm_dev(L_acc, (rm.N, q - 1), torch.float32, "L_acc")
+    _rm_dev(Lrx, (rm.E, q - 1), torch.float32, "Lrx", B, dev)
+    _check_short_llr(short_llr)
+    _rm_done(done, B, dev)
+    _check(lib.nbldpc_rm_combine(rm._h, q, _dev(Lrx), B, c_float(short_llr), _dev(done), _dev(L_acc), _stream(stream, dev)), "RM_Combine")
+    return L_acc
+
+
+def RM_Combine_host(rm, q, Lrx, L_acc, done=None, short_llr=1.0e4):
+    """nbldpc_rm_combine_host: RM_Combine on host arrays; L_acc float32 [B, N, q-1] (C-contiguous) is updated in place."""
+    q, _ = _q_of(q)
+    acc = _rm_acc_host(L_acc, rm.N, q - 1)
+    B = acc.shape[0]
+    Lrx = _rm_host(Lrx, (rm.E, q - 1), np.float32, "Lrx", B)
+    done = _rm_done_host(done, B)
+    _check(lib.nbldpc_rm_combine_host(rm._h, q, _np(Lrx), B, c_float(short_llr), None if done is None else _np(done), _np(acc)), "RM_Combine_host")
+    return acc
+
+
+def RM_Demodulate_Recover(rm, q, rx, sigma, short_llr=1.0e4, stream=None, CONSTELLATION=None):
+    """The fused receive of a first transmission: Demodulate at N := E followed by RM_Recover, bit for bit, from one kernel and
+    without the [B, E, q-1] array.  BPSK: rx CUDA float32 [B, E*m]; with CONSTELLATION (CUDA float32 [q, 2]): rx [B, E, 2]."""
+    q, m = _q_of(q)
+    _check_short_llr(short_llr)
+    if CONSTELLATION is not None:
+        B, dev = _rm_dev(rx, (rm.E, 2), torch.float32, "rx")
+        con = _rm_con(CONSTELLATION, q, dev)
+        Lch = torch.empty((B, rm.N, q - 1), dtype=torch.float32, device=dev)
+        _check(lib.nbldpc_rm_demodulate_qam_recover(rm._h, q, _dev(rx), _dev(con), c_float(sigma), B, c_float(short_llr), _dev(Lch),
+                                                    _stream(stream, dev)), "RM_Demodulate_Recover")
+        return Lch
+    B, dev = _rm_dev(rx, (rm.E * m,), torch.float32, "rx")
+    Lch = torch.empty((B, rm.N, q - 1), dtype=torch.float32, device=dev)
+    _check(lib.nbldpc_rm_demodulate_bpsk_recover(rm._h, q, _dev(rx), c_float(sigma), B, c_float(short_llr), _dev(Lch), _stream(stream, dev)),
+           "RM_Demodulate_Recover")
+    return Lch
+
+
+def RM_Demodulate_Combine(rm, q, rx, sigma, L_acc, done=None, short_llr=1.0e4, stream=None, CONSTELLATION=None):
+    """The fused receive of a retransmission: Demodulate at N := E followed by RM_Combine into L_acc [B, N, q-1] under done, bit for
+    bit, from one kernel.  rx as RM_Demodulate_Recover."""
+    q, m = _q_of(q)
+    _check_short_llr(short_llr)
+    B, dev = _rm_dev(L_acc, (rm.N, q - 1), torch.float32, "L_acc")
+    _rm_done(done, B, dev)
+    if CONSTELLATION is not None:
+        _rm_dev(rx, (rm.E, 2), torch.float32, "rx", B, dev)
+        con = _rm_con(CONSTELLATION, q, dev)
+        _check(lib.nbldpc_rm_demodulate_qam_combine(rm._h, q, _dev(rx), _dev(con), c_float(sigma), B, c_float(short_llr), _dev(done), _dev(L_acc),
+                                                    _stream(stream, dev)), "RM_Demodulate_Combine")
+        return L_acc
+    _rm_dev(rx, (rm.E * m,), torch.float32, "rx", B, dev)
+    _check(lib.nbldpc_rm_demodulate_bpsk_combine(rm._h, q, _dev(rx), c_float(sigma), B, c_float(short_llr), _dev(done), _dev(L_acc),
+                                                 _stream(stream, dev)), "RM_Demodulate_Combine")
+    return L_acc
+
+
+def RM_Demodulate_Recover_host(rm, q, rx, sigma, short_llr=1.0e4, CONSTELLATION=None):
+    """The host statement of RM_Demodulate_Recover: Demodulate_host at N := E, then RM_Recover_host."""
+    q, m = _q_of(q)
+    if CONSTELLATION is not None:
+        rx, con = _rm_host(rx, (rm.E, 2), np.float32, "rx"), _rm_con(CONSTELLATION, q)
+        Lch = np.empty((rx.shape[0], rm.N, q - 1), np.float32)
+        _check(lib.nbldpc_rm_demodulate_qam_recover_host(rm._h, q, _np(rx), _np(con), c_float(sigma), rx.shape[0], c_float(short_llr), _np(Lch)),
+               "RM_Demodulate_Recover_host")
+        return Lch
+    rx = _rm_host(rx, (rm.E * m,), np.float32, "rx")
+    Lch = np.empty((rx.shape[0], rm.N, q - 1), np.float32)
+    _check(lib.nbldpc_rm_demodulate_bpsk_recover_host(rm._h, q, _np(rx), c_float(sigma), rx.shape[0], c_float(short_llr), _np(Lch)),
+           "RM_Demodulate_Recover_host")
+    return Lch
+
+
+def RM_Demodulate_Combine_host(rm, q, rx, sigma, L_acc, done=None, short_llr=1.0e4, CONSTELLATION=None):
+    """The host statement of RM_Demodulate_Combine: Demodulate_host at N := E, then RM_Combine_host (L_acc updated in place)."""
+    q, m = _q_of(q)
+    acc = _rm_acc_host(L_acc, rm.N, q - 1)
+    B = acc.shape[0]
+    done = _rm_done_host(done, B)
+    dp = None if done is None else _np(done)
+    if CONSTELLATION is not None:
+        rx, con = _rm_host(rx, (rm.E, 2), np.float32, "rx", B), _rm_con(CONSTELLATION, q)
+        _check(lib.nbldpc_rm_demodulate_qam_combine_host(rm._h, q, _np(rx), _np(con), c_float(sigma), B, c_float(short_llr), dp, _np(acc)),
+               "RM_Demodulate_Combine_host")
+        return acc
+    rx = _rm_host(rx, (rm.E * m,), np.float32, "rx", B)
+    _check(lib.nbldpc_rm_demodulate_bpsk_combine_host(rm._h, q, _np(rx), c_float(sigma), B, c_float(short_llr), dp, _np(acc)),
+           "RM_Demodulate_Combine_host")
+    return acc
+
+
+def Demodulate_NQ(N, q, rx, sigma, stream=None, CONSTELLATION=None):
+    """Demodulate without a code object (nbldpc_demodulate_*_nq): N symbols of GF(q), e.g. the E transmitted symbols of a profile."""
+    q, m = _q_of(q)
+    if CONSTELLATION is not None:
+        B, dev = _rm_dev(rx, (N, 2), torch.float32, "rx")
+        Lch = torch.empty((B, N, q - 1), dtype=torch.float32, device=dev)
+        _check(lib.nbldpc_demodulate_qam_nq(N, q, _dev(rx), _dev(_rm_con(CONSTELLATION, q, dev)), c_float(sigma), B, _dev(Lch), _stream(stream, dev)),
+               "Demodulate_NQ")
+        return Lch
+    B, dev = _rm_dev(rx, (N * m,), torch.float32, "rx")
+    Lch = torch.empty((B, N, q - 1), dtype=torch.float32, device=dev)
+    _check(lib.nbldpc_demodulate_bpsk_nq(N, q, _dev(rx), c_float(sigma), B, _dev(Lch), _stream(stream, dev)), "Demodulate_NQ")
+    return Lch
+
+
+def Demodulate_NQ_host(N, q, rx, sigma, CONSTELLATION=None):
+    """nbldpc_demodulate_*_nq_host: the demodulators' expressions on host arrays, no device needed."""
+    q, m = _q_of(q)
+    if CONSTELLATION is not None:
+        rx, con = _rm_host(rx, (N, 2), np.float32, "rx"), _rm_con(CONSTELLATION, q)
+        Lch = np.empty((rx.shape[0], N, q - 1), np.float32)
+        _check(lib.nbldpc_demodulate_qam_nq_host(N, q, _np(rx), _np(con), c_float(sigma), rx.shape[0], _np(Lch)), "Demodulate_NQ_host")
+        return Lch
+    rx = _rm_host(rx, (N * m,), np.float32, "rx")
+    Lch = np.empty((rx.shape[0], N, q - 1), np.float32)
+    _check(lib.nbldpc_demodulate_bpsk_nq_host(N, q, _np(rx), c_float(sigma), rx.shape[0], _np(Lch)), "Demodulate_NQ_host")
+    return Lch
+
+
+def RM_Force_Shortened_host(rm, info_pos, msg):
+    """nbldpc_rm_force_shortened_host: the forcing step of PN_CodeWords(rate_match=rm) on a host array msg int32 [B, K'] (a copy is
+    returned): message symbol k becomes 0 where info_pos[k] is a shortened position."""
+    info = np.ascontiguousarray(info_pos, np.int32).reshape(-1)
+    msg = _rm_host(msg, (info.size,), np.int32, "msg").copy()
+    _check(lib.nbldpc_rm_force_shortened_host(rm._h, _np(info), info.size, msg.shape[0], _np(msg)), "RM_Force_Shortened_host")
+    return msg
+
+
+def AWGNChannel_RM_GPU(seed, sigma, rm, q, tx_sym, stream=None):
+    """nbldpc_awgn_channel_device_frames at N := E: tx_sym CUDA int32 [B, E] (RM_Select) -> rx CUDA float32 [B, E*m] over BPSK.
+    seed (int32[3]) advances by 4 E m B draws."""
+    if not (isinstance(seed, np.ndarray) and seed.dtype == np.int32 and seed.size == 3):
+        raise ValueError("seed must be an int32 numpy array of 3")
+    q, m = _q_of(q)
+    B, dev = _rm_dev(tx_sym, (rm.E,), torch.int32, "tx_sym")
+    rx = torch.empty((B, rm.E * m), dtype=torch.float32, device=dev)
+    _check(lib.nbldpc_awgn_channel_device_frames(_np(seed), c_float(sigma), _dev(tx_sym), rm.E, m, B, _dev(rx), _stream(stream, dev)), "AWGNChannel_RM_GPU")
+    return rx

@@ -541,8 +541,8 @@ int bldpc_qam_demap_fading_host(const float *rx, const float *gain, const float 
  *   rx           device float [E][F]                                                Channel_Out  device float [N][F]
  * All arrays frame-fastest.  The device calls are asynchronous on `stream` and allocate nothing per call (the profile's device
  * tables are uploaded by the first of them: use a profile from one host thread at a time, like a code object).
- * Out of scope: hard-decision (BSC) input, the position lists of any standard, the GF(q) half.  (Rate matching and HARQ over QAM:
- * "rate matching over QAM" below.) */
+ * Out of scope: hard-decision (BSC) input, the position lists of any standard.  (Rate matching and HARQ over QAM: "rate matching
+ * over QAM" below.  The GF(q) half reads the same profile over code symbols: include/nbldpc.h, "rate matching".) */
 typedef struct bldpc_rm bldpc_rm; /* opaque: the kind of every position, its rank among the transmitted ones, tx_pos; host + device */
 
 /* Positions are codeword positions in [0, N), in any order.  BLDPC_EINVAL: a position out of range, a position repeated or present

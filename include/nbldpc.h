@@ -250,6 +250,81 @@ int nbldpc_statistic_frames(const nbldpc_code *code, const int *DecodeOutput, co
                             int B, long long *counters, void *stream);
 int nbldpc_frame_errors_frames(const nbldpc_code *code, const int *DecodeOutput, const int *CodeWord_sym, int B, int *errs, void *stream);
 
+/* ---- rate matching: shortening, puncturing and HARQ with symbol-LLR combining --------------------------------------------------
+ *
+ * Profile.  A profile is a bldpc_rm (include/bldpc.h, "rate matching" and "HARQ") whose positions are code SYMBOLS: made by
+ * bldpc_rm_create or bldpc_rm_create_circular with N := the number of code symbols.  Same two lists, buffer (the Ncb positions neither
+ * shortened nor punctured, ascending), k0, E, laps <= 8, tx_pos[e] = buffer[(k0 + e) mod Ncb], and the same rule for a position's
+ * contributions: position n of rank r in the buffer is sent at e_0 = (r - k0) mod Ncb and again at e_0 + Ncb, e_0 + 2 Ncb, ... < E
+ * (e_0 < e_1 < ...); a position with e_0 >= E is not reached.  No new object type and no new table: both halves are one library.
+ *
+ * Layout and LLR convention.  V = q - 1.  All arrays are frame-outer.  L_ch[b][n][k-1] = ln P(y | k) - ln P(y | 0), element 0
+ * implicit at 0 -- what nbldpc_demodulate_qam computes, (|y - c0|^2 - |y - ck|^2) / 2 sigma^2 -- so the LLR vectors of independent
+ * transmissions add entry by entry, and a symbol known to be 0 has every entry equal to -short_llr.
+ *
+ * select.   tx_sym[b][e] = CodeWord_sym[b][tx_pos[e]], int32 [B][N] -> [B][E].
+ * recover.  Lrx float [B][E][V] -> L_ch float [B][N][V].  Entry k of a position with contributions is the 32 bits of Lrx[b][e_0][k],
+ *           then + Lrx[b][e_1][k], and so on: fp32 additions in ascending e, not contracted, not reordered.  One contribution is a copy
+ *           (-0.0f and NaN payloads survive).  A punctured position, or one not reached, gets all V entries 0x00000000; a shortened one
+ *           gets all V entries -short_llr.
+ * combine.  L_acc float [B][N][V] is read and written, for every frame with done[b] == 0 (every frame when done == NULL; done DEVICE
+ *           int32 [B]).  A position with contributions becomes ((acc + Lrx[e_0]) + Lrx[e_1]) + ...; one without is left untouched; a
+ *           shortened one becomes -short_llr.  A frame with done[b] != 0 keeps every bit of its N*V floats (they are not read either).
+ * Fused receive.  Lrx[b][e][k-1] is not read but computed from the received sample of transmitted symbol e by the expression of the
+ *           existing demodulator run at N := E (csrc/nbldpc_demod.hpp holds the two expressions; the demodulators and these calls both
+ *           call them): the QAM form from rx float [B][E][2] and constellation DEVICE float [q][2] (nbldpc_demodulate_qam_nq), the BPSK
+ *           form from rx float [B][E*m] (nbldpc_demodulate_bpsk_nq).  Each is, bit for bit, nbldpc_demodulate_*_nq(N := E) followed by
+ *           nbldpc_rm_recover or nbldpc_rm_combine, in one launch whatever the number of laps and with no [B][E][V] array.
+ * Channel.  None is added: a rate-matched transmission is nbldpc_rm_select followed by nbldpc_awgn_channel_device_qam_frames,
+ *           nbldpc_fading_channel_device_qam_frames or nbldpc_awgn_channel_device_frames called with N := E.  Noise is drawn for the
+ *           transmitted symbols only (4 E draws per frame over QAM, 4 E m over BPSK); a frame's draws depend neither on done nor on its
+ *           batch mates.
+ * Shortened encoding.  nbldpc_rm_encode_random applies the message rule of nbldpc_encode_random, forces to 0 every message symbol k
+ *           whose info_pos[k] is a shortened position, and calls nbldpc_encode.  msg is required (DEVICE int32 [B][K'], the messages
+ *           after the forcing).  NBLDPC_EINVAL when the profile's N differs from the code's or a shortened position is not in the
+ *           information set; punctured positions play no part.
+ * Host statements.  The _host calls are the words above in plain C++ on host pointers (csrc/nbldpc_rm_host.hpp, which a stand-alone
+ *           program can compile without the device code); the fused _host calls are demodulate_*_nq_host(N := E) followed by
+ *           recover_host / combine_host.  nbldpc_rm_force_shortened_host is the forcing step alone on msg HOST int32 [B][K'].
+ * Checks.   NBLDPC_EINVAL, and nothing is launched: a null pointer (done excepted); B < 1; q not a power of two in 2 .. 256 (the code
+ *           object of nbldpc_rm_encode_random has q >= 4); short_llr not finite or not > 0; sigma not > 0 (fused calls); N * V or E * V
+ *           above 65535 * 1024 = 67 107 840 entries per frame (the launch indexes a frame's entries by gridDim.y blocks of 1024; B
+ *           itself may be anything up to 2^31 - 1, offsets are 64-bit); for select E, and for nbldpc_rm_encode_random K', above
+ *           65535 * 256 = 16 776 960 (gridDim.y blocks of 256; a profile's own limit on N and E, 65535 * 32, is lower).  The device calls
+ *           are asynchronous on `stream`; nothing is allocated per call beyond the profile's table upload on its first device use.
+ * Additions.  nbldpc_demodulate_qam_nq_host / _bpsk_nq_host below are not part of the rate matcher: they are the host statements of the
+ *           two existing demodulators, added because the fused _host calls are defined as their composition with recover / combine. ---- */
+typedef struct bldpc_rm bldpc_rm;
+
+int nbldpc_rm_select(const bldpc_rm *rm, const int *CodeWord_sym, int B, int *tx_sym, void *stream);
+int nbldpc_rm_recover(const bldpc_rm *rm, int q, const float *Lrx, int B, float short_llr, float *L_ch, void *stream);
+int nbldpc_rm_combine(const bldpc_rm *rm, int q, const float *Lrx, int B, float short_llr, const int *done, float *L_acc, void *stream);
+int nbldpc_rm_demodulate_qam_recover(const bldpc_rm *rm, int q, const float *rx, const float *constellation, float sigma, int B, float short_llr,
+                                     float *L_ch, void *stream);
+int nbldpc_rm_demodulate_qam_combine(const bldpc_rm *rm, int q, const float *rx, const float *constellation, float sigma, int B, float short_llr,
+                                     const int *done, float *L_acc, void *stream);
+int nbldpc_rm_demodulate_bpsk_recover(const bldpc_rm *rm, int q, const float *rx, float sigma, int B, float short_llr, float *L_ch, void *stream);
+int nbldpc_rm_demodulate_bpsk_combine(const bldpc_rm *rm, int q, const float *rx, float sigma, int B, float short_llr, const int *done, float *L_acc,
+                                      void *stream);
+int nbldpc_rm_encode_random(nbldpc_code *code, const bldpc_rm *rm, unsigned long long seed, long long first_frame, int B, int *msg,
+                            int *CodeWord_sym, void *stream);
+
+int nbldpc_rm_select_host(const bldpc_rm *rm, const int *CodeWord_sym, int B, int *tx_sym);
+int nbldpc_rm_recover_host(const bldpc_rm *rm, int q, const float *Lrx, int B, float short_llr, float *L_ch);
+int nbldpc_rm_combine_host(const bldpc_rm *rm, int q, const float *Lrx, int B, float short_llr, const int *done, float *L_acc);
+int nbldpc_rm_demodulate_qam_recover_host(const bldpc_rm *rm, int q, const float *rx, const float *constellation, float sigma, int B,
+                                          float short_llr, float *L_ch);
+int nbldpc_rm_demodulate_qam_combine_host(const bldpc_rm *rm, int q, const float *rx, const float *constellation, float sigma, int B,
+                                          float short_llr, const int *done, float *L_acc);
+int nbldpc_rm_demodulate_bpsk_recover_host(const bldpc_rm *rm, int q, const float *rx, float sigma, int B, float short_llr, float *L_ch);
+int nbldpc_rm_demodulate_bpsk_combine_host(const bldpc_rm *rm, int q, const float *rx, float sigma, int B, float short_llr, const int *done,
+                                           float *L_acc);
+int nbldpc_rm_force_shortened_host(const bldpc_rm *rm, const int *info_pos, int K_info, int B, int *msg);
+
+/* nbldpc_demodulate_qam_nq / _bpsk_nq as host statements (host pointers, the same expressions). */
+int nbldpc_demodulate_qam_nq_host(int N, int q, const float *rx, const float *constellation, float sigma, int B, float *L_ch);
+int nbldpc_demodulate_bpsk_nq_host(int N, int q, const float *rx, float sigma, int B, float *L_ch);
+
 const char *nbldpc_last_error(void);
 
 #ifdef __cplusplus

@@ -9,6 +9,8 @@
     python sweep.py binary --device-channel --quant 6,8,6 --norm8 6 --llr-scale 16 --per-frame --stop-rule syndrome --pn-message --start 2 --stop 3 --step 0.2
     python sweep.py binary --device-channel --per-frame --layered --pn-message --qam 64 --interleave rowcol --fading 16 --harq 0:2160,2160:48,500:2300
     python sweep.py nb --pn-message --qam 64 --fading 16
+    python sweep.py nb --device-channel --pn-message --puncture 88:96
+    python sweep.py nb --device-channel --pn-message --harq 0:72,72:48,24:96
     python -m torch.distributed.run --nproc-per-node N sweep.py binary ...      (frames sharded over N GPUs)
 
 binary: rows `SNR NTF NEF FER BER AverIT FER_F FER_A` as Simulation.cu:272 prints them (Es/N0, seeds 173/173/173,
@@ -91,11 +93,11 @@ def main():
     ap.add_argument("--stop-rule", choices=["prefix", "syndrome"], default=None,
                     help="--layered / --bp: stop rule / meaning of the flag row (default: syndrome with --pn-message, else prefix)")
     ap.add_argument("--as-written", action="store_true", help="decode on the reference's Transform_H table as written (SURVEY F3)")
-    ap.add_argument("--shorten", metavar="SPEC", default=None, help="binary: codeword positions fixed to 0 and not sent, comma-separated half-open "
-                    "ranges a:b (information positions; needs --device-channel)")
-    ap.add_argument("--puncture", metavar="SPEC", default=None, help="binary: codeword positions not sent, same SPEC (needs --device-channel)")
+    ap.add_argument("--shorten", metavar="SPEC", default=None, help="codeword positions (binary: bits, nb: symbols) fixed to 0 and not sent, "
+                    "comma-separated half-open ranges a:b (information positions; needs --device-channel)")
+    ap.add_argument("--puncture", metavar="SPEC", default=None, help="codeword positions (binary: bits, nb: symbols) not sent, same SPEC (needs --device-channel)")
     ap.add_argument("--short-llr", type=float, default=1.0e4, help="--shorten: the decoder's input on a shortened position")
-    ap.add_argument("--harq", metavar="K0:E[,K0:E...]", default=None, help="binary: incremental-redundancy HARQ over BPSK or --qam, one circular-buffer "
+    ap.add_argument("--harq", metavar="K0:E[,K0:E...]", default=None, help="incremental-redundancy HARQ over BPSK or --qam (nb: symbol-LLR combining, K0 and E in symbols, Eb/N0 by default), one circular-buffer "
                     "transmission per K0:E (start in the buffer of the positions left by --shorten / --puncture, length; E above the buffer "
                     "repeats); only unacknowledged frames are sent and decoded again; --snrtype applies, sigma under Eb/N0 from the FIRST "
                     "transmission's rate (needs --device-channel and --fixed or --per-frame)")
@@ -123,8 +125,8 @@ def main():
     elif args.fade_seed is not None:
         ap.error("--fade-seed belongs to --fading")
     if args.harq is not None:
-        if args.which != "binary" or not args.device_channel or args.as_written or not (args.fixed or args.per_frame):
-            ap.error("--harq belongs to the binary sweep with --device-channel and --fixed or --per-frame")
+        if not args.device_channel or (args.which == "binary" and (args.as_written or not (args.fixed or args.per_frame))):
+            ap.error("--harq needs --device-channel and, in the binary sweep, --fixed or --per-frame")
         try:
             harq = parse_harq(args.harq)
         except ValueError as e:
@@ -163,11 +165,12 @@ def main():
                  "--device-channel (there is no host QAM channel on this path)" % args.qam)
     ratematch = args.shorten is not None or args.puncture is not None or args.harq is not None
     if ratematch:
-        if args.which != "binary" or not args.device_channel:
-            ap.error("--shorten / --puncture belong to the binary sweep with --device-channel")
-        try:
-            shorten = parse_positions(args.shorten, args.L * args.Z) if args.shorten else []
-            puncture = parse_positions(args.puncture, args.L * args.Z) if args.puncture else []
+        if not args.device_channel:
+            ap.error("--shorten / --puncture / --harq need --device-channel")
+        try:  # binary: bit positions; nb: symbol positions, checked against N once the matrix header is read
+            rm_N = args.L * args.Z if args.which == "binary" else None
+            shorten = parse_positions(args.shorten, rm_N) if args.shorten else []
+            puncture = parse_positions(args.puncture, rm_N) if args.puncture else []
         except ValueError as e:
             ap.error(str(e))
         if not (args.short_llr > 0 and args.short_llr < float("inf")):
@@ -176,7 +179,12 @@ def main():
     if args.which == "nb":
         mpath = args.nb_matrix if os.path.exists(args.nb_matrix) else os.path.join(nbd, args.nb_matrix)
         with open(mpath) as f:
-            nb_q = int(f.readline().split()[2])  # header "N M q" (Get_H, Simulation.cpp:355)
+            nb_N, _, nb_q = (int(x) for x in f.readline().split()[:3])  # header "N M q" (Get_H, Simulation.cpp:355)
+        if ratematch and max(shorten + puncture + [0]) >= nb_N:
+            ap.error("--shorten / --puncture: a position past N=%d symbols" % nb_N)
+        if ratematch and (args.qam != 2 or fade is not None):
+            ap.error("nb --shorten / --puncture / --harq run over BPSK: the GF(q) simulations have no rate-matched QAM or fading chain "
+                     "(DESIGN.md 4.19)")
         if not os.path.exists(os.path.join(nbd, "GF", "Arith.Table.GF.%d.txt" % nb_q)):
             ap.error("no GF/Arith.Table.GF.%d.txt for the field of %s" % (nb_q, args.nb_matrix))
         if args.qam != 2 and args.qam != nb_q:
@@ -273,7 +281,7 @@ def main():
               PN_Message=1 if args.pn_message else 0, pn_seed=args.pn_seed, log=print if rank == 0 else None, **lay, **mod, **fad)
     else:
         from cuda_ldpc_amd import nbldpc as nb
-        from cuda_ldpc_amd.nb_simulation import sweep
+        from cuda_ldpc_amd.nb_simulation import sweep, sweep_harq
         mul, _, _ = nb.GFInitial(nb_q, os.path.join(nbd, "GF", "Arith.Table.GF.%d.txt" % nb_q))
         code = nb.NBCode(mpath, mul)
         bds = os.path.basename(mpath) == "BDS.576.288.GF.64.txt"
@@ -287,12 +295,29 @@ def main():
         print("# %s N=%d symbols GF(%d), %s, maxIT=%d, %s%s" % (os.path.basename(mpath).replace(".txt", ""), code.N, code.q,
               ["EMS(2,2)", "trellis min-max", "log-QSPA = EMS(q,dc-1)", "layered trellis min-max"][args.method], args.iters or 20,
               "BPSK" if args.qam == 2 else "%d-QAM (Gray), one point per symbol" % args.qam, words) + (fade_words if fade is not None else ""))
-        print("# SNR      NTF   NEF         FER         BER  AverIT")
         dev_ch = args.device_channel or fade is not None  # the fading channel exists on the device only
         nbatch = args.batch if dev_ch else min(args.batch, 1024)  # the host channel is serial: keep its batches small
+        rmk = {}
+        if ratematch:
+            try:
+                rvs = [C.RateMatch.circular(code.N, shorten, puncture, k0, E) for k0, E in harq] if args.harq is not None else [C.RateMatch(code.N, shorten, puncture)]
+            except C._lib.LdpcError as e:
+                ap.error(str(e))
+            print("# rate matching over symbols: %d shortened, %d punctured, buffer Ncb=%d, E=%s transmitted, rate (K' - n_short) / E = %.4f" % (
+                rvs[0].n_short, rvs[0].n_punct, rvs[0].Ncb, args.harq or rvs[0].E, (code.K_info - rvs[0].n_short) / rvs[0].E))
+            rmk = dict(short_llr=args.short_llr)
+        if args.harq is not None:
+            print("# SNR      NTF  FER after each transmission ...  mean transmissions  throughput (information bits per bit sent)  AverIT")
+            sweep_harq(code, rvs, cw, args.start, args.stop, args.step, snrtype=0 if args.snrtype is None else args.snrtype, maxIT=args.iters or 20,
+                       batch=nbatch, max_batches=args.max_batches, decoder_method=args.method,
+                       PN_Message=1 if args.pn_message else 0, pn_seed=args.pn_seed, compact=not args.no_compact, **rmk)
+            return
+        if ratematch:
+            rmk["rate_match"] = rvs[0]
+        print("# SNR      NTF   NEF         FER         BER  AverIT")
         sweep(code, cw, args.start, args.stop, args.step, maxIT=args.iters or 20, batch=nbatch,
               max_frames=None if args.max_batches is None else args.max_batches * nbatch, device_channel=dev_ch,
-              decoder_method=args.method, n_QAM=args.qam, CONSTELLATION=con, PN_Message=1 if args.pn_message else 0, pn_seed=args.pn_seed, **fad)
+              decoder_method=args.method, n_QAM=args.qam, CONSTELLATION=con, PN_Message=1 if args.pn_message else 0, pn_seed=args.pn_seed, **fad, **rmk)
     if world > 1:
         dist.destroy_process_group()
 
