@@ -1,0 +1,300 @@
+// nbldpc_qspa_kernel.hpp -- k_nb_qspa: the FHT sum-product decoder of include/nbldpc.h ("FHT sum-product"), one workgroup = one
+// frame, all iterations on-chip.  Every value is formed by the expressions of nbldpc_qspa_math.hpp in the order of the host statement
+// (nbldpc_qspa_host.hpp), which it equals bit for bit.
+//
+// Lanes along the field.  A vector of q entries lives in W = min(q, 64) lanes of one wave: q = 64 one vector per wave (lane a <->
+// element a), q < 64 64/q vectors per wave (the transform's strides never cross a vector), q = 128 / 256 q/64 entries per lane
+// (entry a + 64 j in register j of lane a: the strides 1 ... 32 cross lanes, 64 and 128 stay in registers; the simpler of the two
+// forms the field wider than a wave could take, no LDS exchange between waves).  Cross-lane partners: strides 1 and 2 DPP quad_perm,
+// 4, 8 and 16 ds_swizzle in bit mode, 32 ds_bpermute; each stage is checked against a plain LDS exchange in
+// tests/cpp/qspa_step_test.hip.  A wave whose last vectors have no variable / row left computes the last one again in their lanes
+// and keeps their stores back, so every cross-lane step runs with all lanes active; loops over a node's edges run to dvmax / dcmax
+// with the absent edges selected away, for the same reason.
+//
+// LDS (qspa_lds_bytes): p [N][q] floats, the message vectors [M][dcmax][q] floats, the decisions [N], the syndrome flag, and
+// TableMultiply as bytes [q][q].  ONE message array, reused in place: c2v -> v2c (phase C: entry a of every vector of a variable is
+// read and written by the same lane) -> the permuted vector -> U (phase D, one wave per row: the wave's LDS operations execute in
+// order, a wave-level fence keeps the compiler to it) -> the transform of out_t -> c2v.  The per-edge stride is q floats, unpadded:
+// ds_read_b32 / ds_write_b32 conflict within a group of 32 lanes on (address / 4) % 32, so a linear access of a vector is free of
+// conflicts for q >= 32 at any stride (32 consecutive floats), and for q = 4 ... 16 the 32/q vectors of a group lie in unrelated
+// slots that no one stride separates; the scatter and gather through TableMultiply hit banks as the permutation has them.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "nbldpc_qspa_math.hpp"
+
+namespace cldpc {
+
+constexpr int kQspaThreads = 1024;
+constexpr int kQspaMaxDv = 8; // == kNbMaxDv: what nbldpc_code_create accepts
+constexpr size_t kQspaMaxLds = 159 * 1024;
+
+struct QspaArgs {
+    const float *Lch; // [B][N][q-1]
+    int *out;         // [B][N]
+    int *iters;       // [B]
+    int *ok;          // [B]
+    float *APP;       // [B][N][q] or nullptr
+    float *c2v;       // [B][M][dc][q] or nullptr
+    const int *vn_w;   // [N]
+    const int *vn_thr; // [N][dv]  row*dc + slot at the other end of each VN edge
+    const int *cn_w;   // [M]
+    const int *cn_gf;  // [M][dc]
+    const int *cn_vn;  // [M][dc]
+    const unsigned char *mul; // [q][q]
+    int N, M, dv, dc, B, max_iter;
+};
+
+__host__ __device__ inline size_t qspa_lds_bytes(int N, int M, int q, int dc)
+{
+    return ((size_t)N * q + (size_t)M * dc * q) * sizeof(float) + ((size_t)N + 4) * sizeof(int) + (size_t)q * q;
+}
+
+// The value of lane ^ S.  All lanes of the vector the lane belongs to are active at every call.
+template <int S> __device__ __forceinline__ float qspa_lane_xor(float v)
+{
+    int x = __builtin_bit_cast(int, v);
+    if constexpr (S == 1) x = __builtin_amdgcn_update_dpp(x, x, 0xB1 /* quad_perm [1,0,3,2] */, 0xf, 0xf, false);
+    else if constexpr (S == 2) x = __builtin_amdgcn_update_dpp(x, x, 0x4E /* quad_perm [2,3,0,1] */, 0xf, 0xf, false);
+    else if constexpr (S < 32) x = __builtin_amdgcn_ds_swizzle(x, (S << 10) | 0x1f); // bit mode: and 0x1f, or 0, xor S
+    else x = __shfl_xor(x, 32, 64);
+    return __builtin_bit_cast(float, x);
+}
+
+template <int Q> struct QspaShape {
+    static constexpr int EPL = Q > 64 ? Q / 64 : 1; // entries per lane
+    static constexpr int W = Q < 64 ? Q : 64;       // lanes per vector
+    static constexpr int VPW = 64 / W;              // vectors per wave
+};
+
+template <int W, int S = 1> __device__ __forceinline__ float qspa_lanes_max(float m)
+{
+    if constexpr (S < W) {
+        m = qspa_max(m, qspa_lane_xor<S>(m));
+        return qspa_lanes_max<W, S * 2>(m);
+    } else
+        return m;
+}
+
+// The maximum of the vector, in every lane of it.
+template <int Q> __device__ __forceinline__ float qspa_vec_max(const float (&v)[QspaShape<Q>::EPL])
+{
+    float m = v[0];
+#pragma unroll
+    for (int j = 1; j < QspaShape<Q>::EPL; j++) m = qspa_max(m, v[j]);
+    return qspa_lanes_max<QspaShape<Q>::W>(m);
+}
+
+template <int Q, int S = 1> __device__ __forceinline__ void qspa_fht_lanes(float (&v)[QspaShape<Q>::EPL], int lane)
+{
+    if constexpr (S < QspaShape<Q>::W) {
+#pragma unroll
+        for (int j = 0; j < QspaShape<Q>::EPL; j++) v[j] = qspa_butterfly(v[j], qspa_lane_xor<S>(v[j]), (lane & S) != 0);
+        qspa_fht_lanes<Q, S * 2>(v, lane);
+    }
+}
+
+// The unscaled transform of the vector: strides 1, 2, 4, ... in that order, across the lanes first, then across a lane's registers.
+template <int Q> __device__ __forceinline__ void qspa_fht(float (&v)[QspaShape<Q>::EPL], int lane)
+{
+    constexpr int EPL = QspaShape<Q>::EPL;
+    qspa_fht_lanes<Q>(v, lane);
+#pragma unroll
+    for (int s = 1; s < EPL; s <<= 1)
+#pragma unroll
+        for (int j = 0; j < EPL; j++)
+            if (!(j & s)) {
+                const float lo = v[j], hi = v[j | s];
+                v[j] = qspa_butterfly(lo, hi, false);
+                v[j | s] = qspa_butterfly(hi, lo, true);
+            }
+}
+
+// Between two LDS accesses of one wave that meet in other lanes' addresses: the hardware executes a wave's LDS operations in order,
+// this keeps the compiler to the program's.
+__device__ __forceinline__ void qspa_wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+template <int Q> __global__ __launch_bounds__(kQspaThreads) void k_nb_qspa(QspaArgs a)
+{
+    constexpr int EPL = QspaShape<Q>::EPL, W = QspaShape<Q>::W, VPW = QspaShape<Q>::VPW, NT = kQspaThreads, NV = NT / 64 * VPW;
+    extern __shared__ float qspa_lds[];
+    const int N = a.N, M = a.M, dv = a.dv, dc = a.dc, TC = M * dc;
+    float *p = qspa_lds, *msg = p + N * Q;
+    int *dec = (int *)(msg + TC * Q), *flag = dec + N;
+    unsigned char *mulb = (unsigned char *)(flag + 4);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, sv = lane / W, el = lane & (W - 1), vbase = wave * VPW;
+    const size_t b = blockIdx.x;
+
+    for (int k = tid; k < Q * Q / 4; k += NT) ((uint32_t *)mulb)[k] = ((const uint32_t *)a.mul)[k];
+    for (int k = tid; k < TC * Q; k += NT) msg[k] = 1.0f; // initial c2v; the slots beyond a row's weight keep it
+    for (int ib = vbase; ib < N; ib += NV) {              // channel vectors
+        const bool valid = ib + sv < N;
+        const int i = valid ? ib + sv : N - 1;
+        const float *L = a.Lch + (b * N + i) * (Q - 1);
+        float x[EPL];
+#pragma unroll
+        for (int j = 0; j < EPL; j++) x[j] = (el + 64 * j) ? L[el + 64 * j - 1] : 0.0f;
+        const float mx = qspa_vec_max<Q>(x);
+#pragma unroll
+        for (int j = 0; j < EPL; j++)
+            if (valid) p[i * Q + el + 64 * j] = qspa_channel_entry(x[j], mx);
+    }
+    __syncthreads();
+
+    int it = 0, good = 0;
+    while (it < a.max_iter) {
+        it++;
+        if (tid == 0) flag[0] = 0;
+        // ---- A: APP and decision of every variable ----
+        for (int ib = vbase; ib < N; ib += NV) {
+            const bool valid = ib + sv < N;
+            const int i = valid ? ib + sv : N - 1, w = a.vn_w[i];
+            float app[EPL], t[EPL];
+#pragma unroll
+            for (int j = 0; j < EPL; j++) app[j] = p[i * Q + el + 64 * j];
+            for (int d = 0; d < dv; d++) {
+                const bool act = d < w;
+                const int slot = act ? a.vn_thr[i * dv + d] : 0;
+#pragma unroll
+                for (int j = 0; j < EPL; j++) t[j] = app[j] * msg[slot * Q + el + 64 * j];
+                const float mx = qspa_vec_max<Q>(t);
+#pragma unroll
+                for (int j = 0; j < EPL; j++) app[j] = act ? qspa_norm_entry(t[j], mx) : app[j];
+            }
+            const float mx = qspa_vec_max<Q>(app);
+            int best = 0;
+#pragma unroll
+            for (int j = EPL - 1; j >= 0; j--) { // first index of the maximum
+                unsigned long long hit = __ballot(app[j] == mx);
+                if constexpr (W < 64) hit = (hit >> (lane & ~(W - 1))) & ((1ull << W) - 1);
+                if (hit) best = 64 * j + __ffsll((long long)hit) - 1;
+            }
+            if (valid && el == 0) dec[i] = best;
+            if (a.APP && valid) {
+#pragma unroll
+                for (int j = 0; j < EPL; j++) a.APP[(b * N + i) * Q + el + 64 * j] = app[j];
+            }
+        }
+        __syncthreads();
+        // ---- B: syndrome ----
+        for (int r = tid; r < M; r += NT) {
+            unsigned s = 0;
+            for (int t = 0; t < a.cn_w[r]; t++) s ^= mulb[dec[a.cn_vn[r * dc + t]] * Q + a.cn_gf[r * dc + t]];
+            if (s) flag[0] = 1;
+        }
+        __syncthreads();
+        if (flag[0] == 0) {
+            good = 1;
+            it--;
+            break;
+        }
+        // ---- C: variable to check, in place (entry a of a variable's vectors belongs to one lane) ----
+        for (int ib = vbase; ib < N; ib += NV) {
+            const bool valid = ib + sv < N;
+            const int i = valid ? ib + sv : N - 1, w = a.vn_w[i];
+            float res[kQspaMaxDv][EPL], t[EPL];
+#pragma unroll
+            for (int d = 0; d < kQspaMaxDv; d++)
+                if (d < dv) {
+#pragma unroll
+                    for (int j = 0; j < EPL; j++) res[d][j] = p[i * Q + el + 64 * j];
+                    for (int d2 = 0; d2 < dv; d2++) {
+                        if (d2 == d) continue;
+                        const bool act = d2 < w;
+                        const int slot = act ? a.vn_thr[i * dv + d2] : 0;
+#pragma unroll
+                        for (int j = 0; j < EPL; j++) t[j] = res[d][j] * msg[slot * Q + el + 64 * j];
+                        const float mx = qspa_vec_max<Q>(t);
+#pragma unroll
+                        for (int j = 0; j < EPL; j++) res[d][j] = act ? qspa_norm_entry(t[j], mx) : res[d][j];
+                    }
+                }
+#pragma unroll
+            for (int d = 0; d < kQspaMaxDv; d++)
+                if (d < dv && d < w && valid) {
+                    const int slot = a.vn_thr[i * dv + d];
+#pragma unroll
+                    for (int j = 0; j < EPL; j++) msg[slot * Q + el + 64 * j] = res[d][j];
+                }
+        }
+        __syncthreads();
+        // ---- D: check nodes, one vector of lanes per row, in place ----
+        for (int rb = vbase; rb < M; rb += NV) {
+            const bool valid = rb + sv < M;
+            const int r = valid ? rb + sv : M - 1, w = a.cn_w[r];
+            float *row = msg + r * dc * Q;
+            for (int t = 0; t < dc; t++) { // v2c -> permuted -> U = FHT / W[0]
+                const bool st = valid && t < w;
+                const int h = t < w ? a.cn_gf[r * dc + t] : 1;
+                float v[EPL];
+                int pm[EPL];
+#pragma unroll
+                for (int j = 0; j < EPL; j++) {
+                    v[j] = row[t * Q + el + 64 * j];
+                    pm[j] = mulb[h * Q + el + 64 * j];
+                }
+                qspa_wave_sync();
+#pragma unroll
+                for (int j = 0; j < EPL; j++)
+                    if (st) row[t * Q + pm[j]] = v[j];
+                qspa_wave_sync();
+#pragma unroll
+                for (int j = 0; j < EPL; j++) v[j] = row[t * Q + el + 64 * j];
+                qspa_fht<Q>(v, lane);
+                const float w0 = __shfl(v[0], lane & ~(W - 1), 64);
+#pragma unroll
+                for (int j = 0; j < EPL; j++)
+                    if (st) row[t * Q + el + 64 * j] = v[j] / w0;
+            }
+            float F[EPL];
+#pragma unroll
+            for (int j = 0; j < EPL; j++) F[j] = 0.0f;
+            for (int t = 0; t < dc; t++) {
+                const bool st = valid && t < w;
+                const int h = t < w ? a.cn_gf[r * dc + t] : 1;
+                float Bk[EPL], o[EPL];
+#pragma unroll
+                for (int j = 0; j < EPL; j++) Bk[j] = 0.0f;
+                for (int s = dc - 1; s > t; s--) // B_{t+1} = U_{t+1} * (U_{t+2} * ( ... U_{w-1}))
+#pragma unroll
+                    for (int j = 0; j < EPL; j++) {
+                        const float us = row[s * Q + el + 64 * j];
+                        Bk[j] = s == w - 1 ? us : s < w - 1 ? us * Bk[j] : Bk[j];
+                    }
+#pragma unroll
+                for (int j = 0; j < EPL; j++) {
+                    const float ut = row[t * Q + el + 64 * j];
+                    o[j] = t == 0 ? Bk[j] : t == w - 1 ? F[j] : F[j] * Bk[j];
+                    F[j] = t == 0 ? ut : F[j] * ut;
+                }
+                qspa_fht<Q>(o, lane);
+#pragma unroll
+                for (int j = 0; j < EPL; j++)
+                    if (st) row[t * Q + el + 64 * j] = qspa_clamp0(o[j]);
+                qspa_wave_sync();
+#pragma unroll
+                for (int j = 0; j < EPL; j++) o[j] = row[t * Q + mulb[h * Q + el + 64 * j]]; // c[a] = w[mul[h][a]]
+                qspa_wave_sync();
+                const float mx = qspa_vec_max<Q>(o);
+#pragma unroll
+                for (int j = 0; j < EPL; j++)
+                    if (st) row[t * Q + el + 64 * j] = qspa_c2v_entry(o[j], mx);
+            }
+        }
+        __syncthreads();
+    }
+    for (int i = tid; i < N; i += NT) a.out[b * N + i] = dec[i];
+    if (tid == 0) {
+        a.iters[b] = it;
+        a.ok[b] = good;
+    }
+    if (a.c2v)
+        for (int k = tid; k < TC * Q; k += NT) a.c2v[b * TC * Q + k] = msg[k];
+}
+
+} // namespace cldpc

@@ -88,6 +88,8 @@ def _decode(code, Lch, decoder_method, EMS_Nm, EMS_Nc, maxIT):
         return nb.Decoding_EMS(code, Lch, EMS_Nm, EMS_Nc, maxIT)
     if decoder_method == 2:
         return nb.Decoding_EMS(code, Lch, code.q, code.dc - 1, maxIT)  # Simulation.cpp:63-66
+    if decoder_method == 4:
+        return nb.Decoding_QSPA(code, Lch, maxIT)  # ours: the reference stops at 3
     return nb.Decoding_TMM(code, Lch, maxIT, layered=(decoder_method == 3))
 
 
@@ -125,7 +127,8 @@ def Simulation_GPU(code, seed, sigma, SIM, CodeWord_sym, EMS_Nm=2, EMS_Nc=2, max
                    PN_Message=0, pn_seed=0, fading=None, rate_match=None, short_llr=1.0e4):
     """One Eb/N0 point. `seed` (int32[3]) advances exactly as far as the reference would have drawn.
     device_channel: generate the noise on the GPU (same uniforms, device libm) instead of the host, frame by frame.
-    decoder_method (define.h:37, Simulation.cpp:54-70): 0 EMS, 1 trellis min-max, 2 log-QSPA = EMS(q, dc-1), 3 layered TMM.
+    decoder_method (define.h:37, Simulation.cpp:54-70): 0 EMS, 1 trellis min-max, 2 log-QSPA = EMS(q, dc-1), 3 layered TMM;
+    4 is ours, the reference stops at 3: the FHT sum-product decoder (Decoding_QSPA; include/nbldpc.h, "FHT sum-product").
     CONSTELLATION (host float32 [q, 2], Get_CONSTELLATION): the n_QAM = q branches of Modulate / AWGNChannel_CPU / Demodulate
     (one constellation point per code symbol) instead of BPSK; the caller passes the sigma of that n_QAM.
     PN_Message=1: every frame sends its own random codeword in place of CodeWord_sym (may be None): frame i of the point is
@@ -191,12 +194,7 @@ def Simulation_GPU(code, seed, sigma, SIM, CodeWord_sym, EMS_Nm=2, EMS_Nc=2, max
             Lch = nb.Demodulate_QAM_Fading(code, rxt, gain, sigma, con_dev)
         else:
             Lch = nb.Demodulate(code, rxt, sigma, CONSTELLATION=con_dev)
-        if decoder_method == 0:
-            r = nb.Decoding_EMS(code, Lch, EMS_Nm, EMS_Nc, maxIT)
-        elif decoder_method == 2:
-            r = nb.Decoding_EMS(code, Lch, code.q, code.dc - 1, maxIT)  # Simulation.cpp:63-66
-        else:
-            r = nb.Decoding_TMM(code, Lch, maxIT, layered=(decoder_method == 3))
+        r = _decode(code, Lch, decoder_method, EMS_Nm, EMS_Nc, maxIT)
         errs = (r["DecodeOutput"] != (cw_dev if PN_Message else cw_dev[None, :])).sum(dim=1).cpu().numpy()
         its = r["iter_number"].cpu().numpy()
         for b in range(batch):  # account in stream order; stop where the reference's while-condition fails

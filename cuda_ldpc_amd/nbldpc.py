@@ -21,6 +21,9 @@ lib.nbldpc_code_create.argtypes = [c_int] * 5 + [c_void_p] * 7 + [ctypes.POINTER
 lib.nbldpc_code_destroy.argtypes = [c_void_p]
 lib.nbldpc_ems_decode_batch.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int] + [c_void_p] * 6
 lib.nbldpc_tmm_decode_batch.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 6
+lib.nbldpc_qspa_decode_batch.argtypes = [c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 6
+lib.nbldpc_qspa_decode_host.argtypes = [c_int] * 5 + [c_void_p] * 8 + [c_int, c_int] + [c_void_p] * 5
+lib.nbldpc_qspa_exp_host.argtypes = [c_void_p, c_int, c_void_p]
 lib.nbldpc_demodulate_bpsk.argtypes = [c_void_p, c_void_p, c_float, c_int, c_void_p, c_void_p]
 lib.nbldpc_statistic.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
 lib.nbldpc_awgn_channel_host.argtypes = [c_void_p, c_float, c_void_p, c_int, c_int, c_void_p]
@@ -211,6 +214,53 @@ def Decoding_TMM(code, L_ch, maxIT=20, layered=False, want_state=False, stream=N
     _check(lib.nbldpc_tmm_decode_batch(code._h, _dev(L_ch), B, 1 if layered else 0, maxIT, _dev(out), _dev(iters), _dev(ok), _dev(LLR),
                                        _dev(c2v), st), "Decoding_TMM")
     return dict(DecodeOutput=out, iter_number=iters, ok=ok, LLR=LLR, L_c2v=c2v)
+
+
+def Decoding_QSPA(code, L_ch, maxIT=20, want_state=False, stream=None):
+    """nbldpc_qspa_decode_batch: the FHT sum-product decoder (include/nbldpc.h, "FHT sum-product"; ours, the reference has none) for
+    a batch.  Returns the dict of Decoding_TMM: LLR [B,N,q] holds the APP probability vectors of the last executed iteration,
+    L_c2v [B,M,dc,q] the check-to-variable vectors, all q entries each, max-normalised with the floor 2^-40."""
+    if not (L_ch.is_cuda and L_ch.dtype == torch.float32 and L_ch.is_contiguous()):
+        raise ValueError("L_ch must be a contiguous CUDA float32 tensor")
+    if L_ch.dim() != 3 or L_ch.shape[1] != code.N or L_ch.shape[2] != code.q - 1:
+        raise ValueError("L_ch must be [B, N=%d, q-1=%d]" % (code.N, code.q - 1))
+    B, dev = int(L_ch.shape[0]), L_ch.device
+    out = torch.empty((B, code.N), dtype=torch.int32, device=dev)
+    iters = torch.empty(B, dtype=torch.int32, device=dev)
+    ok = torch.empty(B, dtype=torch.int32, device=dev)
+    APP = torch.empty((B, code.N, code.q), dtype=torch.float32, device=dev) if want_state else None
+    c2v = torch.empty((B, code.M, code.dc, code.q), dtype=torch.float32, device=dev) if want_state else None
+    st = c_void_p((stream or torch.cuda.current_stream(dev)).cuda_stream)
+    _check(lib.nbldpc_qspa_decode_batch(code._h, _dev(L_ch), B, maxIT, _dev(out), _dev(iters), _dev(ok), _dev(APP), _dev(c2v), st), "Decoding_QSPA")
+    return dict(DecodeOutput=out, iter_number=iters, ok=ok, LLR=APP, L_c2v=c2v)
+
+
+def Decoding_QSPA_host(code, L_ch, maxIT=20, want_state=False, TableMultiply=None):
+    """nbldpc_qspa_decode_host: the host statement of Decoding_QSPA on host arrays, no device needed.  code: an NBMatrix or NBCode
+    (TableMultiply: the code's unless given); L_ch float32 [B, N, q-1].  Returns the same dict, numpy arrays."""
+    mul = np.ascontiguousarray(code.TableMultiply if TableMultiply is None else TableMultiply, np.uint32)
+    if mul.shape != (code.q, code.q):
+        raise ValueError("TableMultiply must be [q, q]")
+    L = np.ascontiguousarray(L_ch, np.float32)
+    if L.ndim != 3 or L.shape[0] <= 0 or L.shape[1:] != (code.N, code.q - 1):
+        raise ValueError("L_ch must be float32 [B, N=%d, q-1=%d]" % (code.N, code.q - 1))
+    B = L.shape[0]
+    out, iters, ok = np.empty((B, code.N), np.int32), np.empty(B, np.int32), np.empty(B, np.int32)
+    APP = np.empty((B, code.N, code.q), np.float32) if want_state else None
+    c2v = np.empty((B, code.M, code.dc, code.q), np.float32) if want_state else None
+    _check(lib.nbldpc_qspa_decode_host(code.N, code.M, code.q, code.dv, code.dc, _np(code.vn_weight), _np(code.vn_linkCNs), _np(code.vn_linkCNs_GF),
+                                       _np(code.cn_weight), _np(code.cn_linkVNs), _np(code.cn_linkVNs_GF), _np(mul), _np(L), B, maxIT, _np(out),
+                                       _np(iters), _np(ok), None if APP is None else _np(APP), None if c2v is None else _np(c2v)),
+           "Decoding_QSPA_host")
+    return dict(DecodeOutput=out, iter_number=iters, ok=ok, LLR=APP, L_c2v=c2v)
+
+
+def QSPA_Exp_host(x):
+    """nbldpc_qspa_exp_host: the decoder's shared exponential (x <= 0) on a host array, elementwise."""
+    x = np.ascontiguousarray(x, np.float32)
+    y = np.empty_like(x)
+    _check(lib.nbldpc_qspa_exp_host(_np(x), x.size, _np(y)), "QSPA_Exp_host")
+    return y
 
 
 def Get_CONSTELLATION(path, n_QAM):

@@ -64,7 +64,7 @@ int nbldpc_code_destroy(nbldpc_code *code);
 
 /* Name of the kernel the last decode call on this code launched (static string): "k_nb_ems2" = two frames in flight per workgroup,
  * "k_nb_ems" / "k_nb_ems_wide" one frame per workgroup (+ " (frames from a counter)": persistent workgroups), "k_nb_ems_hbm" the
- * workspace kernel, "k_nb_tmm…" the trellis decoders.  The counterpart of bldpc_last_kernel (include/bldpc.h); the reference has no
+ * workspace kernel, "k_nb_tmm…" the trellis decoders, "k_nb_qspa" the FHT sum-product decoder.  The counterpart of bldpc_last_kernel (include/bldpc.h); the reference has no
  * equivalent -- its kernels are fixed at compile time (myNBLDPC/src/Decode_GPU.cu:138-356). */
 const char *nbldpc_last_kernel(const nbldpc_code *code);
 
@@ -324,6 +324,54 @@ int nbldpc_rm_force_shortened_host(const bldpc_rm *rm, const int *info_pos, int 
 /* nbldpc_demodulate_qam_nq / _bpsk_nq as host statements (host pointers, the same expressions). */
 int nbldpc_demodulate_qam_nq_host(int N, int q, const float *rx, const float *constellation, float sigma, int B, float *L_ch);
 int nbldpc_demodulate_bpsk_nq_host(int N, int q, const float *rx, float sigma, int B, float *L_ch);
+
+/* ---- FHT sum-product (QSPA): belief propagation proper over GF(2^m), the check node in the Walsh-Hadamard domain ---------------
+ *
+ * The reference has no such decoder (its decoder_method stops at 3; 2, "log-QSPA", is max-log).  This one is ours, and the host
+ * statement nbldpc_qspa_decode_host, the words below in serial C++ (csrc/nbldpc_qspa_host.hpp), is its definition: the kernel equals
+ * it bit for bit.  Every arithmetic step is one IEEE fp32 operation (+, -, *, /, compare), never contracted, in the order given;
+ * nothing calls expf, logf or another library transcendental (csrc/nbldpc_qspa_math.hpp holds the expressions both sides call).
+ *
+ * Input.  L_ch float [B][N][q-1] as every decoder here takes it: x_0 = 0, x_k = L_ch[k-1] = ln P(k) / P(0).  Any finite values,
+ * the +-1e4 and +0.0 of the rate matcher included; NaN and infinities are not inputs.
+ * Probability vectors.  q fp32 entries, the largest exactly 1, none below kQspaFloor = 2^-40:
+ *     norm(v)[a] = max(v[a] / max(v), 2^-40)                  max(v): the largest entry (order-independent), the division IEEE.
+ * A product of two such vectors has a maximum of at least 2^-80, so no vector underflows to zero.
+ * Channel vector.  p[a] = max(qspa_exp(x_a - max_a x_a), 2^-40), where qspa_exp(x) for x <= 0 is: 0 for x < -87 (or not ordered);
+ *     else n = rintf(x * 0x1.715476p+0f), r = (x - n * 0x1.62e4p-1f) - n * 0x1.7f7d1cp-20f,
+ *     poly = ((((((0x1.6d4932p-10f r + 0x1.12107cp-7f) r + 0x1.5554e4p-5f) r + 0x1.5554d8p-3f) r + 0x1p-1f) r + 1) r + 1),
+ *     qspa_exp = poly * 2^n, the power of two built from its exponent bits.  qspa_exp(0) == 1; every result is 0 or normal.
+ * Schedule.  Flooding, with the loop of Decoding_EMS (LDPC_Decoder.cpp:197-238).  All c2v start as all ones.  Iteration
+ *     iter_number = 1, 2, ...: for every variable app = p, then for its edges d ascending app = norm(app * c2v_d); the decision is
+ *     the first index of app's maximum; then the GF(q) syndrome over all rows, XOR_t TableMultiply[decision][h_t].  Zero syndrome:
+ *     ok = 1, iter_number - 1 is reported, the frame is done.  Otherwise the messages below are formed, and after maxIT iterations
+ *     ok = 0, iter_number = maxIT, DecodeOutput holds the last decision.
+ * Variable to check.  v2c_d = p, then for d' ascending, d' != d: v2c_d = norm(v2c_d * c2v_d').
+ * Check node.  For the edge in slot t of a row, coefficient h: u[TableMultiply[h][a]] = v2c[a]; W = FHT(u); U_t = W / W[0] entry by
+ *     entry (U_t[0] == 1).  FHT: log2 q stages with strides 1, 2, 4, ... in that order; in a stage every pair (i, i + stride) with
+ *     bit `stride` of i clear becomes (lo + hi, lo - hi).  Over the row's slots in order: F_0 = U_0, F_t = F_{t-1} * U_t;
+ *     B_{w-1} = U_{w-1}, B_t = U_t * B_{t+1}; out_0 = B_1, out_{w-1} = F_{w-2}, else out_t = F_{t-1} * B_{t+1} (a row of weight 2
+ *     passes the other edge's U through).  wv = max(FHT(out_t), 0), unscaled (norm removes the 1/q); c[a] = wv[TableMultiply[h][a]];
+ *     c2v_t = norm(c), or all ones if max(c) == 0.
+ * Outputs.  DecodeOutput, iter_number, ok as nbldpc_ems_decode_batch.  Optional APP float [B][N][q]: app of the last executed
+ *     iteration; optional c2v float [B][M][dcmax][q]: the check-to-variable vectors after the call (those the last APP was formed
+ *     from when ok = 1, those of iteration maxIT when ok = 0); slots beyond a row's weight hold the initial ones.  All q entries.
+ * Refusals.  NBLDPC_EINVAL: a null pointer (APP and c2v excepted), B < 1, maxIT < 1, a graph whose two views differ.
+ *     NBLDPC_EUNSUPPORTED: an edge coefficient 0 (the permutation would not be one; as nbldpc_tmm_decode_batch refuses it); q not a
+ *     power of two with 4 <= q <= 256; and, nbldpc_qspa_decode_batch only, a code whose frame state exceeds the kernel's LDS:
+ *         4 (N q + M dcmax q) + 4 (N + 4) + q^2  <=  159 * 1024 bytes
+ *     (p, one message array reused in place, decisions and flag, TableMultiply as bytes).  BDS.576.288.GF.64.txt takes 78 224 bytes;
+ *     Tanner_74_9_Z128_GF16.txt and LDPC_N576_K480_GF256_exp.txt do not fit.  Nothing is launched on a refusal.  There is no
+ *     workspace tier: a code that does not fit is decoded by the host statement or not at all.
+ * nbldpc_qspa_decode_batch: all pointers DEVICE memory, asynchronous on `stream`, return codes as nbldpc_ems_decode_batch; one
+ *     workgroup per frame (k_nb_qspa in nbldpc_last_kernel).  nbldpc_qspa_decode_host: HOST pointers, the node arrays and
+ *     TableMultiply of nbldpc_code_create, serial.  nbldpc_qspa_exp_host: y[i] = qspa_exp(x[i]), for the tests. ---- */
+int nbldpc_qspa_decode_batch(nbldpc_code *code, const float *L_ch, int B, int maxIT, int *DecodeOutput, int *iter_number, int *ok,
+                             float *APP, float *c2v, void *stream);
+int nbldpc_qspa_decode_host(int N, int M, int q, int dvmax, int dcmax, const int *vn_weight, const int *vn_linkCNs, const int *vn_linkCNs_GF,
+                            const int *cn_weight, const int *cn_linkVNs, const int *cn_linkVNs_GF, const unsigned *TableMultiply,
+                            const float *L_ch, int B, int maxIT, int *DecodeOutput, int *iter_number, int *ok, float *APP, float *c2v);
+int nbldpc_qspa_exp_host(const float *x, int n, float *y);
 
 const char *nbldpc_last_error(void);
 
