@@ -16,6 +16,8 @@ struct nbldpc_code {
     int *d_cn_hinv = nullptr, *d_row_order = nullptr, *d_level_begin = nullptr;
     int levels = 0;
     bool tmm_ok = false;
+    int qspa_layered_threads = 0; // k_nb_qspa_layered: threads per workgroup (256 / 512 / 1024), fixed at create time
+    bool row_repeats = false;     // a row lists one variable in two slots: refused by nbldpc_qspa_layered_decode_batch
     int zero_coeff = 0; // an edge with coefficient 0 exists (EMS only, see nb_tables_build)
     const char *last_kernel = "none"; // nbldpc_last_kernel
     int persist_grid = 0; // k_nb_ems / k_nb_ems_wide: workgroups that fill the chip once (CUs x workgroups per CU)

@@ -19,6 +19,8 @@
 #include "nbldpc_tmm_kernel.hpp"
 #include "nbldpc_wide_kernel.hpp"
 #include "nbldpc_hbm_kernel.hpp"
+#include "nbldpc_qspa_host.hpp"
+#include "nbldpc_qspa_kernel.hpp"
 
 namespace cldpc {
 
@@ -26,6 +28,7 @@ struct NbSwitches {
     bool force_hbm = false;  // NBLDPC_FORCE_HBM: the workspace kernel on a code the fused kernels take
     bool no_pipe = false;    // NBLDPC_NO_PIPE: k_nb_ems2 not offered
     bool no_persist = false; // NBLDPC_NO_PERSIST: one workgroup per frame even where the persistent form exists
+    int qspa_layered_threads = 0; // NBLDPC_QSPA_LAYERED_THREADS = 256 | 512 | 1024: k_nb_qspa_layered's workgroup pinned (else by the widest level)
 };
 
 // The only getenv of the GF(q) family.
@@ -35,6 +38,10 @@ inline NbSwitches nb_switches_from_env()
     sw.force_hbm = getenv("NBLDPC_FORCE_HBM") != nullptr;
     sw.no_pipe = getenv("NBLDPC_NO_PIPE") != nullptr;
     sw.no_persist = getenv("NBLDPC_NO_PERSIST") != nullptr;
+    if (const char *v = getenv("NBLDPC_QSPA_LAYERED_THREADS")) {
+        const int nt = atoi(v);
+        if (nt == 256 || nt == 512 || nt == 1024) sw.qspa_layered_threads = nt; // anything else: the rule
+    }
     return sw;
 }
 
@@ -53,8 +60,10 @@ struct NbTables {
     bool hbm = false;     // the workspace kernel decodes this code (see nbldpc_code::hbm)
     size_t lds_bytes = 0; // dynamic LDS of the fused kernel (0: q has none)
     size_t pipe_lds = 0;  // k_nb_ems2 is offered with this much LDS if the device can hold a workgroup of it (0: not offered)
-    int zero_coeff = 0, levels = 0;
+    int zero_coeff = 0, levels = 0, widest_level = 0; // widest_level: the most rows any level holds
+    int qspa_layered_threads = 0;                     // workgroup of k_nb_qspa_layered: the switch, else the rule of qspa_layered_threads()
     bool tmm_ok = false;
+    bool row_repeats = false; // a row lists one variable in two slots: the layered sum-product decoder refuses the code
     std::vector<int> vn_thr, cn_src;              // [N][dv] CN thread of each VN edge, [M][dc] VN edge of each CN slot
     std::vector<unsigned char> mulb;              // TableMultiply as bytes
     std::vector<int> hinv, row_order, level_begin; // trellis decoders: [M][dc] inverse coefficients, rows by level, [levels + 1]
@@ -155,6 +164,9 @@ inline int nb_tables_build(int N, int M, int q, int dv, int dc, const int *vn_w,
     t.level_begin.assign(t.levels + 1, 0);
     for (int i = 0; i < M; i++) t.level_begin[level[i] + 1]++;
     for (int l = 0; l < t.levels; l++) t.level_begin[l + 1] += t.level_begin[l];
+    for (int l = 0; l < t.levels; l++) t.widest_level = std::max(t.widest_level, t.level_begin[l + 1] - t.level_begin[l]);
+    t.qspa_layered_threads = sw.qspa_layered_threads ? sw.qspa_layered_threads : qspa_layered_threads(q, t.widest_level);
+    t.row_repeats = qspa_row_repeats_variable(M, dc, cn_w, cn_vn);
     t.tmm_ok = (q == 16 || q == 32 || q == 64) && inv_ok && dc <= kTmmMaxW && t.levels <= 63 && M <= kTmmThreads && // the trellis kernels keep a vector in one wave
                tmm_lds_bytes(N, M, q, dv, dc, false) <= 160 * 1024;
     // the two-frame pipeline (nbldpc_pipe_kernel.hpp): GF(64), column weights <= 2, no zero coefficient, the columns fit its A/S/B waves
@@ -173,6 +185,7 @@ inline int nb_tables_upload(nbldpc_code *c, const NbTables &t)
 {
     c->N = t.N; c->M = t.M; c->q = t.q; c->m = t.m; c->dv = t.dv; c->dc = t.dc;
     c->lds_bytes = t.lds_bytes; c->hbm = t.hbm; c->zero_coeff = t.zero_coeff; c->levels = t.levels; c->tmm_ok = t.tmm_ok;
+    c->qspa_layered_threads = t.qspa_layered_threads; c->row_repeats = t.row_repeats;
     c->h_cn_w.assign(t.cn_w, t.cn_w + t.M);
     c->h_cn_vn.assign(t.cn_vn, t.cn_vn + (size_t)t.M * t.dc);
     c->h_cn_gf.assign(t.cn_gf, t.cn_gf + (size_t)t.M * t.dc);
@@ -181,6 +194,10 @@ inline int nb_tables_upload(nbldpc_code *c, const NbTables &t)
     const auto bytes = t.bytes();
     for (size_t i = 0; i < ptrs.size(); i++)
         if (int r = bytes[i].n ? upload(ptrs[i], bytes[i].p, bytes[i].n) : 0) return r;
+    if (!t.tmm_ok) { // the level tables for every code: the layered sum-product kernel walks them whether or not the trellis kernels are offered
+        if (int r = upload((void **)&c->d_row_order, t.row_order.data(), (size_t)t.M * sizeof(int))) return r;
+        if (int r = upload((void **)&c->d_level_begin, t.level_begin.data(), t.level_begin.size() * sizeof(int))) return r;
+    }
     return NBLDPC_OK;
 }
 

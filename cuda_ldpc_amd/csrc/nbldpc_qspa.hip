@@ -42,7 +42,8 @@ extern "C" int nbldpc_qspa_decode_batch(nbldpc_code *c, const float *Lch, int B,
     QspaArgs a;
     a.Lch = Lch; a.out = out; a.iters = iters; a.ok = ok; a.APP = APP; a.c2v = c2v;
     a.vn_w = c->d_vn_w; a.vn_thr = c->d_vn_thr; a.cn_w = c->d_cn_w; a.cn_gf = c->d_cn_gf; a.cn_vn = c->d_cn_vn; a.mul = c->d_mul;
-    a.N = c->N; a.M = c->M; a.dv = c->dv; a.dc = c->dc; a.B = B; a.max_iter = maxIT;
+    a.row_order = nullptr; a.level_begin = nullptr;
+    a.N = c->N; a.M = c->M; a.dv = c->dv; a.dc = c->dc; a.B = B; a.max_iter = maxIT; a.levels = 0;
     c->last_kernel = "k_nb_qspa";
     hipLaunchKernelGGL(k, dim3(B), dim3(kQspaThreads), lds, (hipStream_t)stream, a); // one workgroup per frame, whatever B
     CLDPC_HIP(hipGetLastError(), NBLDPC_EHIP);

@@ -1,6 +1,7 @@
-// nbldpc_qspa_host.hpp -- the host statement of the FHT sum-product decoder: the words of include/nbldpc.h ("FHT sum-product") in
-// plain serial C++ on host pointers, with the expressions of nbldpc_qspa_math.hpp.  It is the definition k_nb_qspa is tested
-// against.  No HIP call and no device code: a stand-alone program compiles it (tests/cpp/nb_qspa_host_test.hip).
+// nbldpc_qspa_host.hpp -- the host statement of the FHT sum-product decoder: the words of include/nbldpc.h ("FHT sum-product" and
+// "FHT sum-product, layered schedule") in plain serial C++ on host pointers, with the expressions of nbldpc_qspa_math.hpp.  It is the
+// definition k_nb_qspa and k_nb_qspa_layered are tested against.  No HIP call and no device code: a stand-alone program compiles it
+// (tests/cpp/nb_qspa_host_test.hip, tests/cpp/nb_qspa_layered_host_test.hip).
 #pragma once
 #include <vector>
 
@@ -48,9 +49,10 @@ inline int qspa_check_dims(int N, int M, int q, int dv, int dc, const char **why
 }
 
 // One frame.  Lch [N][q-1]; out [N]; APP [N][q] or null; c2v [M][dc][q] or null.  The graph was validated by the caller.
+// layered: the part of an iteration after the syndrome check runs row by row, each row on the messages as they stand.
 inline void qspa_decode_frame_host(int N, int M, int q, int dv, int dc, const int *vn_w, const int *vn_slot /* [N][dv]: row*dc + slot */,
                                    const int *cn_w, const int *cn_vn, const int *cn_gf, const unsigned *mul, const float *Lch, int maxIT,
-                                   int *out, int *iter_number, int *ok, float *APP, float *c2v_out)
+                                   int *out, int *iter_number, int *ok, float *APP, float *c2v_out, bool layered = false)
 {
 #pragma clang fp contract(off)
     std::vector<float> p((size_t)N * q), msg((size_t)M * dc * q, 1.0f), app((size_t)N * q), tmp(q), F(q), Bk((size_t)dc * q), U((size_t)dc * q);
@@ -79,7 +81,7 @@ inline void qspa_decode_frame_host(int N, int M, int q, int dv, int dc, const in
             zero = s == 0;
         }
         if (zero) { good = 1; it--; break; }
-        for (int i = 0; i < N; i++) { // variable to check, into the edges' slots (read all of a variable's c2v first)
+        for (int i = 0; i < N && !layered; i++) { // variable to check, into the edges' slots (read all of a variable's c2v first)
             const int w = vn_w[i];
             std::vector<float> in((size_t)w * q);
             for (int d = 0; d < w; d++)
@@ -93,6 +95,13 @@ inline void qspa_decode_frame_host(int N, int M, int q, int dv, int dc, const in
         }
         for (int r = 0; r < M; r++) { // check nodes
             const int w = cn_w[r];
+            for (int t = 0; t < w && layered; t++) { // this row's v2c from p and the other edges' c2v as they stand, into its own slots
+                const int i = cn_vn[r * dc + t], self = r * dc + t;
+                for (int e = 0; e < q; e++) tmp[e] = p[(size_t)i * q + e];
+                for (int d2 = 0; d2 < vn_w[i]; d2++)
+                    if (vn_slot[i * dv + d2] != self) qspa_mul_norm_host(tmp.data(), &msg[(size_t)vn_slot[i * dv + d2] * q], q);
+                for (int e = 0; e < q; e++) msg[(size_t)self * q + e] = tmp[e];
+            }
             for (int t = 0; t < w; t++) {
                 const float *v = &msg[((size_t)r * dc + t) * q];
                 const unsigned *mh = mul + (size_t)cn_gf[r * dc + t] * q;
@@ -127,10 +136,20 @@ inline void qspa_decode_frame_host(int N, int M, int q, int dv, int dc, const in
         for (size_t k = 0; k < (size_t)M * dc * q; k++) c2v_out[k] = msg[k];
 }
 
-// nbldpc_qspa_decode_host without the error text: the code, and *why for nbldpc_last_error.
+// A row that lists one variable in two slots: "the other edges of the variable" is not defined for it (layered schedule).
+inline bool qspa_row_repeats_variable(int M, int dc, const int *cn_w, const int *cn_vn)
+{
+    for (int r = 0; r < M; r++)
+        for (int t = 1; t < cn_w[r]; t++)
+            for (int s = 0; s < t; s++)
+                if (cn_vn[r * dc + s] == cn_vn[r * dc + t]) return true;
+    return false;
+}
+
+// nbldpc_qspa_decode_host / nbldpc_qspa_layered_decode_host without the error text: the code, and *why for nbldpc_last_error.
 inline int qspa_decode_host(int N, int M, int q, int dv, int dc, const int *vn_w, const int *vn_cn, const int *vn_gf, const int *cn_w,
                             const int *cn_vn, const int *cn_gf, const unsigned *mul, const float *Lch, int B, int maxIT, int *out, int *iters,
-                            int *ok, float *APP, float *c2v, const char **why)
+                            int *ok, float *APP, float *c2v, const char **why, bool layered = false)
 {
     *why = "";
     if (!vn_w || !vn_cn || !vn_gf || !cn_w || !cn_vn || !cn_gf || !mul || !Lch || !out || !iters || !ok) { *why = "null argument"; return NBLDPC_EINVAL; }
@@ -158,9 +177,10 @@ inline int qspa_decode_host(int N, int M, int q, int dv, int dc, const int *vn_w
             slot[(size_t)i * dv + d] = cn * dc + s;
         }
     }
+    if (layered && qspa_row_repeats_variable(M, dc, cn_w, cn_vn)) { *why = "a row lists one variable in two slots: the layered schedule has no other-edges rule for it"; return NBLDPC_EUNSUPPORTED; }
     for (int b = 0; b < B; b++)
         qspa_decode_frame_host(N, M, q, dv, dc, vn_w, slot.data(), cn_w, cn_vn, cn_gf, mul, Lch + (size_t)b * N * (q - 1), maxIT, out + (size_t)b * N,
-                               iters + b, ok + b, APP ? APP + (size_t)b * N * q : nullptr, c2v ? c2v + (size_t)b * M * dc * q : nullptr);
+                               iters + b, ok + b, APP ? APP + (size_t)b * N * q : nullptr, c2v ? c2v + (size_t)b * M * dc * q : nullptr, layered);
     return NBLDPC_OK;
 }
 

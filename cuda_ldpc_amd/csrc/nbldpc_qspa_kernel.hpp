@@ -1,6 +1,7 @@
 // nbldpc_qspa_kernel.hpp -- k_nb_qspa: the FHT sum-product decoder of include/nbldpc.h ("FHT sum-product"), one workgroup = one
 // frame, all iterations on-chip.  Every value is formed by the expressions of nbldpc_qspa_math.hpp in the order of the host statement
-// (nbldpc_qspa_host.hpp), which it equals bit for bit.
+// (nbldpc_qspa_host.hpp), which it equals bit for bit.  k_nb_qspa_layered ("FHT sum-product, layered schedule") is the same frame
+// body with phases C and D replaced by a walk over the rows' dependency levels; both call one check-row function.
 //
 // Lanes along the field.  A vector of q entries lives in W = min(q, 64) lanes of one wave: q = 64 one vector per wave (lane a <->
 // element a), q < 64 64/q vectors per wave (the transform's strides never cross a vector), q = 128 / 256 q/64 entries per lane
@@ -43,7 +44,8 @@ struct QspaArgs {
     const int *cn_gf;  // [M][dc]
     const int *cn_vn;  // [M][dc]
     const unsigned char *mul; // [q][q]
-    int N, M, dv, dc, B, max_iter;
+    const int *row_order, *level_begin; // layered: rows sorted by level [M], first row of each level [levels+1] (global memory)
+    int N, M, dv, dc, B, max_iter, levels;
 };
 
 __host__ __device__ inline size_t qspa_lds_bytes(int N, int M, int q, int dc)
@@ -119,9 +121,79 @@ __device__ __forceinline__ void qspa_wave_sync()
     __builtin_amdgcn_wave_barrier();
 }
 
-template <int Q> __global__ __launch_bounds__(kQspaThreads) void k_nb_qspa(QspaArgs a)
+// The check-node rule on one row, in place, by the W lanes of one vector: row [dc][Q] holds the row's v2c and leaves holding its c2v;
+// gf the row's coefficients, w its weight.  v2c -> the permuted vector -> U = FHT / W[0], then the forward / backward products, the
+// second transform, the clamp, the inverse permutation and norm.  Lanes with valid == false (no row of their own: they recompute
+// another one) keep every store back.  All lanes of the wave are active at every call.
+template <int Q>
+__device__ __forceinline__ void qspa_check_row(float *row, const int *gf, int w, bool valid, int dc, const unsigned char *mulb, int lane, int el)
 {
-    constexpr int EPL = QspaShape<Q>::EPL, W = QspaShape<Q>::W, VPW = QspaShape<Q>::VPW, NT = kQspaThreads, NV = NT / 64 * VPW;
+    constexpr int EPL = QspaShape<Q>::EPL, W = QspaShape<Q>::W;
+    for (int t = 0; t < dc; t++) { // v2c -> permuted -> U = FHT / W[0]
+        const bool st = valid && t < w;
+        const int h = t < w ? gf[t] : 1;
+        float v[EPL];
+        int pm[EPL];
+#pragma unroll
+        for (int j = 0; j < EPL; j++) {
+            v[j] = row[t * Q + el + 64 * j];
+            pm[j] = mulb[h * Q + el + 64 * j];
+        }
+        qspa_wave_sync();
+#pragma unroll
+        for (int j = 0; j < EPL; j++)
+            if (st) row[t * Q + pm[j]] = v[j];
+        qspa_wave_sync();
+#pragma unroll
+        for (int j = 0; j < EPL; j++) v[j] = row[t * Q + el + 64 * j];
+        qspa_fht<Q>(v, lane);
+        const float w0 = __shfl(v[0], lane & ~(W - 1), 64);
+#pragma unroll
+        for (int j = 0; j < EPL; j++)
+            if (st) row[t * Q + el + 64 * j] = v[j] / w0;
+    }
+    float F[EPL];
+#pragma unroll
+    for (int j = 0; j < EPL; j++) F[j] = 0.0f;
+    for (int t = 0; t < dc; t++) {
+        const bool st = valid && t < w;
+        const int h = t < w ? gf[t] : 1;
+        float Bk[EPL], o[EPL];
+#pragma unroll
+        for (int j = 0; j < EPL; j++) Bk[j] = 0.0f;
+        for (int s = dc - 1; s > t; s--) // B_{t+1} = U_{t+1} * (U_{t+2} * ( ... U_{w-1}))
+#pragma unroll
+            for (int j = 0; j < EPL; j++) {
+                const float us = row[s * Q + el + 64 * j];
+                Bk[j] = s == w - 1 ? us : s < w - 1 ? us * Bk[j] : Bk[j];
+            }
+#pragma unroll
+        for (int j = 0; j < EPL; j++) {
+            const float ut = row[t * Q + el + 64 * j];
+            o[j] = t == 0 ? Bk[j] : t == w - 1 ? F[j] : F[j] * Bk[j];
+            F[j] = t == 0 ? ut : F[j] * ut;
+        }
+        qspa_fht<Q>(o, lane);
+#pragma unroll
+        for (int j = 0; j < EPL; j++)
+            if (st) row[t * Q + el + 64 * j] = qspa_clamp0(o[j]);
+        qspa_wave_sync();
+#pragma unroll
+        for (int j = 0; j < EPL; j++) o[j] = row[t * Q + mulb[h * Q + el + 64 * j]]; // c[a] = w[mul[h][a]]
+        qspa_wave_sync();
+        const float mx = qspa_vec_max<Q>(o);
+#pragma unroll
+        for (int j = 0; j < EPL; j++)
+            if (st) row[t * Q + el + 64 * j] = qspa_c2v_entry(o[j], mx);
+    }
+}
+
+// One frame by one workgroup of NT threads, all iterations: the body of both kernels.  LAYERED false: phases C and D over all
+// variables and all rows (k_nb_qspa, NT a constant).  LAYERED true: the level sweep of k_nb_qspa_layered (NT = blockDim.x).
+template <int Q, bool LAYERED> __device__ __forceinline__ void qspa_decode_frame(const QspaArgs &a, const int NT)
+{
+    constexpr int EPL = QspaShape<Q>::EPL, W = QspaShape<Q>::W, VPW = QspaShape<Q>::VPW;
+    const int NV = NT / 64 * VPW;
     extern __shared__ float qspa_lds[];
     const int N = a.N, M = a.M, dv = a.dv, dc = a.dc, TC = M * dc;
     float *p = qspa_lds, *msg = p + N * Q;
@@ -193,100 +265,80 @@ template <int Q> __global__ __launch_bounds__(kQspaThreads) void k_nb_qspa(QspaA
             it--;
             break;
         }
-        // ---- C: variable to check, in place (entry a of a variable's vectors belongs to one lane) ----
-        for (int ib = vbase; ib < N; ib += NV) {
-            const bool valid = ib + sv < N;
-            const int i = valid ? ib + sv : N - 1, w = a.vn_w[i];
-            float res[kQspaMaxDv][EPL], t[EPL];
+        if constexpr (LAYERED) {
+            // ---- the rows level by level ("FHT sum-product, layered schedule"): the rows of one level share no variable, every
+            // earlier row that shares one with them has run and no later one has, so this is the serial order's result.  A vector of
+            // lanes forms its row's v2c from p and the OTHER edges' slots as they stand (rows of other levels: nobody writes them
+            // now), writes them into the row's own slots (read by nobody else in this level), and runs the check-node rule there ----
+            for (int lv = 0; lv < a.levels; lv++) {
+                const int lb = a.level_begin[lv], le = a.level_begin[lv + 1];
+                for (int rb = lb + vbase; rb < le; rb += NV) {
+                    const bool valid = rb + sv < le;
+                    const int r = a.row_order[valid ? rb + sv : le - 1], w = a.cn_w[r];
+                    float *row = msg + r * dc * Q;
+                    for (int t = 0; t < dc; t++) {
+                        const bool here = t < w;
+                        const int self = r * dc + t, i = a.cn_vn[here ? self : r * dc], wi = a.vn_w[i];
+                        float x[EPL], y[EPL];
 #pragma unroll
-            for (int d = 0; d < kQspaMaxDv; d++)
-                if (d < dv) {
+                        for (int j = 0; j < EPL; j++) x[j] = p[i * Q + el + 64 * j];
+                        for (int d = 0; d < dv; d++) {
+                            const int s = d < wi ? a.vn_thr[i * dv + d] : self;
+                            const bool act = here && s != self;
+                            const int slot = act ? s : 0;
 #pragma unroll
-                    for (int j = 0; j < EPL; j++) res[d][j] = p[i * Q + el + 64 * j];
-                    for (int d2 = 0; d2 < dv; d2++) {
-                        if (d2 == d) continue;
-                        const bool act = d2 < w;
-                        const int slot = act ? a.vn_thr[i * dv + d2] : 0;
+                            for (int j = 0; j < EPL; j++) y[j] = x[j] * msg[slot * Q + el + 64 * j];
+                            const float mx = qspa_vec_max<Q>(y);
 #pragma unroll
-                        for (int j = 0; j < EPL; j++) t[j] = res[d][j] * msg[slot * Q + el + 64 * j];
-                        const float mx = qspa_vec_max<Q>(t);
+                            for (int j = 0; j < EPL; j++) x[j] = act ? qspa_norm_entry(y[j], mx) : x[j];
+                        }
 #pragma unroll
-                        for (int j = 0; j < EPL; j++) res[d][j] = act ? qspa_norm_entry(t[j], mx) : res[d][j];
+                        for (int j = 0; j < EPL; j++)
+                            if (valid && here) row[t * Q + el + 64 * j] = x[j];
                     }
+                    qspa_check_row<Q>(row, a.cn_gf + r * dc, w, valid, dc, mulb, lane, el);
                 }
-#pragma unroll
-            for (int d = 0; d < kQspaMaxDv; d++)
-                if (d < dv && d < w && valid) {
-                    const int slot = a.vn_thr[i * dv + d];
-#pragma unroll
-                    for (int j = 0; j < EPL; j++) msg[slot * Q + el + 64 * j] = res[d][j];
-                }
-        }
-        __syncthreads();
-        // ---- D: check nodes, one vector of lanes per row, in place ----
-        for (int rb = vbase; rb < M; rb += NV) {
-            const bool valid = rb + sv < M;
-            const int r = valid ? rb + sv : M - 1, w = a.cn_w[r];
-            float *row = msg + r * dc * Q;
-            for (int t = 0; t < dc; t++) { // v2c -> permuted -> U = FHT / W[0]
-                const bool st = valid && t < w;
-                const int h = t < w ? a.cn_gf[r * dc + t] : 1;
-                float v[EPL];
-                int pm[EPL];
-#pragma unroll
-                for (int j = 0; j < EPL; j++) {
-                    v[j] = row[t * Q + el + 64 * j];
-                    pm[j] = mulb[h * Q + el + 64 * j];
-                }
-                qspa_wave_sync();
-#pragma unroll
-                for (int j = 0; j < EPL; j++)
-                    if (st) row[t * Q + pm[j]] = v[j];
-                qspa_wave_sync();
-#pragma unroll
-                for (int j = 0; j < EPL; j++) v[j] = row[t * Q + el + 64 * j];
-                qspa_fht<Q>(v, lane);
-                const float w0 = __shfl(v[0], lane & ~(W - 1), 64);
-#pragma unroll
-                for (int j = 0; j < EPL; j++)
-                    if (st) row[t * Q + el + 64 * j] = v[j] / w0;
+                __syncthreads();
             }
-            float F[EPL];
+        } else {
+            // ---- C: variable to check, in place (entry a of a variable's vectors belongs to one lane) ----
+            for (int ib = vbase; ib < N; ib += NV) {
+                const bool valid = ib + sv < N;
+                const int i = valid ? ib + sv : N - 1, w = a.vn_w[i];
+                float res[kQspaMaxDv][EPL], t[EPL];
 #pragma unroll
-            for (int j = 0; j < EPL; j++) F[j] = 0.0f;
-            for (int t = 0; t < dc; t++) {
-                const bool st = valid && t < w;
-                const int h = t < w ? a.cn_gf[r * dc + t] : 1;
-                float Bk[EPL], o[EPL];
+                for (int d = 0; d < kQspaMaxDv; d++)
+                    if (d < dv) {
 #pragma unroll
-                for (int j = 0; j < EPL; j++) Bk[j] = 0.0f;
-                for (int s = dc - 1; s > t; s--) // B_{t+1} = U_{t+1} * (U_{t+2} * ( ... U_{w-1}))
+                        for (int j = 0; j < EPL; j++) res[d][j] = p[i * Q + el + 64 * j];
+                        for (int d2 = 0; d2 < dv; d2++) {
+                            if (d2 == d) continue;
+                            const bool act = d2 < w;
+                            const int slot = act ? a.vn_thr[i * dv + d2] : 0;
 #pragma unroll
-                    for (int j = 0; j < EPL; j++) {
-                        const float us = row[s * Q + el + 64 * j];
-                        Bk[j] = s == w - 1 ? us : s < w - 1 ? us * Bk[j] : Bk[j];
+                            for (int j = 0; j < EPL; j++) t[j] = res[d][j] * msg[slot * Q + el + 64 * j];
+                            const float mx = qspa_vec_max<Q>(t);
+#pragma unroll
+                            for (int j = 0; j < EPL; j++) res[d][j] = act ? qspa_norm_entry(t[j], mx) : res[d][j];
+                        }
                     }
 #pragma unroll
-                for (int j = 0; j < EPL; j++) {
-                    const float ut = row[t * Q + el + 64 * j];
-                    o[j] = t == 0 ? Bk[j] : t == w - 1 ? F[j] : F[j] * Bk[j];
-                    F[j] = t == 0 ? ut : F[j] * ut;
-                }
-                qspa_fht<Q>(o, lane);
+                for (int d = 0; d < kQspaMaxDv; d++)
+                    if (d < dv && d < w && valid) {
+                        const int slot = a.vn_thr[i * dv + d];
 #pragma unroll
-                for (int j = 0; j < EPL; j++)
-                    if (st) row[t * Q + el + 64 * j] = qspa_clamp0(o[j]);
-                qspa_wave_sync();
-#pragma unroll
-                for (int j = 0; j < EPL; j++) o[j] = row[t * Q + mulb[h * Q + el + 64 * j]]; // c[a] = w[mul[h][a]]
-                qspa_wave_sync();
-                const float mx = qspa_vec_max<Q>(o);
-#pragma unroll
-                for (int j = 0; j < EPL; j++)
-                    if (st) row[t * Q + el + 64 * j] = qspa_c2v_entry(o[j], mx);
+                        for (int j = 0; j < EPL; j++) msg[slot * Q + el + 64 * j] = res[d][j];
+                    }
             }
+            __syncthreads();
+            // ---- D: check nodes, one vector of lanes per row, in place ----
+            for (int rb = vbase; rb < M; rb += NV) {
+                const bool valid = rb + sv < M;
+                const int r = valid ? rb + sv : M - 1;
+                qspa_check_row<Q>(msg + r * dc * Q, a.cn_gf + r * dc, a.cn_w[r], valid, dc, mulb, lane, el);
+            }
+            __syncthreads();
         }
-        __syncthreads();
     }
     for (int i = tid; i < N; i += NT) a.out[b * N + i] = dec[i];
     if (tid == 0) {
@@ -295,6 +347,22 @@ template <int Q> __global__ __launch_bounds__(kQspaThreads) void k_nb_qspa(QspaA
     }
     if (a.c2v)
         for (int k = tid; k < TC * Q; k += NT) a.c2v[b * TC * Q + k] = msg[k];
+}
+
+template <int Q> __global__ __launch_bounds__(kQspaThreads) void k_nb_qspa(QspaArgs a) { qspa_decode_frame<Q, false>(a, kQspaThreads); }
+
+// The layered schedule: launched with 256, 512 or 1024 threads (qspa_layered_threads or the experiment switch), the same LDS.
+template <int Q> __global__ __launch_bounds__(kQspaThreads) void k_nb_qspa_layered(QspaArgs a) { qspa_decode_frame<Q, true>(a, (int)blockDim.x); }
+
+// Threads per workgroup of k_nb_qspa_layered: 256 where its waves hold the widest level in one pass (256 / 64 * vectors per wave
+// rows at a time), else 512.  The row sweep is where an iteration's time goes, and it can use no more vectors than a level has rows.
+// 1024 is never chosen: on BDS.576.288.GF.64 (levels of up to 10 rows) it covers every level in one pass and still measured 1.5 times
+// the time of 512, because the runtime keeps one workgroup of 1024 resident per CU where it keeps two of 512; it stays
+// in the set for the experiment switch.
+inline int qspa_layered_threads(int q, int widest_level)
+{
+    const int vpw = q < 64 ? 64 / q : 1;
+    return 256 / 64 * vpw >= widest_level ? 256 : 512;
 }
 
 } // namespace cldpc

@@ -88,8 +88,8 @@ def _decode(code, Lch, decoder_method, EMS_Nm, EMS_Nc, maxIT):
         return nb.Decoding_EMS(code, Lch, EMS_Nm, EMS_Nc, maxIT)
     if decoder_method == 2:
         return nb.Decoding_EMS(code, Lch, code.q, code.dc - 1, maxIT)  # Simulation.cpp:63-66
-    if decoder_method == 4:
-        return nb.Decoding_QSPA(code, Lch, maxIT)  # ours: the reference stops at 3
+    if decoder_method in (4, 5):
+        return nb.Decoding_QSPA(code, Lch, maxIT, layered=(decoder_method == 5))  # ours: the reference stops at 3
     return nb.Decoding_TMM(code, Lch, maxIT, layered=(decoder_method == 3))
 
 
@@ -128,7 +128,8 @@ def Simulation_GPU(code, seed, sigma, SIM, CodeWord_sym, EMS_Nm=2, EMS_Nc=2, max
     """One Eb/N0 point. `seed` (int32[3]) advances exactly as far as the reference would have drawn.
     device_channel: generate the noise on the GPU (same uniforms, device libm) instead of the host, frame by frame.
     decoder_method (define.h:37, Simulation.cpp:54-70): 0 EMS, 1 trellis min-max, 2 log-QSPA = EMS(q, dc-1), 3 layered TMM;
-    4 is ours, the reference stops at 3: the FHT sum-product decoder (Decoding_QSPA; include/nbldpc.h, "FHT sum-product").
+    4 and 5 are ours, the reference stops at 3: the FHT sum-product decoder (Decoding_QSPA; include/nbldpc.h, "FHT sum-product"),
+    flooding and layered (layered=True; "FHT sum-product, layered schedule").
     CONSTELLATION (host float32 [q, 2], Get_CONSTELLATION): the n_QAM = q branches of Modulate / AWGNChannel_CPU / Demodulate
     (one constellation point per code symbol) instead of BPSK; the caller passes the sigma of that n_QAM.
     PN_Message=1: every frame sends its own random codeword in place of CodeWord_sym (may be None): frame i of the point is

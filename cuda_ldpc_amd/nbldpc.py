@@ -24,6 +24,9 @@ lib.nbldpc_tmm_decode_batch.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int]
 lib.nbldpc_qspa_decode_batch.argtypes = [c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 6
 lib.nbldpc_qspa_decode_host.argtypes = [c_int] * 5 + [c_void_p] * 8 + [c_int, c_int] + [c_void_p] * 5
 lib.nbldpc_qspa_exp_host.argtypes = [c_void_p, c_int, c_void_p]
+lib.nbldpc_qspa_layered_decode_batch.argtypes = lib.nbldpc_qspa_decode_batch.argtypes
+lib.nbldpc_qspa_layered_decode_host.argtypes = lib.nbldpc_qspa_decode_host.argtypes
+lib.nbldpc_qspa_layered_threads.argtypes = [c_void_p]
 lib.nbldpc_demodulate_bpsk.argtypes = [c_void_p, c_void_p, c_float, c_int, c_void_p, c_void_p]
 lib.nbldpc_statistic.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
 lib.nbldpc_awgn_channel_host.argtypes = [c_void_p, c_float, c_void_p, c_int, c_int, c_void_p]
@@ -160,6 +163,11 @@ class NBCode(NBMatrix):
         return dict(persist_grid=int(d[0]), pipe_grid=int(d[1]), tmm_grid=int(d[2]), tmm_grid_layered=int(d[3]))
 
     @property
+    def qspa_layered_threads(self):
+        """Threads per workgroup of k_nb_qspa_layered for this code (nbldpc_qspa_layered_threads): 256, 512 or 1024."""
+        return int(lib.nbldpc_qspa_layered_threads(self._h))
+
+    @property
     def persist_grid(self):
         return self.grids()["persist_grid"]
 
@@ -216,10 +224,11 @@ def Decoding_TMM(code, L_ch, maxIT=20, layered=False, want_state=False, stream=N
     return dict(DecodeOutput=out, iter_number=iters, ok=ok, LLR=LLR, L_c2v=c2v)
 
 
-def Decoding_QSPA(code, L_ch, maxIT=20, want_state=False, stream=None):
+def Decoding_QSPA(code, L_ch, maxIT=20, want_state=False, stream=None, layered=False):
     """nbldpc_qspa_decode_batch: the FHT sum-product decoder (include/nbldpc.h, "FHT sum-product"; ours, the reference has none) for
-    a batch.  Returns the dict of Decoding_TMM: LLR [B,N,q] holds the APP probability vectors of the last executed iteration,
-    L_c2v [B,M,dc,q] the check-to-variable vectors, all q entries each, max-normalised with the floor 2^-40."""
+    a batch; layered=True: nbldpc_qspa_layered_decode_batch, the row-by-row schedule ("FHT sum-product, layered schedule").  Returns
+    the dict of Decoding_TMM: LLR [B,N,q] holds the APP probability vectors of the last executed iteration, L_c2v [B,M,dc,q] the
+    check-to-variable vectors, all q entries each, max-normalised with the floor 2^-40."""
     if not (L_ch.is_cuda and L_ch.dtype == torch.float32 and L_ch.is_contiguous()):
         raise ValueError("L_ch must be a contiguous CUDA float32 tensor")
     if L_ch.dim() != 3 or L_ch.shape[1] != code.N or L_ch.shape[2] != code.q - 1:
@@ -231,13 +240,15 @@ def Decoding_QSPA(code, L_ch, maxIT=20, want_state=False, stream=None):
     APP = torch.empty((B, code.N, code.q), dtype=torch.float32, device=dev) if want_state else None
     c2v = torch.empty((B, code.M, code.dc, code.q), dtype=torch.float32, device=dev) if want_state else None
     st = c_void_p((stream or torch.cuda.current_stream(dev)).cuda_stream)
-    _check(lib.nbldpc_qspa_decode_batch(code._h, _dev(L_ch), B, maxIT, _dev(out), _dev(iters), _dev(ok), _dev(APP), _dev(c2v), st), "Decoding_QSPA")
+    call = lib.nbldpc_qspa_layered_decode_batch if layered else lib.nbldpc_qspa_decode_batch
+    _check(call(code._h, _dev(L_ch), B, maxIT, _dev(out), _dev(iters), _dev(ok), _dev(APP), _dev(c2v), st), "Decoding_QSPA")
     return dict(DecodeOutput=out, iter_number=iters, ok=ok, LLR=APP, L_c2v=c2v)
 
 
-def Decoding_QSPA_host(code, L_ch, maxIT=20, want_state=False, TableMultiply=None):
-    """nbldpc_qspa_decode_host: the host statement of Decoding_QSPA on host arrays, no device needed.  code: an NBMatrix or NBCode
-    (TableMultiply: the code's unless given); L_ch float32 [B, N, q-1].  Returns the same dict, numpy arrays."""
+def Decoding_QSPA_host(code, L_ch, maxIT=20, want_state=False, TableMultiply=None, layered=False):
+    """nbldpc_qspa_decode_host (layered=True: nbldpc_qspa_layered_decode_host): the host statement of Decoding_QSPA on host arrays, no
+    device needed.  code: an NBMatrix or NBCode (TableMultiply: the code's unless given); L_ch float32 [B, N, q-1].  Returns the same
+    dict, numpy arrays."""
     mul = np.ascontiguousarray(code.TableMultiply if TableMultiply is None else TableMultiply, np.uint32)
     if mul.shape != (code.q, code.q):
         raise ValueError("TableMultiply must be [q, q]")
@@ -248,7 +259,8 @@ def Decoding_QSPA_host(code, L_ch, maxIT=20, want_state=False, TableMultiply=Non
     out, iters, ok = np.empty((B, code.N), np.int32), np.empty(B, np.int32), np.empty(B, np.int32)
     APP = np.empty((B, code.N, code.q), np.float32) if want_state else None
     c2v = np.empty((B, code.M, code.dc, code.q), np.float32) if want_state else None
-    _check(lib.nbldpc_qspa_decode_host(code.N, code.M, code.q, code.dv, code.dc, _np(code.vn_weight), _np(code.vn_linkCNs), _np(code.vn_linkCNs_GF),
+    call = lib.nbldpc_qspa_layered_decode_host if layered else lib.nbldpc_qspa_decode_host
+    _check(call(code.N, code.M, code.q, code.dv, code.dc, _np(code.vn_weight), _np(code.vn_linkCNs), _np(code.vn_linkCNs_GF),
                                        _np(code.cn_weight), _np(code.cn_linkVNs), _np(code.cn_linkVNs_GF), _np(mul), _np(L), B, maxIT, _np(out),
                                        _np(iters), _np(ok), None if APP is None else _np(APP), None if c2v is None else _np(c2v)),
            "Decoding_QSPA_host")

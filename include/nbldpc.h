@@ -373,6 +373,42 @@ int nbldpc_qspa_decode_host(int N, int M, int q, int dvmax, int dcmax, const int
                             const float *L_ch, int B, int maxIT, int *DecodeOutput, int *iter_number, int *ok, float *APP, float *c2v);
 int nbldpc_qspa_exp_host(const float *x, int n, float *y);
 
+/* ---- FHT sum-product, layered schedule ------------------------------------------------------------------------------------------
+ *
+ * The decoder above with a serial (row by row) schedule; ours as well.  The host statement nbldpc_qspa_layered_decode_host
+ * (csrc/nbldpc_qspa_host.hpp, layered = true) is the definition, and the kernel equals it bit for bit.  Everything is as
+ * "FHT sum-product" has it -- input and probability vectors, norm and the channel vector, the check-node rule, the iteration loop
+ * (APP and decision from p and ALL current c2v, the syndrome, the stop rule, what iter_number, ok and DecodeOutput hold), the
+ * outputs APP and c2v, the expressions of csrc/nbldpc_qspa_math.hpp and no other, never contracted -- except the part of an
+ * iteration after the syndrome check, which reads:
+ *     for rows r = 0 ... M-1 in that order: for every slot t of the row, with variable i and that edge's index d at the variable,
+ *     v2c_t = p_i, then for d' ascending, d' != d: v2c_t = norm(v2c_t * c2v_d'), with the c2v AS THEY STAND AT THAT MOMENT (rows
+ *     before r already hold this iteration's messages).  Then the check-node rule on the row, and its c2v are stored before row
+ *     r + 1 begins.
+ * The extrinsic vector is re-formed from p and the other edges' messages; it is never app / c2v (the 2^-40 floors make that
+ * quotient inexact), so there is no APP array between rows and the state is that of the flooding decoder.
+ * Refusals.  Those of the flooding pair, with the same LDS bound for nbldpc_qspa_layered_decode_batch
+ *         4 (N q + M dcmax q) + 4 (N + 4) + q^2  <=  159 * 1024 bytes
+ *     (the level tables are read from global memory), and one more, in both calls: a row that lists one variable in two slots is
+ *     NBLDPC_EUNSUPPORTED.  nbldpc_code_create accepts such a row when the two slots carry one coefficient (its cross indices take
+ *     the first match), and "the other edges of the variable" is not defined for it.  Nothing is launched on a refusal.
+ * nbldpc_qspa_layered_decode_batch: all pointers DEVICE memory, asynchronous on `stream`; one workgroup per frame
+ *     (k_nb_qspa_layered in nbldpc_last_kernel).  The kernel runs the rows of one dependency level at a time (a row's level is 1 +
+ *     the highest level among the earlier rows that share a variable with it: every earlier row that shares a variable has run, no
+ *     later one has, and the rows of a level share none), which is the serial order's result bit for bit.  Threads per workgroup:
+ *     256 where its waves hold the code's widest level in one pass (4 * max(64 / q, 1) rows), else 512; fixed at
+ *     nbldpc_code_create, where the environment variable NBLDPC_QSPA_LAYERED_THREADS = 256 | 512 | 1024 pins it (an experiment
+ *     switch; 1024 is never the rule's choice).  The results do not depend on it.  nbldpc_qspa_layered_threads reports it (0 for a
+ *     null code).
+ * nbldpc_qspa_layered_decode_host: HOST pointers, the argument list of nbldpc_qspa_decode_host, serial. ---- */
+int nbldpc_qspa_layered_decode_batch(nbldpc_code *code, const float *L_ch, int B, int maxIT, int *DecodeOutput, int *iter_number,
+                                     int *ok, float *APP, float *c2v, void *stream);
+int nbldpc_qspa_layered_decode_host(int N, int M, int q, int dvmax, int dcmax, const int *vn_weight, const int *vn_linkCNs,
+                                    const int *vn_linkCNs_GF, const int *cn_weight, const int *cn_linkVNs, const int *cn_linkVNs_GF,
+                                    const unsigned *TableMultiply, const float *L_ch, int B, int maxIT, int *DecodeOutput,
+                                    int *iter_number, int *ok, float *APP, float *c2v);
+int nbldpc_qspa_layered_threads(const nbldpc_code *code);
+
 const char *nbldpc_last_error(void);
 
 #ifdef __cplusplus

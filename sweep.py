@@ -74,8 +74,8 @@ def main():
     ap.add_argument("--interleave", choices=["none", "rowcol"], default="none", help="binary --qam: the bit interleaver between the codeword (or "
                     "the rate-matched bits) and the points: none = consecutive bits share a point, rowcol = the row-column interleaver")
     ap.add_argument("--nb-matrix", default="BDS.576.288.GF.64.txt", help="nb: matrix file (under data/nb or a path); q from its header")
-    ap.add_argument("--method", type=int, default=0, choices=[0, 1, 2, 3, 4],
-                    help="NB decoder_method (define.h:37): 0 EMS, 1 TMM, 2 log-QSPA, 3 layered TMM; 4 (ours) FHT sum-product")
+    ap.add_argument("--method", type=int, default=0, choices=[0, 1, 2, 3, 4, 5],
+                    help="NB decoder_method (define.h:37): 0 EMS, 1 TMM, 2 log-QSPA, 3 layered TMM; ours: 4 FHT sum-product, 5 layered FHT sum-product")
     ap.add_argument("--device-channel", action="store_true", help="generate the AWGN samples on the GPU (same RNG draws, device libm)")
     ap.add_argument("--pn-message", action="store_true", help="send random codewords (PN_Message 1, define.cuh:26); binary: needs --fixed")
     ap.add_argument("--pn-seed", type=int, default=1, help="--pn-message: seed of the message stream (bldpc_encode_random / nbldpc_encode_random)")
@@ -294,7 +294,7 @@ def main():
         else:
             words = "" if bds else ", all-zero codeword"
         print("# %s N=%d symbols GF(%d), %s, maxIT=%d, %s%s" % (os.path.basename(mpath).replace(".txt", ""), code.N, code.q,
-              ["EMS(2,2)", "trellis min-max", "log-QSPA = EMS(q,dc-1)", "layered trellis min-max", "FHT sum-product"][args.method], args.iters or 20,
+              ["EMS(2,2)", "trellis min-max", "log-QSPA = EMS(q,dc-1)", "layered trellis min-max", "FHT sum-product", "layered FHT sum-product"][args.method], args.iters or 20,
               "BPSK" if args.qam == 2 else "%d-QAM (Gray), one point per symbol" % args.qam, words) + (fade_words if fade is not None else ""))
         dev_ch = args.device_channel or fade is not None  # the fading channel exists on the device only
         nbatch = args.batch if dev_ch else min(args.batch, 1024)  # the host channel is serial: keep its batches small
