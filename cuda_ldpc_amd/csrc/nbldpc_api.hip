@@ -10,15 +10,12 @@
 #include <cstdio>
 #include <new>
 
-#include "nbldpc_plan.hpp" // common.hpp, the code object, the decoder kernel headers
+#include "nbldpc_launch.hpp" // nb_launch and the frame-counter ring
+#include "nbldpc_plan.hpp"   // common.hpp, the code object, the decoder kernel headers
 
 using namespace cldpc;
 
 static_assert(NBLDPC_OK == 0 && NBLDPC_ENOMEM == kUploadEnomem && NBLDPC_EHIP == kUploadEhip, "cldpc::upload (nbldpc_plan.hpp, nbldpc_encode.hip) returns this ABI's codes");
-
-constexpr unsigned kWorkSlots = 1024, kWorkStride = 16; // 64 bytes apart: one counter per cache line
-
-static int *next_work_slot(nbldpc_code *c) { return c->d_work + (size_t)(c->work_next.fetch_add(1) % kWorkSlots) * kWorkStride; }
 
 extern "C" const char *nbldpc_last_error(void) { return err_buf(); }
 
@@ -200,20 +197,6 @@ NbCodeView cldpc::nb_code_view(const nbldpc_code *c)
     nbldpc_code *w = const_cast<nbldpc_code *>(c); // the generator slot is a cache: building it does not change the code
     return NbCodeView{c->N, c->M, c->q, c->m, c->dc, c->h_cn_w.data(), c->h_cn_vn.data(), c->h_cn_gf.data(), c->h_mul.data(),
                       c->d_cn_w, c->d_cn_vn, c->d_cn_gf, c->d_mul, &w->enc};
-}
-
-// One decode launch.  counted: the kernel takes its frames from a counter -- the call's slot of the ring, zeroed stream-ordered.
-template <class Kernel, class Args>
-static int nb_launch(nbldpc_code *c, const char *name, bool counted, Kernel k, int grid, int threads, size_t lds, hipStream_t st, Args &a)
-{
-    if (counted) {
-        a.work = next_work_slot(c);
-        CLDPC_HIP(hipMemsetAsync(a.work, 0, sizeof(int), st), NBLDPC_EHIP);
-    }
-    c->last_kernel = name;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(threads), lds, st, a);
-    CLDPC_HIP(hipGetLastError(), NBLDPC_EHIP);
-    return NBLDPC_OK;
 }
 
 extern "C" int nbldpc_ems_decode_batch(nbldpc_code *c, const float *Lch, int B, int Nm, int Nc, int maxIT, int maxdc_cfg, int *out,

@@ -18,6 +18,8 @@ struct nbldpc_code {
     bool tmm_ok = false;
     int qspa_layered_threads = 0; // k_nb_qspa_layered: threads per workgroup (256 / 512 / 1024), fixed at create time
     bool row_repeats = false;     // a row lists one variable in two slots: refused by nbldpc_qspa_layered_decode_batch
+    int widest_level = 0;         // the most rows any dependency level holds: the layered plan of the workspace tier (nbldpc_qspa_ws.hpp)
+    int qspa_ws_threads = 0, qspa_ws_slots = 0; // NBLDPC_QSPA_WS_THREADS / NBLDPC_QSPA_WS_SLOTS, read once at create time (0: the plan's rule / no cap)
     int zero_coeff = 0; // an edge with coefficient 0 exists (EMS only, see nb_tables_build)
     const char *last_kernel = "none"; // nbldpc_last_kernel
     int persist_grid = 0; // k_nb_ems / k_nb_ems_wide: workgroups that fill the chip once (CUs x workgroups per CU)

@@ -21,6 +21,7 @@
 #include "nbldpc_hbm_kernel.hpp"
 #include "nbldpc_qspa_host.hpp"
 #include "nbldpc_qspa_kernel.hpp"
+#include "nbldpc_qspa_ws.hpp"
 
 namespace cldpc {
 
@@ -29,6 +30,8 @@ struct NbSwitches {
     bool no_pipe = false;    // NBLDPC_NO_PIPE: k_nb_ems2 not offered
     bool no_persist = false; // NBLDPC_NO_PERSIST: one workgroup per frame even where the persistent form exists
     int qspa_layered_threads = 0; // NBLDPC_QSPA_LAYERED_THREADS = 256 | 512 | 1024: k_nb_qspa_layered's workgroup pinned (else by the widest level)
+    int qspa_ws_threads = 0;      // NBLDPC_QSPA_WS_THREADS = 64 | 128 | 256 | 512 | 1024: the workspace tier's workgroup pinned (else qspa_ws_plan's rule)
+    int qspa_ws_slots = 0;        // NBLDPC_QSPA_WS_SLOTS = n > 0: at most n workspace slots (= workgroups) per call of the workspace tier
 };
 
 // The only getenv of the GF(q) family.
@@ -42,6 +45,11 @@ inline NbSwitches nb_switches_from_env()
         const int nt = atoi(v);
         if (nt == 256 || nt == 512 || nt == 1024) sw.qspa_layered_threads = nt; // anything else: the rule
     }
+    if (const char *v = getenv("NBLDPC_QSPA_WS_THREADS")) {
+        const int nt = atoi(v);
+        if (qspa_ws_size_ok(nt)) sw.qspa_ws_threads = nt; // anything else: the rule
+    }
+    if (const char *v = getenv("NBLDPC_QSPA_WS_SLOTS")) sw.qspa_ws_slots = std::max(atoi(v), 0);
     return sw;
 }
 
@@ -64,6 +72,7 @@ struct NbTables {
     int qspa_layered_threads = 0;                     // workgroup of k_nb_qspa_layered: the switch, else the rule of qspa_layered_threads()
     bool tmm_ok = false;
     bool row_repeats = false; // a row lists one variable in two slots: the layered sum-product decoder refuses the code
+    int qspa_ws_threads = 0, qspa_ws_slots = 0; // the workspace tier's switches, as read
     std::vector<int> vn_thr, cn_src;              // [N][dv] CN thread of each VN edge, [M][dc] VN edge of each CN slot
     std::vector<unsigned char> mulb;              // TableMultiply as bytes
     std::vector<int> hinv, row_order, level_begin; // trellis decoders: [M][dc] inverse coefficients, rows by level, [levels + 1]
@@ -167,6 +176,7 @@ inline int nb_tables_build(int N, int M, int q, int dv, int dc, const int *vn_w,
     for (int l = 0; l < t.levels; l++) t.widest_level = std::max(t.widest_level, t.level_begin[l + 1] - t.level_begin[l]);
     t.qspa_layered_threads = sw.qspa_layered_threads ? sw.qspa_layered_threads : qspa_layered_threads(q, t.widest_level);
     t.row_repeats = qspa_row_repeats_variable(M, dc, cn_w, cn_vn);
+    t.qspa_ws_threads = sw.qspa_ws_threads; t.qspa_ws_slots = sw.qspa_ws_slots;
     t.tmm_ok = (q == 16 || q == 32 || q == 64) && inv_ok && dc <= kTmmMaxW && t.levels <= 63 && M <= kTmmThreads && // the trellis kernels keep a vector in one wave
                tmm_lds_bytes(N, M, q, dv, dc, false) <= 160 * 1024;
     // the two-frame pipeline (nbldpc_pipe_kernel.hpp): GF(64), column weights <= 2, no zero coefficient, the columns fit its A/S/B waves
@@ -186,6 +196,7 @@ inline int nb_tables_upload(nbldpc_code *c, const NbTables &t)
     c->N = t.N; c->M = t.M; c->q = t.q; c->m = t.m; c->dv = t.dv; c->dc = t.dc;
     c->lds_bytes = t.lds_bytes; c->hbm = t.hbm; c->zero_coeff = t.zero_coeff; c->levels = t.levels; c->tmm_ok = t.tmm_ok;
     c->qspa_layered_threads = t.qspa_layered_threads; c->row_repeats = t.row_repeats;
+    c->widest_level = t.widest_level; c->qspa_ws_threads = t.qspa_ws_threads; c->qspa_ws_slots = t.qspa_ws_slots;
     c->h_cn_w.assign(t.cn_w, t.cn_w + t.M);
     c->h_cn_vn.assign(t.cn_vn, t.cn_vn + (size_t)t.M * t.dc);
     c->h_cn_gf.assign(t.cn_gf, t.cn_gf + (size_t)t.M * t.dc);

@@ -83,18 +83,18 @@ def _rm_receive(rm, q, rx, sigma, short_llr, acc=None, done=None, n_done=None, f
     return nb.RM_Recover(rm, q, Lrx, short_llr) if acc is None else nb.RM_Combine(rm, q, Lrx, acc, done, short_llr)
 
 
-def _decode(code, Lch, decoder_method, EMS_Nm, EMS_Nc, maxIT):
+def _decode(code, Lch, decoder_method, EMS_Nm, EMS_Nc, maxIT, qspa_tier="lds"):
     if decoder_method == 0:
         return nb.Decoding_EMS(code, Lch, EMS_Nm, EMS_Nc, maxIT)
     if decoder_method == 2:
         return nb.Decoding_EMS(code, Lch, code.q, code.dc - 1, maxIT)  # Simulation.cpp:63-66
     if decoder_method in (4, 5):
-        return nb.Decoding_QSPA(code, Lch, maxIT, layered=(decoder_method == 5))  # ours: the reference stops at 3
+        return nb.Decoding_QSPA(code, Lch, maxIT, layered=(decoder_method == 5), tier=qspa_tier)  # ours: the reference stops at 3
     return nb.Decoding_TMM(code, Lch, maxIT, layered=(decoder_method == 3))
 
 
 def _simulation_rm(code, seed, sigma, SIM, CodeWord_sym, rm, short_llr, EMS_Nm, EMS_Nc, maxIT, batch, leastErrorFrames, leastTestFrames,
-                   max_frames, device, decoder_method, PN_Message, pn_seed):
+                   max_frames, device, decoder_method, PN_Message, pn_seed, qspa_tier="lds"):
     """Simulation_GPU with rate_match=rm, over BPSK: select -> the per-frame channel at N := E -> the fused receive -> the decoder.
     The seed roll-back is by E."""
     words = None if PN_Message else torch.from_numpy(np.ascontiguousarray(CodeWord_sym, np.int32)).to(device)[None, :].expand(batch, code.N).contiguous()
@@ -107,7 +107,7 @@ def _simulation_rm(code, seed, sigma, SIM, CodeWord_sym, rm, short_llr, EMS_Nm, 
         seed0 = seed.copy()
         rx = nb.AWGNChannel_RM_GPU(seed, sigma, rm, code.q, tx)
         Lch = _rm_receive(rm, code.q, rx, sigma, short_llr)
-        r = _decode(code, Lch, decoder_method, EMS_Nm, EMS_Nc, maxIT)
+        r = _decode(code, Lch, decoder_method, EMS_Nm, EMS_Nc, maxIT, qspa_tier)
         errs = (r["DecodeOutput"] != words).sum(dim=1).cpu().numpy()
         its = r["iter_number"].cpu().numpy()
         for b in range(batch):  # account in stream order; stop where the reference's while-condition fails
@@ -124,12 +124,13 @@ def _simulation_rm(code, seed, sigma, SIM, CodeWord_sym, rm, short_llr, EMS_Nm, 
 
 def Simulation_GPU(code, seed, sigma, SIM, CodeWord_sym, EMS_Nm=2, EMS_Nc=2, maxIT=20, batch=1024, leastErrorFrames=50,
                    leastTestFrames=1000, max_frames=None, device=None, device_channel=False, decoder_method=0, CONSTELLATION=None,
-                   PN_Message=0, pn_seed=0, fading=None, rate_match=None, short_llr=1.0e4):
+                   PN_Message=0, pn_seed=0, fading=None, rate_match=None, short_llr=1.0e4, qspa_tier="lds"):
     """One Eb/N0 point. `seed` (int32[3]) advances exactly as far as the reference would have drawn.
     device_channel: generate the noise on the GPU (same uniforms, device libm) instead of the host, frame by frame.
     decoder_method (define.h:37, Simulation.cpp:54-70): 0 EMS, 1 trellis min-max, 2 log-QSPA = EMS(q, dc-1), 3 layered TMM;
     4 and 5 are ours, the reference stops at 3: the FHT sum-product decoder (Decoding_QSPA; include/nbldpc.h, "FHT sum-product"),
-    flooding and layered (layered=True; "FHT sum-product, layered schedule").
+    flooding and layered (layered=True; "FHT sum-product, layered schedule").  qspa_tier ("lds", "workspace" or "auto"): the tier of
+    Decoding_QSPA those two run on; "auto" takes the workspace tier for the codes the LDS tier refuses.
     CONSTELLATION (host float32 [q, 2], Get_CONSTELLATION): the n_QAM = q branches of Modulate / AWGNChannel_CPU / Demodulate
     (one constellation point per code symbol) instead of BPSK; the caller passes the sigma of that n_QAM.
     PN_Message=1: every frame sends its own random codeword in place of CodeWord_sym (may be None): frame i of the point is
@@ -162,7 +163,7 @@ def Simulation_GPU(code, seed, sigma, SIM, CodeWord_sym, EMS_Nm=2, EMS_Nc=2, max
     device = device or torch.device("cuda", torch.cuda.current_device())
     if rate_match is not None:
         return _simulation_rm(code, seed, sigma, SIM, CodeWord_sym, rate_match, short_llr, EMS_Nm, EMS_Nc, maxIT, batch, leastErrorFrames,
-                              leastTestFrames, max_frames, device, decoder_method, PN_Message, pn_seed)
+                              leastTestFrames, max_frames, device, decoder_method, PN_Message, pn_seed, qspa_tier)
     cw = None if PN_Message else np.ascontiguousarray(CodeWord_sym, np.int32)
     cw_dev = None if PN_Message else torch.from_numpy(cw).to(device)
     qam = CONSTELLATION is not None
@@ -195,7 +196,7 @@ def Simulation_GPU(code, seed, sigma, SIM, CodeWord_sym, EMS_Nm=2, EMS_Nc=2, max
             Lch = nb.Demodulate_QAM_Fading(code, rxt, gain, sigma, con_dev)
         else:
             Lch = nb.Demodulate(code, rxt, sigma, CONSTELLATION=con_dev)
-        r = _decode(code, Lch, decoder_method, EMS_Nm, EMS_Nc, maxIT)
+        r = _decode(code, Lch, decoder_method, EMS_Nm, EMS_Nc, maxIT, qspa_tier)
         errs = (r["DecodeOutput"] != (cw_dev if PN_Message else cw_dev[None, :])).sum(dim=1).cpu().numpy()
         its = r["iter_number"].cpu().numpy()
         for b in range(batch):  # account in stream order; stop where the reference's while-condition fails
@@ -212,10 +213,11 @@ def Simulation_GPU(code, seed, sigma, SIM, CodeWord_sym, EMS_Nm=2, EMS_Nc=2, max
                 return 1 if done else 0
 
 
-def sweep(code, CodeWord_sym, startSNR=0.0, stopSNR=5.0, stepSNR=0.5, snrtype=0, seeds=(173, 173, 173), log=print, n_QAM=2, **kw):
+def sweep(code, CodeWord_sym, startSNR=0.0, stopSNR=5.0, stepSNR=0.5, snrtype=0, seeds=(173, 173, 173), log=print, n_QAM=2, qspa_tier="lds",
+          **kw):
     """main.cu:215-260: returns the list of NBSim, one per Eb/N0 point.  n_QAM enters sigma (main.cu:223); pass the
     constellation itself as CONSTELLATION=... for n_QAM != 2.  With rate_match=rm the rate in sigma is the derived code's,
-    (K' - n_short) / E."""
+    (K' - n_short) / E.  qspa_tier: as in Simulation_GPU."""
     out = []
     fading_seed0 = kw["fading"].seed.tolist() if kw.get("fading") is not None else None
     rm = kw.get("rate_match")
@@ -226,7 +228,7 @@ def sweep(code, CodeWord_sym, startSNR=0.0, stopSNR=5.0, stepSNR=0.5, snrtype=0,
         SIM = NBSim(float(s))
         if kw.get("fading") is not None:  # the fading stream restarts at every point, as the noise stream does
             kw["fading"] = Fading(kw["fading"].Lc, np.array(fading_seed0, np.int32))
-        Simulation_GPU(code, seed, nb.sigma_of(float(s), rate, snrtype, n_QAM), SIM, CodeWord_sym, **kw)
+        Simulation_GPU(code, seed, nb.sigma_of(float(s), rate, snrtype, n_QAM), SIM, CodeWord_sym, qspa_tier=qspa_tier, **kw)
         if log:
             log(SIM.row(code.N))
         out.append(SIM)
@@ -236,7 +238,7 @@ def sweep(code, CodeWord_sym, startSNR=0.0, stopSNR=5.0, stepSNR=0.5, snrtype=0,
 
 def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, CodeWord_sym=None, EMS_Nm=2, EMS_Nc=2, maxIT=20, batch=1024, leastErrorFrames=50,
                         leastTestFrames=1000, max_batches=None, device=None, decoder_method=0, PN_Message=1, pn_seed=0,
-                        short_llr=1.0e4, compact=True, log=print, keep=None):
+                        short_llr=1.0e4, compact=True, log=print, keep=None, qspa_tier="lds"):
     """One Eb/N0 point of HARQ with symbol-LLR combining on the device channel, over BPSK.  rvs = [rm_0, ..., rm_{T-1}]: the profile of each
     transmission (RateMatch.circular or RateMatch over code.N symbols, all with the same shortened positions).  SIM is the binary
     side's HarqCounters, counted in symbols: bits_sent is the sum of E_t * m over the transmissions each frame used.
@@ -253,7 +255,8 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, CodeWord_sym=None, EMS_Nm=2
     is advanced by the sum over all T transmissions after every batch, whatever was acknowledged.
     PN_Message=1 (default): frame i sends PN_CodeWords(code, pn_seed, first_frame=i, rate_match=rvs[0]); PN_Message=0: CodeWord_sym
     for every frame (0 at the shortened positions).  The stop rule is the binary one: never_acked + undetected >= leastErrorFrames and
-    num_Frames >= leastTestFrames, tested after every batch.  keep (a list) receives (DecodeOutput, ok, words) of every batch."""
+    num_Frames >= leastTestFrames, tested after every batch.  keep (a list) receives (DecodeOutput, ok, words) of every batch.
+    qspa_tier: as in Simulation_GPU."""
     from .simulation import format_harq_row
     if PN_Message not in (0, 1):
         raise ValueError("PN_Message must be 0 (CodeWord_sym for every frame) or 1 (random codewords)")
@@ -293,18 +296,18 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, CodeWord_sym=None, EMS_Nm=2
             rx = nb.AWGNChannel_RM_GPU(my_seed, sigma, rm, q, nb.RM_Select(rm, words))
             if t == 0:
                 acc = _rm_receive(rm, q, rx, sigma, short_llr)
-                r = _decode(code, acc, decoder_method, EMS_Nm, EMS_Nc, maxIT)
+                r = _decode(code, acc, decoder_method, EMS_Nm, EMS_Nc, maxIT, qspa_tier)
                 out, iters, ok = r["DecodeOutput"], r["iter_number"], r["ok"]
             else:
                 _rm_receive(rm, q, rx, sigma, short_llr, acc=acc, done=ok, n_done=n_done)
                 if compact:
                     idx = torch.nonzero(active).view(-1)
-                    r = _decode(code, acc.index_select(0, idx), decoder_method, EMS_Nm, EMS_Nc, maxIT)
+                    r = _decode(code, acc.index_select(0, idx), decoder_method, EMS_Nm, EMS_Nc, maxIT, qspa_tier)
                     out.index_copy_(0, idx, r["DecodeOutput"])
                     iters.index_copy_(0, idx, r["iter_number"])
                     ok.index_copy_(0, idx, r["ok"])
                 else:  # an acknowledged frame's L_acc has not changed: it decodes to what it decoded to
-                    r = _decode(code, acc, decoder_method, EMS_Nm, EMS_Nc, maxIT)
+                    r = _decode(code, acc, decoder_method, EMS_Nm, EMS_Nc, maxIT, qspa_tier)
                     out, iters, ok = r["DecodeOutput"], r["iter_number"], r["ok"]
             now = (ok != 0) & active
             wrong = (out != words).any(1)
@@ -333,7 +336,8 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, CodeWord_sym=None, EMS_Nm=2
             return 1 if stop else 0
 
 
-def sweep_harq(code, rvs, CodeWord_sym=None, startSNR=0.0, stopSNR=5.0, stepSNR=0.5, snrtype=0, seeds=(173, 173, 173), log=print, **kw):
+def sweep_harq(code, rvs, CodeWord_sym=None, startSNR=0.0, stopSNR=5.0, stepSNR=0.5, snrtype=0, seeds=(173, 173, 173), log=print,
+               qspa_tier="lds", **kw):
     """The sweep of `sweep` over Simulation_HARQ_GPU: a list of HarqCounters, one per Eb/N0 point.  sigma comes from nbldpc.sigma_of
     (BPSK) with the rate of the FIRST transmission, (K' - n_short) / E_0: the operating point is named by what is sent when nothing goes
     wrong, and the later transmissions run over the same channel."""
@@ -345,7 +349,7 @@ def sweep_harq(code, rvs, CodeWord_sym=None, startSNR=0.0, stopSNR=5.0, stepSNR=
         seed = np.array(seeds, np.int32)
         SIM = HarqCounters()
         SIM.SNR = float(s)
-        Simulation_HARQ_GPU(code, seed, nb.sigma_of(float(s), rate, snrtype), SIM, rvs, CodeWord_sym, log=log, **kw)
+        Simulation_HARQ_GPU(code, seed, nb.sigma_of(float(s), rate, snrtype), SIM, rvs, CodeWord_sym, log=log, qspa_tier=qspa_tier, **kw)
         out.append(SIM)
         s = np.float32(np.float64(s) + stepSNR)
     return out

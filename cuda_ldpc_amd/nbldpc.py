@@ -27,6 +27,10 @@ lib.nbldpc_qspa_exp_host.argtypes = [c_void_p, c_int, c_void_p]
 lib.nbldpc_qspa_layered_decode_batch.argtypes = lib.nbldpc_qspa_decode_batch.argtypes
 lib.nbldpc_qspa_layered_decode_host.argtypes = lib.nbldpc_qspa_decode_host.argtypes
 lib.nbldpc_qspa_layered_threads.argtypes = [c_void_p]
+lib.nbldpc_qspa_ws_decode_batch.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 6
+lib.nbldpc_qspa_ws_plan_host.argtypes = [c_int] * 6 + [c_void_p]
+lib.nbldpc_qspa_ws_info.argtypes = [c_void_p, c_int, c_void_p]
+lib.nbldpc_qspa_ws_slots.argtypes = [c_void_p, c_int, c_int]
 lib.nbldpc_demodulate_bpsk.argtypes = [c_void_p, c_void_p, c_float, c_int, c_void_p, c_void_p]
 lib.nbldpc_statistic.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
 lib.nbldpc_awgn_channel_host.argtypes = [c_void_p, c_float, c_void_p, c_int, c_int, c_void_p]
@@ -167,6 +171,20 @@ class NBCode(NBMatrix):
         """Threads per workgroup of k_nb_qspa_layered for this code (nbldpc_qspa_layered_threads): 256, 512 or 1024."""
         return int(lib.nbldpc_qspa_layered_threads(self._h))
 
+    def qspa_ws_info(self, layered=False):
+        """nbldpc_qspa_ws_info: the workspace tier's plan for this code, dict(threads, lds_bytes, slot_bytes, vectors), with the
+        switches the code was created under (NBLDPC_QSPA_WS_THREADS).  Raises LdpcError where the plan refuses the code."""
+        d = np.zeros(4, np.int32)
+        _check(lib.nbldpc_qspa_ws_info(self._h, 1 if layered else 0, _np(d)), "nbldpc_qspa_ws_info")
+        return dict(threads=int(d[0]), lds_bytes=int(d[1]), slot_bytes=int(d[2]), vectors=int(d[3]))
+
+    def qspa_ws_slots(self, B, layered=False):
+        """nbldpc_qspa_ws_slots: the workspace slots (= persistent workgroups) a workspace-tier call with B frames allocates on this
+        code: min(B, 1024, what fits in 2 GiB, NBLDPC_QSPA_WS_SLOTS as read when the code was created)."""
+        n = int(lib.nbldpc_qspa_ws_slots(self._h, 1 if layered else 0, B))
+        _check(min(n, 0), "nbldpc_qspa_ws_slots")
+        return n
+
     @property
     def persist_grid(self):
         return self.grids()["persist_grid"]
@@ -224,11 +242,33 @@ def Decoding_TMM(code, L_ch, maxIT=20, layered=False, want_state=False, stream=N
     return dict(DecodeOutput=out, iter_number=iters, ok=ok, LLR=LLR, L_c2v=c2v)
 
 
-def Decoding_QSPA(code, L_ch, maxIT=20, want_state=False, stream=None, layered=False):
+QSPA_LDS_LIMIT = 159 * 1024
+QSPA_TIERS = ("lds", "workspace", "auto")
+
+
+def qspa_lds_bytes(N, M, q, dc):
+    """The frame state of the LDS tier of Decoding_QSPA (include/nbldpc.h, "FHT sum-product": the bound is QSPA_LDS_LIMIT)."""
+    return 4 * (N * q + M * dc * q) + 4 * (N + 4) + q * q
+
+
+def QSPA_WS_Plan_host(N, M, q, dc, widest_level=0, layered=False):
+    """nbldpc_qspa_ws_plan_host: the plan of the workspace tier without a device, dict(threads, lds_bytes, slot_bytes, vectors).
+    widest_level (the most rows any dependency level holds) is read for layered=True only.  Raises LdpcError on a refusal."""
+    d = np.zeros(4, np.int32)
+    _check(lib.nbldpc_qspa_ws_plan_host(N, M, q, dc, widest_level, 1 if layered else 0, _np(d)), "QSPA_WS_Plan_host")
+    return dict(threads=int(d[0]), lds_bytes=int(d[1]), slot_bytes=int(d[2]), vectors=int(d[3]))
+
+
+def Decoding_QSPA(code, L_ch, maxIT=20, want_state=False, stream=None, layered=False, tier="lds"):
     """nbldpc_qspa_decode_batch: the FHT sum-product decoder (include/nbldpc.h, "FHT sum-product"; ours, the reference has none) for
     a batch; layered=True: nbldpc_qspa_layered_decode_batch, the row-by-row schedule ("FHT sum-product, layered schedule").  Returns
     the dict of Decoding_TMM: LLR [B,N,q] holds the APP probability vectors of the last executed iteration, L_c2v [B,M,dc,q] the
-    check-to-variable vectors, all q entries each, max-normalised with the floor 2^-40."""
+    check-to-variable vectors, all q entries each, max-normalised with the floor 2^-40.
+    tier: "lds" the calls above (a code whose frame state exceeds QSPA_LDS_LIMIT is refused); "workspace"
+    nbldpc_qspa_ws_decode_batch, the frame's vectors in a global-memory workspace ("FHT sum-product, workspace tier"); "auto" the LDS
+    call where qspa_lds_bytes fits, else the workspace call.  The results do not depend on it."""
+    if tier not in QSPA_TIERS:
+        raise ValueError("tier must be one of %s, not %r" % (", ".join(QSPA_TIERS), tier))
     if not (L_ch.is_cuda and L_ch.dtype == torch.float32 and L_ch.is_contiguous()):
         raise ValueError("L_ch must be a contiguous CUDA float32 tensor")
     if L_ch.dim() != 3 or L_ch.shape[1] != code.N or L_ch.shape[2] != code.q - 1:
@@ -240,6 +280,10 @@ def Decoding_QSPA(code, L_ch, maxIT=20, want_state=False, stream=None, layered=F
     APP = torch.empty((B, code.N, code.q), dtype=torch.float32, device=dev) if want_state else None
     c2v = torch.empty((B, code.M, code.dc, code.q), dtype=torch.float32, device=dev) if want_state else None
     st = c_void_p((stream or torch.cuda.current_stream(dev)).cuda_stream)
+    if tier == "workspace" or (tier == "auto" and qspa_lds_bytes(code.N, code.M, code.q, code.dc) > QSPA_LDS_LIMIT):
+        _check(lib.nbldpc_qspa_ws_decode_batch(code._h, _dev(L_ch), B, 1 if layered else 0, maxIT, _dev(out), _dev(iters), _dev(ok), _dev(APP),
+                                               _dev(c2v), st), "Decoding_QSPA")
+        return dict(DecodeOutput=out, iter_number=iters, ok=ok, LLR=APP, L_c2v=c2v)
     call = lib.nbldpc_qspa_layered_decode_batch if layered else lib.nbldpc_qspa_decode_batch
     _check(call(code._h, _dev(L_ch), B, maxIT, _dev(out), _dev(iters), _dev(ok), _dev(APP), _dev(c2v), st), "Decoding_QSPA")
     return dict(DecodeOutput=out, iter_number=iters, ok=ok, LLR=APP, L_c2v=c2v)

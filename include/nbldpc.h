@@ -64,7 +64,7 @@ int nbldpc_code_destroy(nbldpc_code *code);
 
 /* Name of the kernel the last decode call on this code launched (static string): "k_nb_ems2" = two frames in flight per workgroup,
  * "k_nb_ems" / "k_nb_ems_wide" one frame per workgroup (+ " (frames from a counter)": persistent workgroups), "k_nb_ems_hbm" the
- * workspace kernel, "k_nb_tmm…" the trellis decoders, "k_nb_qspa" the FHT sum-product decoder.  The counterpart of bldpc_last_kernel (include/bldpc.h); the reference has no
+ * workspace kernel, "k_nb_tmm…" the trellis decoders, "k_nb_qspa…" the FHT sum-product decoders.  The counterpart of bldpc_last_kernel (include/bldpc.h); the reference has no
  * equivalent -- its kernels are fixed at compile time (myNBLDPC/src/Decode_GPU.cu:138-356). */
 const char *nbldpc_last_kernel(const nbldpc_code *code);
 
@@ -361,8 +361,8 @@ int nbldpc_demodulate_bpsk_nq_host(int N, int q, const float *rx, float sigma, i
  *     power of two with 4 <= q <= 256; and, nbldpc_qspa_decode_batch only, a code whose frame state exceeds the kernel's LDS:
  *         4 (N q + M dcmax q) + 4 (N + 4) + q^2  <=  159 * 1024 bytes
  *     (p, one message array reused in place, decisions and flag, TableMultiply as bytes).  BDS.576.288.GF.64.txt takes 78 224 bytes;
- *     Tanner_74_9_Z128_GF16.txt and LDPC_N576_K480_GF256_exp.txt do not fit.  Nothing is launched on a refusal.  There is no
- *     workspace tier: a code that does not fit is decoded by the host statement or not at all.
+ *     Tanner_74_9_Z128_GF16.txt and LDPC_N576_K480_GF256_exp.txt do not fit.  Nothing is launched on a refusal.  A code
+ *     that does not fit is decoded by the workspace tier below (nbldpc_qspa_ws_decode_batch), never by this call.
  * nbldpc_qspa_decode_batch: all pointers DEVICE memory, asynchronous on `stream`, return codes as nbldpc_ems_decode_batch; one
  *     workgroup per frame (k_nb_qspa in nbldpc_last_kernel).  nbldpc_qspa_decode_host: HOST pointers, the node arrays and
  *     TableMultiply of nbldpc_code_create, serial.  nbldpc_qspa_exp_host: y[i] = qspa_exp(x[i]), for the tests. ---- */
@@ -408,6 +408,35 @@ int nbldpc_qspa_layered_decode_host(int N, int M, int q, int dvmax, int dcmax, c
                                     const unsigned *TableMultiply, const float *L_ch, int B, int maxIT, int *DecodeOutput,
                                     int *iter_number, int *ok, float *APP, float *c2v);
 int nbldpc_qspa_layered_threads(const nbldpc_code *code);
+
+/* ---- FHT sum-product, workspace tier --------------------------------------------------------------------------------------------
+ *
+ * Both schedules for the codes whose frame state exceeds the LDS bound above (Tanner_74_9_Z128_GF16.txt: 2.1 MB per frame;
+ * LDPC_N576_K480_GF256_exp.txt: 285 KB).  The results are those of the host statements nbldpc_qspa_decode_host (layered = 0) /
+ * nbldpc_qspa_layered_decode_host (layered != 0) bit for bit -- DecodeOutput, iter_number, ok, APP and c2v -- by the expressions of
+ * csrc/nbldpc_qspa_math.hpp and no other, never contracted.  Arguments and return codes are those of nbldpc_qspa_decode_batch.
+ * The frame's vectors live in a global-memory workspace slot, p [N][q] floats then the messages [M][dcmax][q] floats, that belongs to
+ * one workgroup for the whole launch; the workgroups are persistent and take their frames from a counter.  LDS holds the decisions,
+ * 4 flag words, TableMultiply as bytes and NV row slabs of dcmax * q floats, NV = threads / 64 * max(64 / q, 1):
+ *         4 (N + 4) + q^2 + 4 NV dcmax q  <=  159 * 1024 bytes.
+ * Plan.  threads = the largest of 1024, 512, 256, 128, 64 that meets the bound; layered: the smallest of those that meet it whose NV
+ *     holds the code's widest dependency level in one pass, if there is one.  The workspace is allocated and freed stream-ordered by
+ *     the call: min(B, 1024, what fits in 2 GiB) slots.
+ * Refusals (nothing launched, outputs untouched, nbldpc_last_kernel unchanged).  Those of nbldpc_qspa_decode_batch without its LDS
+ *     bound, layered: a row that lists one variable in two slots; and NBLDPC_EUNSUPPORTED where even 64 threads miss the bound above
+ *     (q = 256 with dcmax = 96, whatever N) or one slot does not fit in 2 GiB.  A code that fits the LDS tier is accepted as any other.
+ * nbldpc_last_kernel reads "k_nb_qspa_ws" / "k_nb_qspa_ws_layered".
+ * nbldpc_qspa_ws_plan_host: the plan without a device; info = {threads, LDS bytes, slot bytes, NV}.  widest_level is read for
+ *     layered != 0 only.  nbldpc_qspa_ws_info: the same for a code object, with the code's switches applied.  nbldpc_qspa_ws_slots: the
+ *     workspace slots (= workgroups) a call with B frames on this code allocates, or a negative return code.
+ * Experiment switches, read once at nbldpc_code_create; the results never depend on them: NBLDPC_QSPA_WS_SLOTS = n caps the slots;
+ *     NBLDPC_QSPA_WS_THREADS = 64 | 128 | 256 | 512 | 1024 pins the workgroup, and a size that misses the bound is
+ *     NBLDPC_EUNSUPPORTED at decode. ---- */
+int nbldpc_qspa_ws_decode_batch(nbldpc_code *code, const float *L_ch, int B, int layered, int maxIT, int *DecodeOutput, int *iter_number,
+                                int *ok, float *APP, float *c2v, void *stream);
+int nbldpc_qspa_ws_plan_host(int N, int M, int q, int dcmax, int widest_level, int layered, int info[4]);
+int nbldpc_qspa_ws_info(const nbldpc_code *code, int layered, int info[4]);
+int nbldpc_qspa_ws_slots(const nbldpc_code *code, int layered, int B);
 
 const char *nbldpc_last_error(void);
 

@@ -76,6 +76,9 @@ def main():
     ap.add_argument("--nb-matrix", default="BDS.576.288.GF.64.txt", help="nb: matrix file (under data/nb or a path); q from its header")
     ap.add_argument("--method", type=int, default=0, choices=[0, 1, 2, 3, 4, 5],
                     help="NB decoder_method (define.h:37): 0 EMS, 1 TMM, 2 log-QSPA, 3 layered TMM; ours: 4 FHT sum-product, 5 layered FHT sum-product")
+    ap.add_argument("--qspa-tier", default="lds", choices=["lds", "workspace", "auto"],
+                    help="NB --method 4|5: the tier of the FHT sum-product decoder; lds keeps a frame in LDS and refuses a code over its bound, "
+                         "workspace keeps it in a global-memory workspace, auto takes the workspace where lds refuses")
     ap.add_argument("--device-channel", action="store_true", help="generate the AWGN samples on the GPU (same RNG draws, device libm)")
     ap.add_argument("--pn-message", action="store_true", help="send random codewords (PN_Message 1, define.cuh:26); binary: needs --fixed")
     ap.add_argument("--pn-seed", type=int, default=1, help="--pn-message: seed of the message stream (bldpc_encode_random / nbldpc_encode_random)")
@@ -311,14 +314,15 @@ def main():
             print("# SNR      NTF  FER after each transmission ...  mean transmissions  throughput (information bits per bit sent)  AverIT")
             sweep_harq(code, rvs, cw, args.start, args.stop, args.step, snrtype=0 if args.snrtype is None else args.snrtype, maxIT=args.iters or 20,
                        batch=nbatch, max_batches=args.max_batches, decoder_method=args.method,
-                       PN_Message=1 if args.pn_message else 0, pn_seed=args.pn_seed, compact=not args.no_compact, **rmk)
+                       PN_Message=1 if args.pn_message else 0, pn_seed=args.pn_seed, compact=not args.no_compact, qspa_tier=args.qspa_tier, **rmk)
             return
         if ratematch:
             rmk["rate_match"] = rvs[0]
         print("# SNR      NTF   NEF         FER         BER  AverIT")
         sweep(code, cw, args.start, args.stop, args.step, maxIT=args.iters or 20, batch=nbatch,
               max_frames=None if args.max_batches is None else args.max_batches * nbatch, device_channel=dev_ch,
-              decoder_method=args.method, n_QAM=args.qam, CONSTELLATION=con, PN_Message=1 if args.pn_message else 0, pn_seed=args.pn_seed, **fad, **rmk)
+              decoder_method=args.method, n_QAM=args.qam, CONSTELLATION=con, PN_Message=1 if args.pn_message else 0, pn_seed=args.pn_seed,
+              qspa_tier=args.qspa_tier, **fad, **rmk)
     if world > 1:
         dist.destroy_process_group()
 
