@@ -1,7 +1,9 @@
-// nbldpc_qspa_kernel.hpp -- k_nb_qspa: the FHT sum-product decoder of include/nbldpc.h ("FHT sum-product"), one workgroup = one
-// frame, all iterations on-chip.  Every value is formed by the expressions of nbldpc_qspa_math.hpp in the order of the host statement
-// (nbldpc_qspa_host.hpp), which it equals bit for bit.  k_nb_qspa_layered ("FHT sum-product, layered schedule") is the same frame
-// body with phases C and D replaced by a walk over the rows' dependency levels; both call one check-row function.
+// nbldpc_qspa_kernel.hpp -- the kernels of the FHT sum-product decoders of include/nbldpc.h: k_nb_qspa ("FHT sum-product") and
+// k_nb_qspa_layered ("FHT sum-product, layered schedule"), one workgroup = one frame, all iterations on-chip; k_nb_qspa_ws and
+// k_nb_qspa_ws_layered ("FHT sum-product, workspace tier"), the same two for the codes whose frame state exceeds the LDS.  All four
+// run ONE frame body, qspa_decode_frame: every value is formed by the expressions of nbldpc_qspa_math.hpp in the order of the host
+// statement (nbldpc_qspa_host.hpp), which it equals bit for bit.  The layered schedule replaces phases C and D with a walk over the
+// rows' dependency levels; a tier decides where p and the messages live and how a check row reaches qspa_check_row (qspa_row).
 //
 // Lanes along the field.  A vector of q entries lives in W = min(q, 64) lanes of one wave: q = 64 one vector per wave (lane a <->
 // element a), q < 64 64/q vectors per wave (the transform's strides never cross a vector), q = 128 / 256 q/64 entries per lane
@@ -12,24 +14,41 @@
 // and keeps their stores back, so every cross-lane step runs with all lanes active; loops over a node's edges run to dvmax / dcmax
 // with the absent edges selected away, for the same reason.
 //
-// LDS (qspa_lds_bytes): p [N][q] floats, the message vectors [M][dcmax][q] floats, the decisions [N], the syndrome flag, and
+// LDS tier (qspa_lds_bytes): p [N][q] floats, the message vectors [M][dcmax][q] floats, the decisions [N], 4 flag words, and
 // TableMultiply as bytes [q][q].  ONE message array, reused in place: c2v -> v2c (phase C: entry a of every vector of a variable is
 // read and written by the same lane) -> the permuted vector -> U (phase D, one wave per row: the wave's LDS operations execute in
 // order, a wave-level fence keeps the compiler to it) -> the transform of out_t -> c2v.  The per-edge stride is q floats, unpadded:
 // ds_read_b32 / ds_write_b32 conflict within a group of 32 lanes on (address / 4) % 32, so a linear access of a vector is free of
 // conflicts for q >= 32 at any stride (32 consecutive floats), and for q = 4 ... 16 the 32/q vectors of a group lie in unrelated
 // slots that no one stride separates; the scatter and gather through TableMultiply hit banks as the permutation has them.
+//
+// Workspace tier.  p and the messages (stride and layout of the LDS tier) live in a global-memory slot that belongs to ONE workgroup
+// for the whole launch; LDS keeps the decisions, the flag words, TableMultiply and NV row slabs of dc * q floats, one per vector of
+// lanes (nbldpc_qspa_ws.hpp has the sizes and the plan).  Phases A and C and the syndrome run on the slot's addresses as they do on
+// LDS: entry a of a variable's vectors is read and written by one lane.  A check row goes through the vector's slab (qspa_row).
+//
+// Lanes without a row, workspace tier.  A vector with no row of its own in a pass recomputes the pass's last row in ITS OWN slab, with
+// valid = true for qspa_check_row (the slab is private, so unlike the LDS tier nothing there has to be held back), and keeps every
+// store to the slot back.  Its reads of the slot may race with the owning vector's write-back of the same row: intended and
+// harmless, what it computes is discarded and it stores nothing outside its slab.
+//
+// Visibility.  A slot is written and read by the waves of one workgroup only, with plain vector loads and stores, and every phase
+// ends in __syncthreads(), which orders the workgroup's global accesses as it orders its LDS accesses (the waves of a workgroup share
+// their CU's vector cache): what k_nb_ems_hbm relies on.  No agent-scope fence, no atomics on the slot.
+//
+// Frames, workspace tier.  Workgroups are persistent: each takes its next frame from the call's counter (work) until the batch is used
+// up, and a frame re-initialises p, sets the messages to 1.0f and resets the flag, so a slot serves several frames one after the other.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "nbldpc_qspa_math.hpp"
+#include "nbldpc_qspa_ws.hpp" // kQspaMaxLds, qspa_vectors, qspa_lds_bytes
 
 namespace cldpc {
 
 constexpr int kQspaThreads = 1024;
 constexpr int kQspaMaxDv = 8; // == kNbMaxDv: what nbldpc_code_create accepts
-constexpr size_t kQspaMaxLds = 159 * 1024;
 
 struct QspaArgs {
     const float *Lch; // [B][N][q-1]
@@ -48,10 +67,12 @@ struct QspaArgs {
     int N, M, dv, dc, B, max_iter, levels;
 };
 
-__host__ __device__ inline size_t qspa_lds_bytes(int N, int M, int q, int dc)
-{
-    return ((size_t)N * q + (size_t)M * dc * q) * sizeof(float) + ((size_t)N + 4) * sizeof(int) + (size_t)q * q;
-}
+struct QspaWsArgs {
+    QspaArgs a;
+    float *ws;        // [slots][ws_stride]
+    size_t ws_stride; // floats per slot: N q + M dc q
+    int *work;        // the call's frame counter (nb_launch)
+};
 
 // The value of lane ^ S.  All lanes of the vector the lane belongs to are active at every call.
 template <int S> __device__ __forceinline__ float qspa_lane_xor(float v)
@@ -67,7 +88,7 @@ template <int S> __device__ __forceinline__ float qspa_lane_xor(float v)
 template <int Q> struct QspaShape {
     static constexpr int EPL = Q > 64 ? Q / 64 : 1; // entries per lane
     static constexpr int W = Q < 64 ? Q : 64;       // lanes per vector
-    static constexpr int VPW = 64 / W;              // vectors per wave
+    static constexpr int VPW = qspa_vectors(64, Q); // vectors per wave
 };
 
 template <int W, int S = 1> __device__ __forceinline__ float qspa_lanes_max(float m)
@@ -188,21 +209,47 @@ __device__ __forceinline__ void qspa_check_row(float *row, const int *gf, int w,
     }
 }
 
-// One frame by one workgroup of NT threads, all iterations: the body of both kernels.  LAYERED false: phases C and D over all
-// variables and all rows (k_nb_qspa, NT a constant).  LAYERED true: the level sweep of k_nb_qspa_layered (NT = blockDim.x).
-template <int Q, bool LAYERED> __device__ __forceinline__ void qspa_decode_frame(const QspaArgs &a, const int NT)
+// One row through the check-node rule, by one vector of lanes: where the tiers differ.  first: the index in msg of the row's message
+// vectors [dc][Q] (an index, not a pointer to them: with the pointer the workspace tier's copies lost the constant offsets of their
+// loads, which then went out two at a time, and k_nb_qspa_ws<256> measured 8 % slower).  LDS tier: in place on them, stores under
+// valid.  Workspace tier: slot -> the vector's slab (FILLED: the layered sweep has written the row's v2c there already), the rule on
+// the slab, the c2v back to the slot under valid; entry el + 64 j is moved by the lane that owns it.
+template <int Q, bool WS, bool FILLED>
+__device__ __forceinline__ void qspa_row(float *msg, int first, float *slab, const int *gf, int w, bool valid, int dc, const unsigned char *mulb,
+                                         int lane, int el)
+{
+    constexpr int EPL = QspaShape<Q>::EPL;
+    if constexpr (!WS) {
+        qspa_check_row<Q>(msg + first, gf, w, valid, dc, mulb, lane, el);
+    } else {
+        if constexpr (!FILLED)
+            for (int t = 0; t < dc; t++)
+#pragma unroll
+                for (int j = 0; j < EPL; j++) slab[t * Q + el + 64 * j] = msg[first + t * Q + el + 64 * j];
+        qspa_wave_sync();
+        qspa_check_row<Q>(slab, gf, w, true, dc, mulb, lane, el);
+        qspa_wave_sync();
+        for (int t = 0; t < dc; t++)
+#pragma unroll
+            for (int j = 0; j < EPL; j++)
+                if (valid && t < w) msg[first + t * Q + el + 64 * j] = slab[t * Q + el + 64 * j];
+        qspa_wave_sync();
+    }
+}
+
+// Frame b by one workgroup of NT threads, all iterations: the body of all four kernels.  LAYERED false: phases C and D over all
+// variables and all rows.  LAYERED true: the level sweep.  WS false: p and msg in LDS, slab unused.  WS true: p and msg in the
+// workgroup's slot, slab this vector's row slab.  dec, flag and mulb (loaded by the caller) in LDS.  The caller derives every pointer
+// inside the kernel, so after inlining each access is an LDS or a global one, never a flat one.
+template <int Q, bool LAYERED, bool WS>
+__device__ __forceinline__ void qspa_decode_frame(const QspaArgs &a, const int NT, const size_t b, float *p, float *msg, float *slab, int *dec,
+                                                  int *flag, const unsigned char *mulb)
 {
     constexpr int EPL = QspaShape<Q>::EPL, W = QspaShape<Q>::W, VPW = QspaShape<Q>::VPW;
-    const int NV = NT / 64 * VPW;
-    extern __shared__ float qspa_lds[];
+    const int NV = qspa_vectors(NT, Q);
     const int N = a.N, M = a.M, dv = a.dv, dc = a.dc, TC = M * dc;
-    float *p = qspa_lds, *msg = p + N * Q;
-    int *dec = (int *)(msg + TC * Q), *flag = dec + N;
-    unsigned char *mulb = (unsigned char *)(flag + 4);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, sv = lane / W, el = lane & (W - 1), vbase = wave * VPW;
-    const size_t b = blockIdx.x;
 
-    for (int k = tid; k < Q * Q / 4; k += NT) ((uint32_t *)mulb)[k] = ((const uint32_t *)a.mul)[k];
     for (int k = tid; k < TC * Q; k += NT) msg[k] = 1.0f; // initial c2v; the slots beyond a row's weight keep it
     for (int ib = vbase; ib < N; ib += NV) {              // channel vectors
         const bool valid = ib + sv < N;
@@ -269,13 +316,14 @@ template <int Q, bool LAYERED> __device__ __forceinline__ void qspa_decode_frame
             // ---- the rows level by level ("FHT sum-product, layered schedule"): the rows of one level share no variable, every
             // earlier row that shares one with them has run and no later one has, so this is the serial order's result.  A vector of
             // lanes forms its row's v2c from p and the OTHER edges' slots as they stand (rows of other levels: nobody writes them
-            // now), writes them into the row's own slots (read by nobody else in this level), and runs the check-node rule there ----
+            // now), writes them into the row's own slots (read by nobody else in this level; workspace tier: into its slab), and runs
+            // the check-node rule there ----
             for (int lv = 0; lv < a.levels; lv++) {
                 const int lb = a.level_begin[lv], le = a.level_begin[lv + 1];
                 for (int rb = lb + vbase; rb < le; rb += NV) {
                     const bool valid = rb + sv < le;
                     const int r = a.row_order[valid ? rb + sv : le - 1], w = a.cn_w[r];
-                    float *row = msg + r * dc * Q;
+                    float *row = WS ? slab : msg + r * dc * Q;
                     for (int t = 0; t < dc; t++) {
                         const bool here = t < w;
                         const int self = r * dc + t, i = a.cn_vn[here ? self : r * dc], wi = a.vn_w[i];
@@ -292,11 +340,15 @@ template <int Q, bool LAYERED> __device__ __forceinline__ void qspa_decode_frame
 #pragma unroll
                             for (int j = 0; j < EPL; j++) x[j] = act ? qspa_norm_entry(y[j], mx) : x[j];
                         }
+                        // LDS tier: the slots beyond the row's weight keep their 1.0f and a lane without a row stores nothing.  Workspace
+                        // tier: the slab is the vector's own and holds another row's leftovers, so every slot of it is written
 #pragma unroll
-                        for (int j = 0; j < EPL; j++)
-                            if (valid && here) row[t * Q + el + 64 * j] = x[j];
+                        for (int j = 0; j < EPL; j++) {
+                            if constexpr (WS) row[t * Q + el + 64 * j] = here ? x[j] : 1.0f;
+                            else if (valid && here) row[t * Q + el + 64 * j] = x[j];
+                        }
                     }
-                    qspa_check_row<Q>(row, a.cn_gf + r * dc, w, valid, dc, mulb, lane, el);
+                    qspa_row<Q, WS, true>(msg, r * dc * Q, slab, a.cn_gf + r * dc, w, valid, dc, mulb, lane, el);
                 }
                 __syncthreads();
             }
@@ -331,11 +383,11 @@ template <int Q, bool LAYERED> __device__ __forceinline__ void qspa_decode_frame
                     }
             }
             __syncthreads();
-            // ---- D: check nodes, one vector of lanes per row, in place ----
+            // ---- D: check nodes, one vector of lanes per row ----
             for (int rb = vbase; rb < M; rb += NV) {
                 const bool valid = rb + sv < M;
                 const int r = valid ? rb + sv : M - 1;
-                qspa_check_row<Q>(msg + r * dc * Q, a.cn_gf + r * dc, a.cn_w[r], valid, dc, mulb, lane, el);
+                qspa_row<Q, WS, false>(msg, r * dc * Q, slab, a.cn_gf + r * dc, a.cn_w[r], valid, dc, mulb, lane, el);
             }
             __syncthreads();
         }
@@ -349,20 +401,57 @@ template <int Q, bool LAYERED> __device__ __forceinline__ void qspa_decode_frame
         for (int k = tid; k < TC * Q; k += NT) a.c2v[b * TC * Q + k] = msg[k];
 }
 
-template <int Q> __global__ __launch_bounds__(kQspaThreads) void k_nb_qspa(QspaArgs a) { qspa_decode_frame<Q, false>(a, kQspaThreads); }
+template <int Q> __device__ __forceinline__ void qspa_load_mul(unsigned char *mulb, const unsigned char *mul, int NT)
+{
+    for (int k = threadIdx.x; k < Q * Q / 4; k += NT) ((uint32_t *)mulb)[k] = ((const uint32_t *)mul)[k];
+}
+
+// The LDS tier's entry: the frame of this workgroup, its whole state carved from LDS.
+template <int Q, bool LAYERED> __device__ __forceinline__ void qspa_lds_entry(const QspaArgs &a, const int NT)
+{
+    extern __shared__ float qspa_lds[];
+    float *p = qspa_lds, *msg = p + a.N * Q;
+    int *dec = (int *)(msg + a.M * a.dc * Q), *flag = dec + a.N;
+    unsigned char *mulb = (unsigned char *)(flag + 4);
+    qspa_load_mul<Q>(mulb, a.mul, NT);
+    qspa_decode_frame<Q, LAYERED, false>(a, NT, blockIdx.x, p, msg, nullptr, dec, flag, mulb);
+}
+
+// The workspace tier's entry: the frames of this workgroup, one after the other in its slot.
+template <int Q, bool LAYERED> __device__ __forceinline__ void qspa_ws_entry(const QspaWsArgs &wa, const int NT)
+{
+    const QspaArgs &a = wa.a;
+    extern __shared__ float qspa_lds[];
+    int *dec = (int *)qspa_lds, *flag = dec + a.N; // flag[0]: a syndrome is non-zero; flag[1]: the workgroup's frame
+    unsigned char *mulb = (unsigned char *)(flag + 4);
+    const int lane = threadIdx.x & 63, vec = (threadIdx.x >> 6) * QspaShape<Q>::VPW + lane / QspaShape<Q>::W;
+    float *slab = (float *)(mulb + Q * Q) + (size_t)vec * a.dc * Q; // this vector's row slab
+    float *p = wa.ws + (size_t)blockIdx.x * wa.ws_stride, *msg = p + a.N * Q;
+    qspa_load_mul<Q>(mulb, a.mul, NT);
+    for (;;) {
+        if (threadIdx.x == 0) flag[1] = atomicAdd(wa.work, 1);
+        __syncthreads();
+        if (flag[1] >= a.B) break;
+        qspa_decode_frame<Q, LAYERED, true>(a, NT, (size_t)flag[1], p, msg, slab, dec, flag, mulb);
+        __syncthreads(); // the slot, the decisions and the flag words are reused by this workgroup's next frame
+    }
+}
+
+template <int Q> __global__ __launch_bounds__(kQspaThreads) void k_nb_qspa(QspaArgs a) { qspa_lds_entry<Q, false>(a, kQspaThreads); }
 
 // The layered schedule: launched with 256, 512 or 1024 threads (qspa_layered_threads or the experiment switch), the same LDS.
-template <int Q> __global__ __launch_bounds__(kQspaThreads) void k_nb_qspa_layered(QspaArgs a) { qspa_decode_frame<Q, true>(a, (int)blockDim.x); }
+template <int Q> __global__ __launch_bounds__(kQspaThreads) void k_nb_qspa_layered(QspaArgs a) { qspa_lds_entry<Q, true>(a, (int)blockDim.x); }
 
-// Threads per workgroup of k_nb_qspa_layered: 256 where its waves hold the widest level in one pass (256 / 64 * vectors per wave
-// rows at a time), else 512.  The row sweep is where an iteration's time goes, and it can use no more vectors than a level has rows.
+// Launched with the plan's threads (64 ... 1024), LDS bytes and one workgroup per workspace slot.
+template <int Q> __global__ __launch_bounds__(kQspaThreads) void k_nb_qspa_ws(QspaWsArgs wa) { qspa_ws_entry<Q, false>(wa, (int)blockDim.x); }
+
+template <int Q> __global__ __launch_bounds__(kQspaThreads) void k_nb_qspa_ws_layered(QspaWsArgs wa) { qspa_ws_entry<Q, true>(wa, (int)blockDim.x); }
+
+// Threads per workgroup of k_nb_qspa_layered: 256 where its waves hold the widest level in one pass (qspa_vectors rows at a time),
+// else 512.  The row sweep is where an iteration's time goes, and it can use no more vectors than a level has rows.
 // 1024 is never chosen: on BDS.576.288.GF.64 (levels of up to 10 rows) it covers every level in one pass and still measured 1.5 times
 // the time of 512, because the runtime keeps one workgroup of 1024 resident per CU where it keeps two of 512; it stays
 // in the set for the experiment switch.
-inline int qspa_layered_threads(int q, int widest_level)
-{
-    const int vpw = q < 64 ? 64 / q : 1;
-    return 256 / 64 * vpw >= widest_level ? 256 : 512;
-}
+inline int qspa_layered_threads(int q, int widest_level) { return qspa_vectors(256, q) >= widest_level ? 256 : 512; }
 
 } // namespace cldpc

@@ -47,25 +47,25 @@ int main()
                         if (!pl.threads) {
                             refused++;
                             NEED(pl.why && pl.why[0]);
-                            NEED(qspa_ws_lds_bytes(N, q, dc, 64) > kQspaWsMaxLds || qspa_ws_slot_bytes(N, M, q, dc) >= kQspaWsMaxBytes);
+                            NEED(qspa_ws_lds_bytes(N, q, dc, 64) > kQspaMaxLds || qspa_ws_slot_bytes(N, M, q, dc) >= kQspaWsMaxBytes);
                             all.insert(all.end(), {0, 0, 0, 0});
                             continue;
                         }
                         NEED(qspa_ws_size_ok(pl.threads));
-                        NEED(pl.lds_bytes == qspa_ws_lds_bytes(N, q, dc, pl.threads) && pl.lds_bytes <= kQspaWsMaxLds);
-                        NEED(pl.vectors == qspa_ws_vectors(pl.threads, q) && pl.slot_bytes == qspa_ws_slot_bytes(N, M, q, dc));
+                        NEED(pl.lds_bytes == qspa_ws_lds_bytes(N, q, dc, pl.threads) && pl.lds_bytes <= kQspaMaxLds);
+                        NEED(pl.vectors == qspa_vectors(pl.threads, q) && pl.slot_bytes == qspa_ws_slot_bytes(N, M, q, dc));
                         if (!layered) {
                             last_threads = pl.threads; // the largest that fits: twice as many threads would not
-                            NEED(pl.threads == 1024 || qspa_ws_lds_bytes(N, q, dc, 2 * pl.threads) > kQspaWsMaxLds);
+                            NEED(pl.threads == 1024 || qspa_ws_lds_bytes(N, q, dc, 2 * pl.threads) > kQspaMaxLds);
                         } else {
                             NEED(pl.threads <= last_threads);
-                            if (pl.threads < last_threads) NEED(pl.vectors >= wide && (pl.threads == 64 || qspa_ws_vectors(pl.threads / 2, q) < wide));
-                            else NEED(pl.vectors < wide || pl.threads == 64 || qspa_ws_vectors(pl.threads / 2, q) < wide);
+                            if (pl.threads < last_threads) NEED(pl.vectors >= wide && (pl.threads == 64 || qspa_vectors(pl.threads / 2, q) < wide));
+                            else NEED(pl.vectors < wide || pl.threads == 64 || qspa_vectors(pl.threads / 2, q) < wide);
                         }
                         // a pin gives that size or a refusal, and never changes the slot
                         for (int pin : kQspaWsSizes) {
                             const QspaWsPlan pp = qspa_ws_plan(N, M, q, dc, wide, layered, pin);
-                            NEED(pp.threads == (qspa_ws_lds_bytes(N, q, dc, pin) <= kQspaWsMaxLds ? pin : 0));
+                            NEED(pp.threads == (qspa_ws_lds_bytes(N, q, dc, pin) <= kQspaMaxLds ? pin : 0));
                             NEED(!pp.threads || pp.slot_bytes == pl.slot_bytes);
                         }
                         NEED(!qspa_ws_plan(N, M, q, dc, wide, layered, 96).threads);

@@ -3,9 +3,13 @@ nbldpc_qspa_decode_host / nbldpc_qspa_layered_decode_host: DecodeOutput, iter_nu
 tests/nb_qspa_cases.py (flooding) and tests/nb_qspa_layered_cases.py (layered) under tier="workspace"; the code just over the LDS
 bound under "workspace" and "auto"; a GF(256) code with rows of 12 whose plan runs the rows in two passes; one and five workspace
 slots for 12 and 300 frames; pinned workgroup sizes; the two shipped matrices the LDS tier refuses; B = 1, no state outputs, a
-rate-matched input; the refusals; and the simulation loop.  tests/test_nb_qspa_ws_cpu.py asserts that the inputs are worth decoding."""
+rate-matched input; the refusals; and the simulation loop.  tests/test_nb_qspa_ws_cpu.py asserts that the inputs are worth decoding.
+The codes and texts of the refusals of all three decode calls, and which one wins where two apply, are pinned by
+tests/golden/nb_qspa_refusals.json; `python tests/test_nb_qspa_ws_gpu.py --record FILE` writes that file from the library it runs on."""
 import ctypes
+import json
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -269,6 +273,62 @@ def test_refusals(nb, tmp_path):
     assert code.last_kernel == "k_nb_qspa_ws"
 
 
+# ---- every refusal's code and text, and which one wins: as recorded in tests/golden/nb_qspa_refusals.json ---------------------------------
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "nb_qspa_refusals.json")
+CALLS = {"lds": ("nbldpc_qspa_decode_batch", None), "lds_layered": ("nbldpc_qspa_layered_decode_batch", None),
+         "ws": ("nbldpc_qspa_ws_decode_batch", 0), "ws_layered": ("nbldpc_qspa_ws_decode_batch", 1)}
+
+
+def refusals(nb, tmp):
+    """{"case/call": [return code, nbldpc_last_error text]} of the refused calls; last_kernel is unchanged after each."""
+    from nb_shape_cases import write_matrix
+    got = {}
+
+    def refuse(case, code, calls, B=2, maxIT=4):
+        L = torch.zeros((2, code.N, code.q - 1), dtype=torch.float32, device="cuda")
+        out = torch.zeros((2, code.N), dtype=torch.int32, device="cuda")
+        its, ok = torch.zeros(2, dtype=torch.int32, device="cuda"), torch.zeros(2, dtype=torch.int32, device="cuda")
+        P = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        for call in calls:
+            before = code.last_kernel
+            name, layered = CALLS[call]
+            args = (code._h, P(L), B) + (() if layered is None else (layered,)) + (maxIT, P(out), P(its), P(ok), None, None, None)
+            rc = getattr(nb.lib, name)(*args)
+            got["%s/%s" % (case, call)] = [rc, nb.lib.nbldpc_last_error().decode()]
+            assert rc != 0 and code.last_kernel == before, (case, call, rc, code.last_kernel)
+
+    def written(name, N, M, q, dv, dc, edges):
+        path = os.path.join(tmp, name + ".txt")
+        write_matrix(path, N, M, q, dv, dc, edges)
+        return nb.NBCode(path, Q.mul_table(q))
+
+    refuse("lds_over", dev_code(nb, "lds_over", False), ("lds", "lds_layered"))
+    mul, _, _ = nb.GFInitial(64, os.path.join(W.NB, "GF", "Arith.Table.GF.64.txt"))
+    refuse("zero_coefficient", nb.NBCode(os.path.join(W.NB, "LDPC_N576_K288_GF64_d1_exp.txt"), mul), CALLS)
+    repeat = written("repeat", 3, 1, 16, 2, 4, [(0, 0, 1), (0, 1, 2), (0, 0, 1), (0, 2, 3)])
+    refuse("repeated_variable", repeat, ("lds_layered", "ws_layered"))
+    small = dev_code(nb, "q16_part", False)
+    refuse("B_0", small, CALLS, B=0)
+    refuse("maxIT_0", small, CALLS, maxIT=0)
+    refuse("pin_too_large", dev_code(nb, "q256_dc12", False, NBLDPC_QSPA_WS_THREADS=512), ("ws", "ws_layered"))
+    # two refusals at once: the zero coefficient is named, not the LDS bound
+    M, edges = Q.graph(Q.LDS_OVER)
+    r0, c0, _ = edges[0]
+    over = Q.LDS_OVER
+    refuse("lds_over_and_zero_coefficient", written("over_zero", over.N, M, over.q, over.dv, over.dc, [(r0, c0, 0)] + list(edges[1:])),
+           ("lds", "lds_layered"))
+    return got
+
+
+def test_refusal_codes_and_texts_are_those_recorded(nb, tmp_path):
+    with open(GOLDEN) as f:
+        golden = json.load(f)
+    got = refusals(nb, str(tmp_path))
+    assert sorted(got) == sorted(golden["cases"])
+    for key in sorted(got):
+        assert got[key] == golden["cases"][key], key
+
+
 # ---- the simulation loop ----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("method", [4, 5])
 def test_simulation_counts_what_the_host_statement_decodes(nb, method):
@@ -293,3 +353,14 @@ def test_simulation_counts_what_the_host_statement_decodes(nb, method):
     with pytest.raises(LdpcError, match=r"\(-5\).*LDS"):  # the default tier is today's call
         S.Simulation_GPU(code, np.array([173, 173, 173], np.int32), sigma, S.NBSim(2.0), cw, maxIT=maxIT, batch=8, max_frames=8,
                          device_channel=True, decoder_method=method)
+
+
+if __name__ == "__main__":  # --record FILE COMMIT: the refusals of the library this runs on (built from COMMIT), in the golden file's form
+    import tempfile
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from cuda_ldpc_amd import nbldpc
+    at = sys.argv.index("--record")
+    with tempfile.TemporaryDirectory() as tmp, open(sys.argv[at + 1], "w") as f:
+        json.dump({"recorded": "by `python tests/test_nb_qspa_ws_gpu.py --record FILE COMMIT`, this file copied into a built checkout of "
+                               "COMMIT = " + sys.argv[at + 2], "cases": refusals(nbldpc, tmp)}, f, indent=1)
+        f.write("\n")
