@@ -119,6 +119,18 @@ lib.nbldpc_fading_channel_host_qam_frames.argtypes = [c_void_p, ctypes.c_float, 
 lib.nbldpc_demodulate_qam_fading.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_float, c_int, c_void_p, c_void_p]
 lib.nbldpc_demodulate_qam_fading_nq.argtypes = [c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.c_float, c_int, c_void_p, c_void_p]
 lib.nbldpc_demodulate_qam_fading_host.argtypes = [c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.c_float, c_int, c_void_p]
+lib.bldpc_hard_pack.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p]
+lib.bldpc_hard_pack_int.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p]
+lib.bldpc_hard_unpack.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p]
+lib.bldpc_hard_pack_host.argtypes = [c_void_p, c_int, c_int, c_void_p]
+lib.bldpc_hard_pack_int_host.argtypes = [c_void_p, c_int, c_int, c_void_p]
+lib.bldpc_hard_unpack_host.argtypes = [c_void_p, c_int, c_int, c_void_p]
+lib.bldpc_bsc_channel_device.argtypes = [c_void_p, ctypes.c_float, c_void_p, c_int, c_int, c_void_p, c_void_p]
+lib.bldpc_bsc_channel_host.argtypes = [c_void_p, ctypes.c_float, c_void_p, c_int, c_int, c_void_p]
+lib.bldpc_decode_bitflip.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
+lib.bldpc_decode_bitflip_host.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
+lib.bldpc_bitflip_info.argtypes = [c_void_p, c_void_p]
+lib.bldpc_bitflip_plan_host.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p]
 lib.bldpc_sigma.restype = ctypes.c_float
 lib.bldpc_sigma.argtypes = [ctypes.c_float, c_int, ctypes.c_float]
 

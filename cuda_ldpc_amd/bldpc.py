@@ -18,6 +18,8 @@ from .nbldpc import Get_CONSTELLATION  # noqa: F401  -- the constellation files 
 EXIT_FIXED, EXIT_BATCH_GLOBAL, EXIT_PER_FRAME = 0, 1, 2
 KERNEL_AUTO, KERNEL_TABLE, KERNEL_QC_LDS = 0, 1, 2
 STOP_PREFIX, STOP_SYNDROME = 0, 1  # stop rules of the layered decoder (bldpc.h)
+BF_THRESHOLD, BF_GRADIENT = 0, 1  # rules of the bit-flipping decoder (bldpc.h)
+BITFLIP_LDS_BOUND = 160 * 1024 - 1024  # the dynamic LDS a workgroup of k_bf may ask for: a code fits when its plan's figure is within it
 IL_NONE, IL_ROWCOL = 0, 1  # index rules of the QAM modem (bldpc.h): bit b of symbol s is bit s*m + b, or b*Ns + s (row-column interleaver)
 
 
@@ -196,6 +198,12 @@ class BinaryCode:
         check(lib.bldpc_code_qc_info(self._h, _np_ptr(d)), "bldpc_code_qc_info")
         return dict(variant=int(d[0]), variant_per_frame=int(d[1]), persist_grid=int(d[2]), frames_per_wg=int(d[3]),
                     force_regroup=bool(d[4]), no_persist=bool(d[5]), persist_grid_per_frame=int(d[6]))
+
+    def bitflip_info(self):
+        """bldpc_bitflip_info: dict(lds_bytes, threads, frames_per_wg, fits) of the bit-flipping kernel k_bf for this code, without a launch."""
+        d = np.zeros(4, np.int32)
+        check(lib.bldpc_bitflip_info(self._h, _np_ptr(d)), "bldpc_bitflip_info")
+        return dict(lds_bytes=int(d[0]), threads=int(d[1]), frames_per_wg=int(d[2]), fits=int(d[0]) <= BITFLIP_LDS_BOUND)
 
     @property
     def qc_variant(self):
@@ -564,6 +572,175 @@ def quant_host(H, J, L, Z, y, quant, max_iter=25, length=0, exit_mode=EXIT_FIXED
     y: float32 [N, F] host array (frame-fastest).  Returns dict(D=int32 [N+1, F], app=int32 [N, F] or None, iters=int32 [F])."""
     return _host_statement("quant_host", lib.bldpc_decode_layered_quant_host, H, J, L, Z, y, max_iter, lambda: _quant_ref(quant), length, exit_mode,
                            stop_rule, want_app, np.int32)
+
+
+# ---- hard-decision decoding: packed hard bits, the binary symmetric channel, bit flipping (bldpc.h) ----------------------------------------
+def _words(F):
+    return (int(F) + 31) // 32
+
+
+def _check_bits(bits, rows, F, dev=None):
+    """Packed hard bits [rows, ceil(F/32)] as the C ABI reads them: int32 words (torch has no uint32 arithmetic; the bits are the same)."""
+    W = _words(F)
+    if dev is None:
+        a = np.ascontiguousarray(bits)
+        if a.dtype not in (np.uint32, np.int32) or a.shape != (rows, W):
+            raise ValueError("bits must be a uint32 array [%d, %d]" % (rows, W))
+        return a.view(np.uint32)
+    if not (torch.is_tensor(bits) and bits.is_cuda and bits.dtype == torch.int32 and bits.is_contiguous() and tuple(bits.shape) == (rows, W)):
+        raise ValueError("bits must be a contiguous CUDA int32 tensor [%d, %d]" % (rows, W))
+    return bits
+
+
+def _pack_device(what, fn, src, dtype, stream):
+    if not (torch.is_tensor(src) and src.is_cuda and src.dtype == dtype and src.is_contiguous() and src.dim() == 2 and src.numel() > 0):
+        raise ValueError("%s needs a contiguous CUDA %s tensor [rows, F]" % (what, dtype))
+    rows, F = (int(x) for x in src.shape)
+    bits = torch.empty((rows, _words(F)), dtype=torch.int32, device=src.device)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(src.device)).cuda_stream)
+    check(fn(_dev_ptr(src), rows, F, _dev_ptr(bits), st), what)
+    return bits
+
+
+def Hard_Pack(Channel_Out, stream=None):
+    """bldpc_hard_pack: the hard decisions of Channel_Out (CUDA float32 [N, F]) as packed bits, CUDA int32 [N, ceil(F/32)]: frame f is
+    bit f % 32 of word f // 32, the bit is Channel_Out < 0 (-0.0 and NaN give 0), padding bits are 0."""
+    return _pack_device("Hard_Pack", lib.bldpc_hard_pack, Channel_Out, torch.float32, stream)
+
+
+def Hard_Pack_Int(CodeWord, stream=None):
+    """bldpc_hard_pack_int: the same layout from int32 bits [rows, F], the bit is != 0."""
+    return _pack_device("Hard_Pack_Int", lib.bldpc_hard_pack_int, CodeWord, torch.int32, stream)
+
+
+def Hard_Unpack(bits, F, stream=None):
+    """bldpc_hard_unpack: packed bits (CUDA int32 [rows, ceil(F/32)]) -> CUDA int32 [rows, F] of 0 and 1."""
+    if not (torch.is_tensor(bits) and bits.dim() == 2 and F > 0):
+        raise ValueError("bits must be a CUDA int32 tensor [rows, ceil(F/32)] and F > 0")
+    rows = int(bits.shape[0])
+    _check_bits(bits, rows, F, bits.device)
+    D = torch.empty((rows, int(F)), dtype=torch.int32, device=bits.device)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(bits.device)).cuda_stream)
+    check(lib.bldpc_hard_unpack(_dev_ptr(bits), rows, int(F), _dev_ptr(D), st), "Hard_Unpack")
+    return D
+
+
+def _pack_host(what, fn, src, dtype):
+    a = np.ascontiguousarray(src, dtype)
+    if a.ndim != 2 or a.size == 0:
+        raise ValueError("%s needs an array [rows, F]" % what)
+    bits = np.empty((a.shape[0], _words(a.shape[1])), np.uint32)
+    check(fn(_np_ptr(a), a.shape[0], a.shape[1], _np_ptr(bits)), what)
+    return bits
+
+
+def Hard_Pack_host(Channel_Out):
+    """bldpc_hard_pack_host: Hard_Pack over a host float32 array [N, F]; returns uint32 [N, ceil(F/32)]."""
+    return _pack_host("Hard_Pack_host", lib.bldpc_hard_pack_host, Channel_Out, np.float32)
+
+
+def Hard_Pack_Int_host(CodeWord):
+    """bldpc_hard_pack_int_host: Hard_Pack_Int over a host int32 array [rows, F]."""
+    return _pack_host("Hard_Pack_Int_host", lib.bldpc_hard_pack_int_host, CodeWord, np.int32)
+
+
+def Hard_Unpack_host(bits, F):
+    """bldpc_hard_unpack_host: packed host bits [rows, ceil(F/32)] -> int32 [rows, F]."""
+    bits = np.ascontiguousarray(bits)
+    if bits.ndim != 2 or F <= 0:
+        raise ValueError("bits must be [rows, ceil(F/32)] and F > 0")
+    bits = _check_bits(bits, bits.shape[0], F)
+    D = np.empty((bits.shape[0], int(F)), np.int32)
+    check(lib.bldpc_hard_unpack_host(_np_ptr(bits), bits.shape[0], int(F), _np_ptr(D)), "Hard_Unpack_host")
+    return D
+
+
+def _check_bsc(seed, p):
+    if not (isinstance(seed, np.ndarray) and seed.dtype == np.int32 and seed.size == 3):
+        raise ValueError("seed must be an int32 numpy array of 3")
+    if not (np.isfinite(p) and 0.0 <= p <= 0.5):
+        raise ValueError("p must be a crossover probability in [0, 0.5], not %r" % (p,))
+
+
+def BSCChannel_CPU(seed, p, N, F, CodeWord=None):
+    """bldpc_bsc_channel_host: the binary symmetric channel over the RandomModule stream.  Bit (f, n) is CodeWord[n, f] (None: the all-zero
+    word) flipped iff draw f * N + n is below p (a float32 compare).  seed (int32[3]) advances by N * F draws.  Returns packed bits,
+    uint32 [N, ceil(F/32)]."""
+    _check_bsc(seed, p)
+    cw = None if CodeWord is None else np.ascontiguousarray(CodeWord, np.int32)
+    if cw is not None and cw.shape != (N, F):
+        raise ValueError("CodeWord must be [N=%d, F=%d]" % (N, F))
+    bits = np.empty((N, _words(F)), np.uint32)
+    check(lib.bldpc_bsc_channel_host(_np_ptr(seed), ctypes.c_float(p), None if cw is None else _np_ptr(cw), N, F, _np_ptr(bits)), "BSCChannel_CPU")
+    return bits
+
+
+def BSCChannel_GPU(seed, p, N, F, device=None, CodeWord=None, stream=None):
+    """bldpc_bsc_channel_device: the same channel and the same draws on the device.  CodeWord: CUDA int32 [N, F] or None.  Returns
+    packed bits, CUDA int32 [N, ceil(F/32)]; seed advanced."""
+    _check_bsc(seed, p)
+    device = device or (CodeWord.device if CodeWord is not None else torch.device("cuda", torch.cuda.current_device()))
+    if CodeWord is not None and not (torch.is_tensor(CodeWord) and CodeWord.is_cuda and CodeWord.dtype == torch.int32 and CodeWord.is_contiguous()
+                                     and tuple(CodeWord.shape) == (N, F)):
+        raise ValueError("CodeWord must be a contiguous CUDA int32 tensor [N=%d, F=%d]" % (N, F))
+    bits = torch.empty((N, _words(F)), dtype=torch.int32, device=device)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(device)).cuda_stream)
+    check(lib.bldpc_bsc_channel_device(_np_ptr(seed), ctypes.c_float(p), _dev_ptr(CodeWord), N, F, _dev_ptr(bits), st), "BSCChannel_GPU")
+    return bits
+
+
+def LDPC_Decoder_BitFlip_GPU(code, bits, F, rule=BF_GRADIENT, max_iter=30, exit_mode=EXIT_FIXED, D=None, want_bits=False, stream=None, want_D=True):
+    """bldpc_decode_bitflip: hard-decision decoding by parallel bit flipping (semantics in include/bldpc.h), 32 frames in the bits of a
+    word, all iterations on-chip (k_bf).  bits: packed received bits, CUDA int32 [N, ceil(F/32)] (Hard_Pack, BSCChannel_GPU).
+    rule: BF_THRESHOLD (flip iff 2 u + e > d) or BF_GRADIENT (flip the variables of largest u + e).  EXIT_FIXED or EXIT_PER_FRAME.
+    Returns dict(D=int32 [N+1, F] with row N the syndrome flag, or None with want_D=False; Dbits=int32 [N+1, ceil(F/32)] or None;
+    iters=int32 [F])."""
+    if not isinstance(F, (int, np.integer)) or F <= 0:
+        raise ValueError("F must be a positive int")
+    if not (torch.is_tensor(bits) and bits.is_cuda):
+        raise ValueError("bits must be a CUDA int32 tensor [N, ceil(F/32)]")
+    dev = bits.device
+    _check_bits(bits, code.N, F, dev)
+    if D is not None:
+        _check_D(D, code.N, F, dev)
+    elif want_D:
+        D = torch.empty((code.N + 1, F), dtype=torch.int32, device=dev)
+    elif not want_bits:
+        raise ValueError("want_D=False needs want_bits=True: the call must have an output")
+    Dbits = torch.empty((code.N + 1, _words(F)), dtype=torch.int32, device=dev) if want_bits else None
+    iters = torch.empty(F, dtype=torch.int32, device=dev)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(dev)).cuda_stream)
+    check(lib.bldpc_decode_bitflip(code._h, _dev_ptr(bits), int(F), int(max_iter), int(rule), int(exit_mode), _dev_ptr(D), _dev_ptr(Dbits),
+                                   _dev_ptr(iters), st), "LDPC_Decoder_BitFlip_GPU")
+    return dict(D=D, Dbits=Dbits, iters=iters)
+
+
+def bitflip_host(H, J, L, Z, bits, F, rule=BF_GRADIENT, max_iter=30, exit_mode=EXIT_FIXED):
+    """bldpc_decode_bitflip_host: the bit-flipping decoder on the host (no device), the statement of its semantics.  bits: uint32
+    [N, ceil(F/32)].  Returns dict(D=int32 [N+1, F], Dbits=uint32 [N+1, ceil(F/32)], iters=int32 [F])."""
+    H = np.ascontiguousarray(H, np.int32)
+    if H.size != J * L:
+        raise ValueError("H must hold J*L shifts")
+    if not isinstance(F, (int, np.integer)) or F <= 0:
+        raise ValueError("F must be a positive int")
+    N = L * Z
+    bits = _check_bits(bits, N, F)
+    D = np.zeros((N + 1, F), np.int32)
+    Dbits = np.zeros((N + 1, _words(F)), np.uint32)
+    iters = np.zeros(F, np.int32)
+    check(lib.bldpc_decode_bitflip_host(J, L, Z, _np_ptr(H), _np_ptr(bits), int(F), int(max_iter), int(rule), int(exit_mode), _np_ptr(D),
+                                        _np_ptr(Dbits), _np_ptr(iters)), "bitflip_host")
+    return dict(D=D, Dbits=Dbits, iters=iters)
+
+
+def bitflip_plan_host(H, J, L, Z):
+    """bldpc_bitflip_plan_host: what BinaryCode.bitflip_info returns, from the block matrix alone (no device)."""
+    H = np.ascontiguousarray(H, np.int32)
+    if H.size != J * L:
+        raise ValueError("H must hold J*L shifts")
+    d = np.zeros(4, np.int32)
+    check(lib.bldpc_bitflip_plan_host(J, L, Z, _np_ptr(H), _np_ptr(d)), "bitflip_plan_host")
+    return dict(lds_bytes=int(d[0]), threads=int(d[1]), frames_per_wg=int(d[2]), fits=int(d[0]) <= BITFLIP_LDS_BOUND)
 
 
 def normalised_host(H, J, L, Z, y, max_iter=50, alpha=1.0, length=0, exit_mode=EXIT_FIXED, want_app=True):

@@ -12,7 +12,7 @@ struct bldpc_code;
 
 namespace cldpc {
 
-enum LayerSlot { kSlotMinSum, kSlotBp, kSlotQuant }; // the code object keeps one plan per layered decoder
+enum LayerSlot { kSlotMinSum, kSlotBp, kSlotQuant, kSlotBitflip }; // the code object keeps one plan per layered decoder, and one for bit flipping
 
 struct LayerPlan {
     bool built = false;

@@ -33,6 +33,10 @@ def binary_draws_per_frame(N):
     return 2 * N   # u1, u2 per sample (LDPC_Encoder.cu:32-33)
 
 
+def bsc_draws_per_frame(N):
+    return N       # the binary symmetric channel: one draw per bit (bldpc_bsc_channel_device)
+
+
 def nb_draws_per_frame(N, m):
     return 4 * N * m  # Real and Image part, two draws each (LDPC_Encoder.cpp:57-66)
 

@@ -13,7 +13,8 @@ import torch
 
 from . import sharding
 from ._lib import check, lib
-from .bldpc import (EXIT_BATCH_GLOBAL, EXIT_FIXED, EXIT_PER_FRAME, KERNEL_AUTO, STOP_PREFIX, STOP_SYNDROME, AWGNChannel_CPU, AWGNChannel_Fading_GPU,
+from .bldpc import (BF_GRADIENT, BF_THRESHOLD, BSCChannel_GPU, Hard_Pack, LDPC_Decoder_BitFlip_GPU,
+                    EXIT_BATCH_GLOBAL, EXIT_FIXED, EXIT_PER_FRAME, KERNEL_AUTO, STOP_PREFIX, STOP_SYNDROME, AWGNChannel_CPU, AWGNChannel_Fading_GPU,
                     AWGNChannel_GPU, AWGNChannel_QAM_Fading_GPU, AWGNChannel_QAM_GPU, AWGNChannel_RM_Combine_GPU, AWGNChannel_RM_GPU,
                     Decode_Statistic, Demodulate_QAM, Demodulate_QAM_Fading, Fading, Fading_Gains, Frames_Gather, Frames_Scatter, IL_NONE, IL_ROWCOL,
                     LDPC_Decoder_BP_GPU, LDPC_Decoder_GPU, LDPC_Decoder_Layered_GPU, LDPC_Decoder_Quant_GPU, Modulate_QAM, PN_CodeWords, Quant,
@@ -24,8 +25,10 @@ from .nbldpc import sigma_of as nb_sigma_of
 def _check_schedule(schedule, alpha, quant):
     """The schedule of a sweep against its alpha and quant, as Simulation_GPU and Simulation_HARQ_GPU both refuse them.  Returns
     (bp, layered): sum-product, any of the row-layered decoders."""
-    if schedule not in ("flooding", "layered", "bp", "quant"):
-        raise ValueError("schedule must be 'flooding', 'layered', 'bp' or 'quant'")
+    if schedule not in ("flooding", "layered", "bp", "quant", "hard"):
+        raise ValueError("schedule must be 'flooding', 'layered', 'bp', 'quant' or 'hard'")
+    if schedule == "hard" and (alpha != 1.0 or quant is not None):
+        raise ValueError("schedule='hard' decodes hard decisions by bit flipping: it has no alpha and no quant")
     bp = schedule == "bp"
     layered = schedule in ("layered", "bp", "quant")  # the row-layered decoders share modes, rules and outputs
     if bp and alpha != 1.0:
@@ -109,7 +112,7 @@ def _qam_receive(rm, rx, con_dev, scale, short_llr, interleave, acc=None, done=N
 def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, exit_mode=EXIT_BATCH_GLOBAL, kernel=KERNEL_AUTO,
                    leastErrorFrames=50, leastTestFrames=10000, displayStep=40960, dist=None, device=None, max_batches=None,
                    log=print, device_channel=False, PN_Message=0, pn_seed=0, schedule="flooding", alpha=1.0, stop_rule=None,
-                   n_QAM=2, CONSTELLATION=None, rate_match=None, short_llr=1.0e4, quant=None, interleave=IL_NONE, fading=None):
+                   n_QAM=2, CONSTELLATION=None, rate_match=None, short_llr=1.0e4, quant=None, interleave=IL_NONE, fading=None, hard_rule=None):
     """One SNR point (Simulation.cu:12-171).  `seed` (int32[3]) is the AWGN->seed state, advanced in place by the
     WHOLE batch on every rank so that all ranks stay on the reference's single noise stream.
 
@@ -150,6 +153,11 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
     by the prefix bits that are not shortened.  The caller passes the sigma of the derived rate, rate_match.rate(code.K).  Needs
     device_channel=True.
 
+    schedule="hard" decodes the hard decisions of the channel values with LDPC_Decoder_BitFlip_GPU (rule `hard_rule`, BF_GRADIENT by
+    default; `hard_rule` belongs to this schedule): whatever chain makes Channel_Out (BPSK, QAM, fading) is followed by Hard_Pack and the
+    decoder, EXIT_FIXED or EXIT_PER_FRAME.  Its flag is always the syndrome, so random codewords run with either exit mode.  `alpha`,
+    `quant`, `stop_rule` and `rate_match` are refused: a punctured position is an erasure, and a hard decoder has no value for it.
+
     fading (a Fading) puts flat Rayleigh block fading with receiver CSI on the channel (include/bldpc.h, "block fading"): every batch
     draws the gains of its S channel uses per frame (S = the transmitted bits over BPSK, ceil(bits / m) points over QAM) from the fading
     stream, fading.seed, which is advanced in place by the whole batch on every rank, ceil(S / Lc) draws per frame, while the noise
@@ -161,8 +169,19 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
     if PN_Message not in (0, 1):
         raise ValueError("PN_Message must be 0 (all-zero codeword) or 1 (random codewords)")
     bp, layered = _check_schedule(schedule, alpha, quant)
+    hard = schedule == "hard"
     if not layered and stop_rule is not None:
         raise ValueError("stop_rule belongs to schedule='layered', schedule='bp' and schedule='quant'")
+    if hard_rule is not None and not hard:
+        raise ValueError("hard_rule belongs to schedule='hard'")
+    if hard:
+        hard_rule = BF_GRADIENT if hard_rule is None else hard_rule
+        if hard_rule not in (BF_THRESHOLD, BF_GRADIENT):
+            raise ValueError("hard_rule must be BF_THRESHOLD or BF_GRADIENT")
+        if rate_match is not None:
+            raise ValueError("schedule='hard' takes no rate_match: punctured positions are erasures, and a hard decoder has no value for them")
+        if exit_mode not in (EXIT_FIXED, EXIT_PER_FRAME):
+            raise ValueError("schedule='hard' takes EXIT_FIXED or EXIT_PER_FRAME")
     norm = not layered and alpha != 1.0  # normalised min-sum on the flooding decoders (LDPC_Decoder_GPU(alpha=...))
     if norm and exit_mode not in (EXIT_FIXED, EXIT_PER_FRAME):
         raise ValueError("schedule='flooding' with alpha takes EXIT_FIXED or EXIT_PER_FRAME")
@@ -175,7 +194,7 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
             raise ValueError("schedule='%s' takes EXIT_FIXED or EXIT_PER_FRAME" % schedule)
         if PN_Message == 1 and stop_rule != STOP_SYNDROME and exit_mode != EXIT_FIXED:
             raise ValueError("PN_Message=1 with per-frame exit needs stop_rule=STOP_SYNDROME: STOP_PREFIX tests for the all-zero word")
-    elif PN_Message == 1 and exit_mode != EXIT_FIXED:
+    elif PN_Message == 1 and exit_mode != EXIT_FIXED and not hard:
         raise ValueError("PN_Message=1 needs exit_mode=EXIT_FIXED: the decoders' early exit tests for the all-zero word")
     if n_QAM != 2 and PN_Message == 1 and not device_channel:  # every refusal before anything touches the device
         raise ValueError("n_QAM != 2 needs device_channel=True: there is no host QAM channel on this path")
@@ -233,7 +252,12 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
             yd = torch.from_numpy(AWGNChannel_CPU(my_seed, sigma, code.N, count, CodeWord=None if cw is None else cw.cpu().numpy())).to(device)
         seed[:] = sharding.lcg_jump(seed, F * per_frame)
         dev_cnt.zero_()
-        if count and layered:
+        if count and hard:
+            r = LDPC_Decoder_BitFlip_GPU(code, Hard_Pack(yd), count, rule=hard_rule, max_iter=maxIT, exit_mode=exit_mode, D=D)
+            st = torch.cuda.current_stream(device).cuda_stream
+            check(lib.bldpc_statistic_per_frame(code._h, _dev_ptr(D), _dev_ptr(cw), count, length, _dev_ptr(r["iters"]), _dev_ptr(dev_cnt), st),
+                  "Statistic")
+        elif count and layered:
             if bp:
                 r = LDPC_Decoder_BP_GPU(code, yd, max_iter=maxIT, llr_scale=llr_scale, length=length, exit_mode=exit_mode, stop_rule=stop_rule, D=D)
             elif quant is not None:
@@ -271,6 +295,71 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
             log(format_row(SIM, ber_bits))
         if stop or (max_batches is not None and batches >= max_batches):
             return 1 if stop else 0
+
+
+def Simulation_BSC_GPU(code, seed, p, SIM, rule=BF_GRADIENT, Num_Frames_OneTime=4096, maxIT=30, exit_mode=EXIT_PER_FRAME, PN_Message=0, pn_seed=0,
+                       max_batches=None, leastErrorFrames=50, leastTestFrames=10000, displayStep=40960, dist=None, device=None, log=print):
+    """One point of a hard-decision sweep: the binary symmetric channel with crossover probability p, then bit flipping.  A batch is
+    PN_CodeWords (PN_Message=1; the all-zero word otherwise) -> BSCChannel_GPU -> LDPC_Decoder_BitFlip_GPU(rule) -> the statistics
+    of Simulation_GPU on D, whose flag row is the syndrome.  `seed` (int32[3]) is the RandomModule state, advanced in place by the WHOLE
+    batch on every rank, N draws per frame (sharding.bsc_draws_per_frame); the batch loop, its stop rule and the sharding over ranks are
+    those of Simulation_GPU.  SIM.SNR is printed as it is: the caller may keep p there."""
+    if PN_Message not in (0, 1):
+        raise ValueError("PN_Message must be 0 (all-zero codeword) or 1 (random codewords)")
+    if rule not in (BF_THRESHOLD, BF_GRADIENT):
+        raise ValueError("rule must be BF_THRESHOLD or BF_GRADIENT")
+    if exit_mode not in (EXIT_FIXED, EXIT_PER_FRAME):
+        raise ValueError("Simulation_BSC_GPU takes EXIT_FIXED or EXIT_PER_FRAME")
+    if not (np.isfinite(p) and 0.0 <= p <= 0.5):
+        raise ValueError("p must be a crossover probability in [0, 0.5], not %r" % (p,))
+    rank = dist.get_rank() if dist is not None and dist.is_initialized() else 0
+    world = dist.get_world_size() if dist is not None and dist.is_initialized() else 1
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    F = Num_Frames_OneTime
+    first, count = sharding.shard_frames(F, world, rank)
+    per_frame = sharding.bsc_draws_per_frame(code.N)
+    dev_cnt = torch.zeros(5, dtype=torch.int64, device=device)
+    D = torch.empty((code.N + 1, max(count, 1)), dtype=torch.int32, device=device)
+    length = code.K
+    batches = 0
+    while True:
+        SIM.num_Frames += F
+        my_seed = sharding.lcg_jump(seed, first * per_frame)
+        seed[:] = sharding.lcg_jump(seed, F * per_frame)
+        dev_cnt.zero_()
+        if count:
+            cw = PN_CodeWords(code, pn_seed, count, first_frame=batches * F + first, device=device) if PN_Message else None
+            bits = BSCChannel_GPU(my_seed, p, code.N, count, device=device, CodeWord=cw)
+            r = LDPC_Decoder_BitFlip_GPU(code, bits, count, rule=rule, max_iter=maxIT, exit_mode=exit_mode, D=D)
+            st = torch.cuda.current_stream(device).cuda_stream
+            check(lib.bldpc_statistic_per_frame(code._h, _dev_ptr(D), _dev_ptr(cw), count, length, _dev_ptr(r["iters"]), _dev_ptr(dev_cnt), st),
+                  "Statistic")
+        sharding.allreduce_counters(dev_cnt, dist)
+        c = dev_cnt.cpu().tolist()
+        SIM.num_Error_Frames += c[0]
+        SIM.num_Error_Bits += c[1]
+        SIM.Total_Iteration += c[2]
+        SIM.num_False_Frames += c[3]
+        SIM.num_Alarm_Frames += c[4]
+        batches += 1
+        stop = SIM.num_Error_Frames >= leastErrorFrames and SIM.num_Frames >= leastTestFrames
+        last = max_batches is not None and batches >= max_batches
+        if rank == 0 and log and (SIM.num_Frames % displayStep == 0 or stop or last):
+            log(format_row(SIM, length))
+        if stop or last:
+            return 1 if stop else 0
+
+
+def sweep_bsc(code, ps, seeds=(173, 173, 173), dist=None, log=print, **kw):
+    """Simulation_BSC_GPU at every crossover probability of `ps`, seed and counters reset at every point as in `sweep`: a list of
+    SimCounters whose SNR field holds p."""
+    out = []
+    for p in ps:
+        SIM = SimCounters()
+        SIM.SNR = float(p)
+        Simulation_BSC_GPU(code, np.array(seeds, np.int32), float(p), SIM, dist=dist, log=log, **kw)
+        out.append(SIM)
+    return out
 
 
 @dataclass
@@ -345,6 +434,8 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
     if PN_Message not in (0, 1):
         raise ValueError("PN_Message must be 0 (all-zero codeword) or 1 (random codewords)")
     bp, layered = _check_schedule(schedule, alpha, quant)
+    if schedule == "hard":
+        raise ValueError("HARQ takes no schedule='hard': soft combining has no meaning for hard decisions, and an unsent position is an erasure")
     if exit_mode not in (EXIT_FIXED, EXIT_PER_FRAME):
         raise ValueError("HARQ takes EXIT_FIXED or EXIT_PER_FRAME: the results of EXIT_BATCH_GLOBAL depend on the batch")
     if not layered and stop_rule is not None:

@@ -735,6 +735,58 @@ int bldpc_code_qc_info(const bldpc_code *code, int info[8]);
  *              [7] FNV-1a of the nested plan's seven digests (56 bytes, as stored), 0: no nested plan */
 int bldpc_qc_plan_host(int J, int L, int Z, const int *H, int pin, int flags, int info[8], unsigned long long digest[8]);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * Hard-decision decoding: packed hard bits, a binary symmetric channel and two bit-flipping decoders.
+ *
+ * Packed hard bits.  `bits` is uint32 [rows][W] with W = ceil(F / 32): frame f of row n is bit f % 32 of word [n][f / 32].  The bits
+ * of frames >= F in the last word of a row are padding: every producer below writes them as 0, every consumer ignores them.
+ *   bldpc_hard_pack       bit = Channel_Out[n][f] < 0, the layered decoders' hard-bit rule (-0.0f and NaN give 0)
+ *   bldpc_hard_pack_int   bit = CodeWord[n][f] != 0
+ *   bldpc_hard_unpack     D[n][f] = the bit, int32 0 or 1
+ * The device forms are asynchronous on `stream`; each has a _host statement over host arrays.
+ *
+ * Binary symmetric channel.  bits[n][f] = CodeWord[n][f] (NULL: the all-zero word) xor (u < p), u the draw f * N + n of the
+ * RandomModule stream `seed` (frame outer, bit inner, one draw per bit, a float compare).  seed is advanced by N * F draws, as the
+ * AWGN calls advance theirs.  BLDPC_EINVAL: p not finite or outside [0, 0.5], a seed state outside [0, modulus).
+ *
+ * Bit flipping.  Per frame: r[N] the received bits, x = r; d_v the column weight of v; s_c the XOR of x_v over check row c (rows and
+ * their variables as in bldpc_decode_layered).  Iteration k = 1 .. max_iter:
+ *   1. if every s_c is 0 nothing flips;
+ *   2. otherwise, with u_v the number of unsatisfied checks of v and e_v = x_v xor r_v, all flips are decided from the same s and
+ *      applied together:
+ *        BLDPC_BF_THRESHOLD  flip v iff 2 u_v + e_v > d_v
+ *        BLDPC_BF_GRADIENT   flip every v with E_v = u_v + e_v equal to the maximum of E over the N variables of the frame
+ *   3. s is recomputed; the flag is "every s_c is 0".
+ * BLDPC_EXIT_PER_FRAME: a frame stops after the first iteration that leaves its flag set, iters[f] is that k (a clean word: 1).
+ * BLDPC_EXIT_FIXED: max_iter iterations, iters[f] = max_iter when iters is given.  A converged frame never flips again, so both
+ * modes return the same D, Dbits and flags.  BLDPC_EXIT_BATCH_GLOBAL is refused.
+ *   D      int32 [N+1][F], row N the flag (what bldpc_statistic and bldpc_syndrome take), or NULL
+ *   Dbits  uint32 [N+1][W] packed, row N the flags, or NULL; at least one of the two
+ * BLDPC_EINVAL: unknown rule or mode, max_iter < 1, F <= 0, null input, both outputs null, iters NULL with per-frame exit.
+ * BLDPC_EUNSUPPORTED (kept with the code object, the same text at every call): a code built from an address table; a code whose
+ * 32-frame state, 4 (N + M) bytes, exceeds the LDS a workgroup may use (there is no workspace tier).  Block rows of weight 1 and
+ * block columns of weight 0 are taken.  The device call is asynchronous on `stream` and allocates nothing once its scratch has grown;
+ * the _host form is the definition (plain C++, one frame at a time, at most 16 threads).
+ *
+ * bldpc_bitflip_info / bldpc_bitflip_plan_host: info[4] = LDS bytes of a workgroup of k_bf, threads, frames per workgroup, 0; the
+ * first for a code object without a launch, the second without a device.  A code fits when info[0] <= 162816. */
+#define BLDPC_BF_THRESHOLD 0
+#define BLDPC_BF_GRADIENT 1
+int bldpc_hard_pack(const float *Channel_Out, int N, int F, unsigned *bits, void *stream);
+int bldpc_hard_pack_int(const int *CodeWord, int N, int F, unsigned *bits, void *stream);
+int bldpc_hard_unpack(const unsigned *bits, int rows, int F, int *D, void *stream);
+int bldpc_hard_pack_host(const float *Channel_Out, int N, int F, unsigned *bits);
+int bldpc_hard_pack_int_host(const int *CodeWord, int N, int F, unsigned *bits);
+int bldpc_hard_unpack_host(const unsigned *bits, int rows, int F, int *D);
+int bldpc_bsc_channel_device(int seed[3], float p, const int *CodeWord, int N, int F, unsigned *bits, void *stream);
+int bldpc_bsc_channel_host(int seed[3], float p, const int *CodeWord, int N, int F, unsigned *bits);
+int bldpc_decode_bitflip(bldpc_code *code, const unsigned *bits_in, int F, int max_iter, int rule, int exit_mode, int *D, unsigned *Dbits,
+                         int *iters, void *stream);
+int bldpc_decode_bitflip_host(int J, int L, int Z, const int *H, const unsigned *bits_in, int F, int max_iter, int rule, int exit_mode, int *D,
+                              unsigned *Dbits, int *iters);
+int bldpc_bitflip_info(bldpc_code *code, int info[4]);
+int bldpc_bitflip_plan_host(int J, int L, int Z, const int *H, int info[4]);
+
 const char *bldpc_last_error(void);
 
 #ifdef __cplusplus

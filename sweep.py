@@ -7,6 +7,8 @@
     python sweep.py binary --device-channel --layered --per-frame --pn-message --qam 64 --interleave rowcol --snrtype 0 --harq 0:2160,2160:144,500:2400 --start 8 --stop 9 --step 0.5
     python sweep.py binary --device-channel --bp --per-frame --stop-rule syndrome --pn-message --start 2 --stop 3 --step 0.2
     python sweep.py binary --device-channel --quant 6,8,6 --norm8 6 --llr-scale 16 --per-frame --stop-rule syndrome --pn-message --start 2 --stop 3 --step 0.2
+    python sweep.py binary --hard gradient --per-frame --pn-message --bsc 0.002,0.004,0.006
+    python sweep.py binary --hard threshold --device-channel --per-frame --start 4 --stop 6 --step 0.5
     python sweep.py binary --device-channel --per-frame --layered --pn-message --qam 64 --interleave rowcol --fading 16 --harq 0:2160,2160:48,500:2300
     python sweep.py nb --pn-message --qam 64 --fading 16
     python sweep.py nb --device-channel --pn-message --puncture 88:96
@@ -92,6 +94,11 @@ def main():
     ap.add_argument("--quant-offset", type=int, default=0, help="--quant: offset subtracted after the normalisation")
     ap.add_argument("--llr-scale", type=float, default=16.0, help="--quant: quantiser gain on the channel value (resolution only: min-sum is "
                     "scale-invariant; below about 16 the rate-5/6 codes lose error rate)")
+    ap.add_argument("--hard", choices=["threshold", "gradient"], default=None, help="binary: hard-decision decoding by parallel bit flipping "
+                    "(bldpc_decode_bitflip) on the hard decisions of the channel values: threshold = flip iff 2 u + e > d, gradient = flip the "
+                    "variables of largest u + e; with --device-channel and --fixed or --per-frame; no --alpha, --stop-rule, --shorten / --puncture, --harq")
+    ap.add_argument("--bsc", metavar="P[,P...]", default=None, help="--hard: crossover probabilities of a binary symmetric channel in place of the "
+                    "SNR list (Simulation_BSC_GPU; the first column of a row is P)")
     ap.add_argument("--alpha", type=float, default=1.0, help="binary: normalisation factor in (0, 1]; with --layered the layered decoder's, without it "
                     "normalised min-sum on the flooding decoders (with --fixed or --per-frame)")
     ap.add_argument("--stop-rule", choices=["prefix", "syndrome"], default=None,
@@ -152,6 +159,23 @@ def main():
         quant = (ch, app, msg, args.norm8, args.quant_offset, args.llr_scale)  # checked by Quant once the package is imported
     elif args.norm8 != 6 or args.quant_offset != 0 or args.llr_scale != 16.0:
         ap.error("--norm8, --quant-offset and --llr-scale belong to --quant")
+    bsc = None
+    if args.hard is not None:
+        if (args.which != "binary" or args.layered or args.bp or quant is not None or args.alpha != 1.0 or args.stop_rule is not None or args.as_written
+                or args.shorten is not None or args.puncture is not None or args.harq is not None or not (args.fixed or args.per_frame)):
+            ap.error("--hard belongs to the binary sweep on a QC code with --fixed or --per-frame, without --layered, --bp, --quant, --alpha, "
+                     "--stop-rule, --shorten, --puncture and --harq (a hard decoder has no value for an unsent position)")
+        if args.bsc is not None:
+            try:
+                bsc = [float(x) for x in args.bsc.split(",")]
+            except ValueError:
+                ap.error("--bsc takes crossover probabilities P[,P...]")
+            if not bsc or not all(0.0 <= x <= 0.5 for x in bsc) or args.qam != 2 or fade is not None:
+                ap.error("--bsc takes probabilities in [0, 0.5] and replaces the channel: no --qam, no --fading")
+        elif not args.device_channel:
+            ap.error("--hard without --bsc needs --device-channel")
+    elif args.bsc is not None:
+        ap.error("--bsc belongs to --hard")
     rows = args.layered or args.bp or quant is not None  # the row-layered decoders take the same modes and rules
     if args.which == "binary" and rows:
         if args.as_written or not (args.fixed or args.per_frame):
@@ -162,7 +186,7 @@ def main():
         ap.error("--stop-rule belongs to the binary sweep with --layered, --bp or --quant, --alpha to the binary sweep")
     elif args.alpha != 1.0 and not (args.fixed or args.per_frame):
         ap.error("--alpha without --layered (normalised flooding min-sum) needs --fixed or --per-frame")
-    if args.which == "binary" and not rows and args.pn_message and (not args.fixed or args.as_written):
+    if args.which == "binary" and not rows and args.hard is None and args.pn_message and (not args.fixed or args.as_written):
         ap.error("--pn-message needs the binary sweep with --fixed (the decoders' early exit tests for the all-zero word) on a QC code")
     if args.which == "binary" and args.qam != 2 and not (args.pn_message and args.device_channel):
         ap.error("binary --qam %d needs --pn-message (a QAM channel is not symmetric: the all-zero word is not representative) and "
@@ -234,6 +258,21 @@ def main():
                     lay = dict(schedule="quant", quant=C.Quant(*quant), stop_rule=lay["stop_rule"])
                 except ValueError as e:
                     ap.error("--quant: %s" % e)
+        if args.hard is not None:
+            lay = dict(schedule="hard", hard_rule=C.BF_GRADIENT if args.hard == "gradient" else C.BF_THRESHOLD)
+        if bsc is not None:
+            from cuda_ldpc_amd.simulation import sweep_bsc
+            if rank == 0:
+                print("# %s N=%d K=%d, binary symmetric channel, bit flipping (%s rule), %s, maxIT=%d, batch=%d x %d GPU(s)%s" % (
+                    os.path.basename(args.matrix), code.N, code.K, args.hard, "fixed iterations" if args.fixed else "per-frame early exit",
+                    args.iters or 30, args.batch, world, ", random codewords (PN seed %d)" % args.pn_seed if args.pn_message else ""))
+                print("#   P      NTF   NEF         FER         BER  AverIT       FER_F      FER_A")
+            sweep_bsc(code, bsc, dist=dist, rule=lay["hard_rule"], Num_Frames_OneTime=args.batch, maxIT=args.iters or 30,
+                      exit_mode=C.EXIT_FIXED if args.fixed else C.EXIT_PER_FRAME, max_batches=args.max_batches, displayStep=10 ** 12,
+                      PN_Message=1 if args.pn_message else 0, pn_seed=args.pn_seed, log=print if rank == 0 else None)
+            if world > 1:
+                dist.destroy_process_group()
+            return
         mod = {}
         if args.qam != 2:  # the GF(q) half's constellation file and sigma (Eb/N0, n_QAM in the formula): the two sweeps share both
             mod = dict(n_QAM=args.qam, CONSTELLATION=C.Get_CONSTELLATION(os.path.join(nbd, "Constellation", "GRAY_%dQAM.txt" % args.qam), args.qam),
@@ -274,13 +313,14 @@ def main():
                   "layered sum-product llr_scale=%s stop=%s, " % ("2/sigma^2" if args.qam == 2 else "1", stop) if args.bp else
                   "quantised layered min-sum %r stop=%s, " % (lay["quant"], stop) if quant is not None else
                   "layered min-sum alpha=%g stop=%s, " % (args.alpha, stop) if args.layered else
+                  "hard decisions, bit flipping (%s rule), " % args.hard if args.hard is not None else
                   ("normalised flooding min-sum alpha=%g, " % args.alpha if args.alpha != 1.0 else ""),
                   "fixed iterations" if args.fixed else ("per-frame early exit" if args.per_frame else "batch-global early exit"),
-                  args.iters or (25 if rows else 50), args.batch, world,
+                  args.iters or (25 if rows else 30 if args.hard is not None else 50), args.batch, world,
                   ", random codewords (PN seed %d, K'=%d), syndrome flag" % (args.pn_seed, code.K_info) if args.pn_message else "")
                   + (fade_words if fade is not None else ""))
             print("# SNR      NTF   NEF         FER         BER  AverIT       FER_F      FER_A")
-        sweep(code, args.start, args.stop, args.step, snrtype=1 if args.qam == 2 else 0, dist=dist, Num_Frames_OneTime=args.batch, maxIT=args.iters or (25 if rows else 50),
+        sweep(code, args.start, args.stop, args.step, snrtype=1 if args.qam == 2 else 0, dist=dist, Num_Frames_OneTime=args.batch, maxIT=args.iters or (25 if rows else 30 if args.hard is not None else 50),
               exit_mode=C.EXIT_FIXED if args.fixed else (C.EXIT_PER_FRAME if args.per_frame else C.EXIT_BATCH_GLOBAL), max_batches=args.max_batches, displayStep=10 ** 12, device_channel=args.device_channel,
               PN_Message=1 if args.pn_message else 0, pn_seed=args.pn_seed, log=print if rank == 0 else None, **lay, **mod, **fad)
     else:
