@@ -131,6 +131,18 @@ lib.bldpc_decode_bitflip.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_
 lib.bldpc_decode_bitflip_host.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
 lib.bldpc_bitflip_info.argtypes = [c_void_p, c_void_p]
 lib.bldpc_bitflip_plan_host.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p]
+lib.bldpc_bec_channel_device.argtypes = [c_void_p, ctypes.c_float, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]
+lib.bldpc_bec_channel_host.argtypes = [c_void_p, ctypes.c_float, c_void_p, c_int, c_int, c_void_p, c_void_p]
+lib.bldpc_decode_erasure.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+lib.bldpc_decode_erasure_host.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
+lib.bldpc_erasure_info.argtypes = [c_void_p, c_void_p]
+lib.bldpc_erasure_plan_host.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p]
+lib.bldpc_rm_select_bits.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p]
+lib.bldpc_rm_recover_bits.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]
+lib.bldpc_rm_select_bits_host.argtypes = [c_void_p, c_void_p, c_int, c_void_p]
+lib.bldpc_rm_recover_bits_host.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
+lib.bldpc_statistic_bits.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]
+lib.bldpc_statistic_bits_host.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]
 lib.bldpc_sigma.restype = ctypes.c_float
 lib.bldpc_sigma.argtypes = [ctypes.c_float, c_int, ctypes.c_float]
 

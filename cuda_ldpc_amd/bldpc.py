@@ -205,6 +205,12 @@ class BinaryCode:
         check(lib.bldpc_bitflip_info(self._h, _np_ptr(d)), "bldpc_bitflip_info")
         return dict(lds_bytes=int(d[0]), threads=int(d[1]), frames_per_wg=int(d[2]), fits=int(d[0]) <= BITFLIP_LDS_BOUND)
 
+    def erasure_info(self):
+        """bldpc_erasure_info: dict(lds_bytes, threads, frames_per_wg, fits) of the peeling kernel k_er for this code, without a launch."""
+        d = np.zeros(4, np.int32)
+        check(lib.bldpc_erasure_info(self._h, _np_ptr(d)), "bldpc_erasure_info")
+        return dict(lds_bytes=int(d[0]), threads=int(d[1]), frames_per_wg=int(d[2]), fits=int(d[0]) <= ERASURE_LDS_BOUND)
+
     @property
     def qc_variant(self):
         """Index into qc_variants() of the fused kernel variant this code runs on (-1: the table kernels serve it)."""
@@ -743,6 +749,155 @@ def bitflip_plan_host(H, J, L, Z):
     return dict(lds_bytes=int(d[0]), threads=int(d[1]), frames_per_wg=int(d[2]), fits=int(d[0]) <= BITFLIP_LDS_BOUND)
 
 
+# ---- erasure decoding: erased words, the binary erasure channel, peeling, statistics on packed words (bldpc.h) ----------------------------
+ERASURE_LDS_BOUND = BITFLIP_LDS_BOUND  # k_er's state, 4 (2 N + M) bytes, against the same bound
+
+
+def _check_bec(seed, p):
+    if not (isinstance(seed, np.ndarray) and seed.dtype == np.int32 and seed.size == 3):
+        raise ValueError("seed must be an int32 numpy array of 3")
+    if not (np.isfinite(p) and 0.0 <= p <= 1.0):
+        raise ValueError("p must be an erasure probability in [0, 1], not %r" % (p,))
+
+
+def BECChannel_CPU(seed, p, N, F, CodeWord=None):
+    """bldpc_bec_channel_host: the binary erasure channel over the RandomModule stream.  Bit (f, n) is erased iff draw f * N + n is
+    below p (the BSC's indexing and float32 compare); bits = CodeWord (None: the all-zero word) with 0 at the erased positions.  seed
+    (int32[3]) advances by N * F draws.  Returns (bits, erased), uint32 [N, ceil(F/32)] each."""
+    _check_bec(seed, p)
+    cw = None if CodeWord is None else np.ascontiguousarray(CodeWord, np.int32)
+    if cw is not None and cw.shape != (N, F):
+        raise ValueError("CodeWord must be [N=%d, F=%d]" % (N, F))
+    bits, erased = np.empty((N, _words(F)), np.uint32), np.empty((N, _words(F)), np.uint32)
+    check(lib.bldpc_bec_channel_host(_np_ptr(seed), ctypes.c_float(p), None if cw is None else _np_ptr(cw), N, F, _np_ptr(bits), _np_ptr(erased)),
+          "BECChannel_CPU")
+    return bits, erased
+
+
+def BECChannel_GPU(seed, p, N, F, device=None, CodeWord=None, stream=None):
+    """bldpc_bec_channel_device: the same channel and the same draws on the device.  CodeWord: CUDA int32 [N, F] or None.  Returns
+    (bits, erased), CUDA int32 [N, ceil(F/32)] each; seed advanced."""
+    _check_bec(seed, p)
+    device = device or (CodeWord.device if CodeWord is not None else torch.device("cuda", torch.cuda.current_device()))
+    if CodeWord is not None and not (torch.is_tensor(CodeWord) and CodeWord.is_cuda and CodeWord.dtype == torch.int32 and CodeWord.is_contiguous()
+                                     and tuple(CodeWord.shape) == (N, F)):
+        raise ValueError("CodeWord must be a contiguous CUDA int32 tensor [N=%d, F=%d]" % (N, F))
+    bits = torch.empty((N, _words(F)), dtype=torch.int32, device=device)
+    erased = torch.empty((N, _words(F)), dtype=torch.int32, device=device)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(device)).cuda_stream)
+    check(lib.bldpc_bec_channel_device(_np_ptr(seed), ctypes.c_float(p), _dev_ptr(CodeWord), N, F, _dev_ptr(bits), _dev_ptr(erased), st),
+          "BECChannel_GPU")
+    return bits, erased
+
+
+def LDPC_Decoder_Erasure_GPU(code, bits, erased, F, max_iter=100, D=None, want_bits=True, want_erased=True, want_D=False, stream=None):
+    """bldpc_decode_erasure: parallel peeling on the erasure channel (semantics in include/bldpc.h), 32 frames in the bits of a word, all
+    iterations on-chip (k_er).  bits, erased: CUDA int32 [N, ceil(F/32)] (BECChannel_GPU, RM_Recover_Bits).  Returns dict(D=int32
+    [N+1, F] with row N the flag, given or with want_D=True, else None; Dbits=int32 [N+1, ceil(F/32)] or None; Ebits=int32
+    [N, ceil(F/32)], the residual mask, or None; iters=int32 [F], the last productive iteration of every frame)."""
+    if not isinstance(F, (int, np.integer)) or F <= 0:
+        raise ValueError("F must be a positive int")
+    if not (torch.is_tensor(bits) and bits.is_cuda and torch.is_tensor(erased) and erased.is_cuda and erased.device == bits.device):
+        raise ValueError("bits and erased must be CUDA int32 tensors [N, ceil(F/32)] on one device")
+    dev = bits.device
+    _check_bits(bits, code.N, F, dev)
+    _check_bits(erased, code.N, F, dev)
+    if D is not None:
+        _check_D(D, code.N, F, dev)
+    elif want_D:
+        D = torch.empty((code.N + 1, F), dtype=torch.int32, device=dev)
+    elif not (want_bits or want_erased):
+        raise ValueError("the call must have an output: D, want_D, want_bits or want_erased")
+    Dbits = torch.empty((code.N + 1, _words(F)), dtype=torch.int32, device=dev) if want_bits else None
+    Ebits = torch.empty((code.N, _words(F)), dtype=torch.int32, device=dev) if want_erased else None
+    iters = torch.empty(F, dtype=torch.int32, device=dev)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(dev)).cuda_stream)
+    check(lib.bldpc_decode_erasure(code._h, _dev_ptr(bits), _dev_ptr(erased), int(F), int(max_iter), _dev_ptr(D), _dev_ptr(Dbits), _dev_ptr(Ebits),
+                                   _dev_ptr(iters), st), "LDPC_Decoder_Erasure_GPU")
+    return dict(D=D, Dbits=Dbits, Ebits=Ebits, iters=iters)
+
+
+def erasure_host(H, J, L, Z, bits, erased, F, max_iter=100):
+    """bldpc_decode_erasure_host: the peeling decoder on the host (no device), the statement of its semantics.  bits, erased: uint32
+    [N, ceil(F/32)].  Returns dict(D=int32 [N+1, F], Dbits=uint32 [N+1, ceil(F/32)], Ebits=uint32 [N, ceil(F/32)], iters=int32 [F])."""
+    H = np.ascontiguousarray(H, np.int32)
+    if H.size != J * L:
+        raise ValueError("H must hold J*L shifts")
+    if not isinstance(F, (int, np.integer)) or F <= 0:
+        raise ValueError("F must be a positive int")
+    N = L * Z
+    bits, erased = _check_bits(bits, N, F), _check_bits(erased, N, F)
+    D = np.zeros((N + 1, F), np.int32)
+    Dbits = np.zeros((N + 1, _words(F)), np.uint32)
+    Ebits = np.zeros((N, _words(F)), np.uint32)
+    iters = np.zeros(F, np.int32)
+    check(lib.bldpc_decode_erasure_host(J, L, Z, _np_ptr(H), _np_ptr(bits), _np_ptr(erased), int(F), int(max_iter), _np_ptr(D), _np_ptr(Dbits),
+                                        _np_ptr(Ebits), _np_ptr(iters)), "erasure_host")
+    return dict(D=D, Dbits=Dbits, Ebits=Ebits, iters=iters)
+
+
+def erasure_plan_host(H, J, L, Z):
+    """bldpc_erasure_plan_host: what BinaryCode.erasure_info returns, from the block matrix alone (no device)."""
+    H = np.ascontiguousarray(H, np.int32)
+    if H.size != J * L:
+        raise ValueError("H must hold J*L shifts")
+    d = np.zeros(4, np.int32)
+    check(lib.bldpc_erasure_plan_host(J, L, Z, _np_ptr(H), _np_ptr(d)), "erasure_plan_host")
+    return dict(lds_bytes=int(d[0]), threads=int(d[1]), frames_per_wg=int(d[2]), fits=int(d[0]) <= ERASURE_LDS_BOUND)
+
+
+def Statistic_Bits(code, Dbits, F, counters, Ebits=None, CodeWordBits=None, iters=None, length=0, stream=None):
+    """bldpc_statistic_bits: the five counters of the sweeps (error frames, error bits, iterations, false frames, alarm frames)
+    accumulated into `counters` (CUDA int64, at least 5) from packed words: Dbits int32 [N+1, ceil(F/32)] with row N the flag, Ebits the
+    residual mask [N, ceil(F/32)] or None, CodeWordBits the packed sent words [>= length rows, ceil(F/32)] or None for the all-zero word,
+    iters int32 [F] or None.  A position still erased is a bit error.  length: the rows counted, 0 = code.K."""
+    if not isinstance(F, (int, np.integer)) or F <= 0:
+        raise ValueError("F must be a positive int")
+    if not (torch.is_tensor(Dbits) and Dbits.is_cuda):
+        raise ValueError("Dbits must be a CUDA int32 tensor [N+1, ceil(F/32)]")
+    dev = Dbits.device
+    _check_bits(Dbits, code.N + 1, F, dev)
+    if Ebits is not None:
+        _check_bits(Ebits, code.N, F, dev)
+    if length < 0 or length > code.N:
+        raise ValueError("length must lie in [0, N=%d]" % code.N)
+    rows = length or code.K
+    if CodeWordBits is not None and not (torch.is_tensor(CodeWordBits) and CodeWordBits.dim() == 2 and CodeWordBits.shape[0] >= rows):
+        raise ValueError("CodeWordBits must hold at least %d rows" % rows)
+    if CodeWordBits is not None:
+        _check_bits(CodeWordBits, int(CodeWordBits.shape[0]), F, dev)
+    if iters is not None and not (torch.is_tensor(iters) and iters.is_cuda and iters.dtype == torch.int32 and iters.is_contiguous() and iters.numel() >= F):
+        raise ValueError("iters must be a contiguous CUDA int32 tensor of at least F=%d" % F)
+    _check_counters(counters, 5, dev)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(dev)).cuda_stream)
+    check(lib.bldpc_statistic_bits(code._h, _dev_ptr(Dbits), _dev_ptr(Ebits), _dev_ptr(CodeWordBits), int(F), int(length), _dev_ptr(iters),
+                                   _dev_ptr(counters), st), "Statistic_Bits")
+    return counters
+
+
+def Statistic_Bits_host(N, Dbits, F, length, Ebits=None, CodeWordBits=None, iters=None, counters=None):
+    """bldpc_statistic_bits_host: Statistic_Bits over host arrays, N in place of the code object and a length in [1, N].  Accumulates
+    into `counters` (int64 [5]; None: zeros) and returns it."""
+    Dbits = _check_bits(Dbits, N + 1, F)
+    Ebits = None if Ebits is None else _check_bits(Ebits, N, F)
+    if CodeWordBits is not None:
+        CodeWordBits = np.ascontiguousarray(CodeWordBits)
+        if CodeWordBits.ndim != 2 or CodeWordBits.shape[0] < length:
+            raise ValueError("CodeWordBits must hold at least %d rows" % length)
+        CodeWordBits = _check_bits(CodeWordBits, CodeWordBits.shape[0], F)
+    if iters is not None:
+        iters = np.ascontiguousarray(iters, np.int32)
+        if iters.size < F:
+            raise ValueError("iters must hold F=%d counts" % F)
+    counters = np.zeros(5, np.int64) if counters is None else counters
+    if not (isinstance(counters, np.ndarray) and counters.dtype == np.int64 and counters.size >= 5 and counters.flags.c_contiguous):
+        raise ValueError("counters must be a contiguous int64 array of at least 5")
+    ptr = lambda a: None if a is None else _np_ptr(a)  # noqa: E731
+    check(lib.bldpc_statistic_bits_host(int(N), ptr(Dbits), ptr(Ebits), ptr(CodeWordBits), int(F), int(length), ptr(iters), _np_ptr(counters)),
+          "Statistic_Bits_host")
+    return counters
+
+
 def normalised_host(H, J, L, Z, y, max_iter=50, alpha=1.0, length=0, exit_mode=EXIT_FIXED, want_app=True):
     """bldpc_decode_normalised_host: the flooding decoder with normalised min-sum on the host (no device), the statement of its
     semantics.  y: float32 [N, F] host array (frame-fastest).  Returns dict(D=int32 [N+1, F], app=float32 [N, F] or None,
@@ -1149,6 +1304,55 @@ def RM_Recover_host(rm, rx, short_llr=1.0e4):
     out = np.empty((rm.N, rx.shape[1]), np.float32)
     check(lib.bldpc_rm_recover_host(rm._h, _np_ptr(rx), rx.shape[1], ctypes.c_float(short_llr), _np_ptr(out)), "RM_Recover_host")
     return out
+
+
+def RM_Select_Bits(rm, bits, F, stream=None):
+    """bldpc_rm_select_bits: packed words CUDA int32 [N, ceil(F/32)] -> the transmitted rows [E, ceil(F/32)] (tx[e] = bits[tx_pos[e]]),
+    padding written as 0: Hard_Pack_Int(RM_Select(rm, .)) of the unpacked words, bit for bit."""
+    if not (torch.is_tensor(bits) and bits.is_cuda):
+        raise ValueError("bits must be a CUDA int32 tensor [N=%d, ceil(F/32)]" % rm.N)
+    _check_bits(bits, rm.N, F, bits.device)
+    tx = torch.empty((rm.E, _words(F)), dtype=torch.int32, device=bits.device)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(bits.device)).cuda_stream)
+    check(lib.bldpc_rm_select_bits(rm._h, _dev_ptr(bits), int(F), _dev_ptr(tx), st), "RM_Select_Bits")
+    return tx
+
+
+def RM_Recover_Bits(rm, rx_bits, F, rx_erased=None, stream=None):
+    """bldpc_rm_recover_bits: received packed words [E, ceil(F/32)] and their erasure mask (None: nothing erased) -> (bits, erased) of
+    the mother code, CUDA int32 [N, ceil(F/32)]: shortened positions known 0, punctured and unsent ones erased, a position sent several
+    times takes its first unerased copy."""
+    if not (torch.is_tensor(rx_bits) and rx_bits.is_cuda):
+        raise ValueError("rx_bits must be a CUDA int32 tensor [E=%d, ceil(F/32)]" % rm.E)
+    dev = rx_bits.device
+    _check_bits(rx_bits, rm.E, F, dev)
+    if rx_erased is not None:
+        if not (torch.is_tensor(rx_erased) and rx_erased.is_cuda and rx_erased.device == dev):
+            raise ValueError("rx_erased must be a CUDA int32 tensor [E=%d, ceil(F/32)] on %s" % (rm.E, dev))
+        _check_bits(rx_erased, rm.E, F, dev)
+    bits = torch.empty((rm.N, _words(F)), dtype=torch.int32, device=dev)
+    erased = torch.empty((rm.N, _words(F)), dtype=torch.int32, device=dev)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(dev)).cuda_stream)
+    check(lib.bldpc_rm_recover_bits(rm._h, _dev_ptr(rx_bits), _dev_ptr(rx_erased), int(F), _dev_ptr(bits), _dev_ptr(erased), st), "RM_Recover_Bits")
+    return bits, erased
+
+
+def RM_Select_Bits_host(rm, bits, F):
+    """bldpc_rm_select_bits_host: RM_Select_Bits on a host array uint32 [N, ceil(F/32)], no device needed."""
+    bits = _check_bits(bits, rm.N, F)
+    tx = np.empty((rm.E, _words(F)), np.uint32)
+    check(lib.bldpc_rm_select_bits_host(rm._h, _np_ptr(bits), int(F), _np_ptr(tx)), "RM_Select_Bits_host")
+    return tx
+
+
+def RM_Recover_Bits_host(rm, rx_bits, F, rx_erased=None):
+    """bldpc_rm_recover_bits_host: RM_Recover_Bits on host arrays uint32 [E, ceil(F/32)], no device needed.  Returns (bits, erased)."""
+    rx_bits = _check_bits(rx_bits, rm.E, F)
+    rx_erased = None if rx_erased is None else _check_bits(rx_erased, rm.E, F)
+    bits, erased = np.empty((rm.N, _words(F)), np.uint32), np.empty((rm.N, _words(F)), np.uint32)
+    check(lib.bldpc_rm_recover_bits_host(rm._h, _np_ptr(rx_bits), None if rx_erased is None else _np_ptr(rx_erased), int(F), _np_ptr(bits),
+                                         _np_ptr(erased)), "RM_Recover_Bits_host")
+    return bits, erased
 
 
 def AWGNChannel_RM_CPU(rm, seed, sigma, F, CodeWord=None, short_llr=1.0e4):

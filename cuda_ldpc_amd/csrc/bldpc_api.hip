@@ -41,14 +41,14 @@ struct bldpc_code {
     unsigned ev_n = 0; // decode calls recorded since the last bldpc_kernel_ms_mean
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     EncState *enc = nullptr; // systematic encoder and syndrome tables (bldpc_encode.hip), built on first use
-    // the row-layered decoders (bldpc_layered.hip, bldpc_bp.hip, bldpc_quant.hip) and the bit-flipping decoder (bldpc_bitflip.hip): per
-    // decoder the edge tables, the tier choice and its own scratch, built on first use
-    LayerPlan *lay = nullptr, *bp = nullptr, *quant = nullptr, *bitflip = nullptr;
+    // the row-layered decoders (bldpc_layered.hip, bldpc_bp.hip, bldpc_quant.hip), the bit-flipping decoder (bldpc_bitflip.hip) and the
+    // peeling decoder (bldpc_erasure.hip): per decoder the edge tables, the tier choice and its own scratch, built on first use
+    LayerPlan *lay = nullptr, *bp = nullptr, *quant = nullptr, *bitflip = nullptr, *erasure = nullptr;
 };
 
 LayerView cldpc::layer_view(bldpc_code *c, LayerSlot slot)
 {
-    LayerPlan **plan = slot == kSlotMinSum ? &c->lay : slot == kSlotBp ? &c->bp : slot == kSlotQuant ? &c->quant : &c->bitflip;
+    LayerPlan **plan = slot == kSlotMinSum ? &c->lay : slot == kSlotBp ? &c->bp : slot == kSlotQuant ? &c->quant : slot == kSlotBitflip ? &c->bitflip : &c->erasure;
     return LayerView{c->J, c->L, c->Z, c->N, c->M, c->K, c->has_qc ? c->H.data() : nullptr, plan, &c->last_kernel};
 }
 
@@ -234,6 +234,7 @@ extern "C" int bldpc_code_destroy(bldpc_code *c)
     delete c->bp;
     delete c->quant;
     delete c->bitflip;
+    delete c->erasure;
     for (hipEvent_t e : c->evr)
         if (e) (void)hipEventDestroy(e);
     delete c;

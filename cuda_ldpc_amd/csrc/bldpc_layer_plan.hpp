@@ -12,7 +12,7 @@ struct bldpc_code;
 
 namespace cldpc {
 
-enum LayerSlot { kSlotMinSum, kSlotBp, kSlotQuant, kSlotBitflip }; // the code object keeps one plan per layered decoder, and one for bit flipping
+enum LayerSlot { kSlotMinSum, kSlotBp, kSlotQuant, kSlotBitflip, kSlotErasure }; // the code object keeps one plan per layered decoder, one for bit flipping, one for peeling
 
 struct LayerPlan {
     bool built = false;

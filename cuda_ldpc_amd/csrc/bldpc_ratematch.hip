@@ -10,6 +10,9 @@
 // combining movements add a transmission into an accumulator [N][F] under a per-frame done mask.  They have kernels of their own
 // (k_rm_circ, k_rm_awgn_circ); a profile from bldpc_rm_create keeps k_rm_recover and k_rm_awgn in the entry points it had.  Frame
 // compaction (bldpc_frames_gather / _scatter) moves the columns of the unacknowledged frames.
+//
+// Packed words (include/bldpc.h, "erasure decoding"): select and recover once more on [rows][ceil(F/32)] arrays of 32 frames a word
+// (k_rm_select_bits, k_rm_recover_bits), the word index along threadIdx.x; an unsent position is an erasure there, not a +0.0f.
 #include "../../include/bldpc.h"
 
 #include <algorithm>
@@ -191,6 +194,48 @@ __global__ __launch_bounds__(256) void k_frames(const unsigned *__restrict__ src
     for (int r = r0; r < min(rows, r0 + kRows); r++) {
         if (SCATTER) dst[(size_t)r * F + i] = src[(size_t)r * Fa + a];
         else dst[(size_t)r * Fa + a] = src[(size_t)r * F + i];
+    }
+}
+
+// Rate matching on packed words (include/bldpc.h, "erasure decoding"): [rows][W] arrays of 32 frames per word, the word index along
+// threadIdx.x, kRows rows per thread.  `last` masks the padding of word W - 1.
+__device__ __forceinline__ unsigned rm_valid(int w, int W, unsigned last) { return w == W - 1 ? last : ~0u; }
+
+__global__ __launch_bounds__(256) void k_rm_select_bits(const int *__restrict__ tx_pos, const unsigned *__restrict__ bits, int E, int W, unsigned last,
+                                                        unsigned *__restrict__ tx)
+{
+    const int w = blockIdx.x * 256 + threadIdx.x;
+    const int e0 = blockIdx.y * kRows;
+    if (w >= W) return;
+    const unsigned valid = rm_valid(w, W, last);
+    for (int e = e0; e < min(E, e0 + kRows); e++) tx[(size_t)e * W + w] = bits[(size_t)tx_pos[e] * W + w] & valid;
+}
+
+// Output-driven, one owner per (n, w) as k_rm_circ: the copies of position n are walked in transmission order, e0, e0 + Ncb, ..., and a
+// frame takes the value of its first unerased copy.  rx_erased == nullptr: nothing was erased.
+__global__ __launch_bounds__(256) void k_rm_recover_bits(const int *__restrict__ map, const unsigned *__restrict__ rx, const unsigned *__restrict__ rxe,
+                                                         int N, int Ncb, int k0, int E, int W, unsigned last, unsigned *__restrict__ bits,
+                                                         unsigned *__restrict__ erased)
+{
+    const int w = blockIdx.x * 256 + threadIdx.x;
+    const int n0 = blockIdx.y * kRows;
+    if (w >= W) return;
+    const unsigned valid = rm_valid(w, W, last);
+    for (int n = n0; n < min(N, n0 + kRows); n++) {
+        const int b = map[n]; // uniform over the workgroup
+        unsigned known = 0, val = 0;
+        if (b == kRmShort) known = ~0u;
+        else if (b >= 0) {
+            int e = b - k0;
+            if (e < 0) e += Ncb;
+            for (; e < E; e += Ncb) {
+                const unsigned ok = rxe ? ~rxe[(size_t)e * W + w] : ~0u;
+                val |= rx[(size_t)e * W + w] & ok & ~known;
+                known |= ok;
+            }
+        }
+        bits[(size_t)n * W + w] = val & known & valid;
+        erased[(size_t)n * W + w] = ~known & valid;
     }
 }
 
@@ -628,4 +673,78 @@ extern "C" int bldpc_rm_encode_random(bldpc_code *code, const bldpc_rm *rm, unsi
     if (N != rm->N) return fail(BLDPC_EINVAL, "bldpc_rm_encode_random: the profile is over N=%d positions, the code has N=%d", rm->N, N);
     if ((r = device_tables(rm))) return r;
     return encode_random_shortened(code, rm->d_map, rm->short_pos.data(), rm->n_short, seed, first_frame, F, msg, cw, stream);
+}
+
+// ---------------------------------------------------------------------------------------------- packed words: select, recover
+namespace {
+
+int words_of(int F) { return (F + 31) / 32; }
+unsigned last_mask(int F) { return F % 32 ? (1u << (F % 32)) - 1u : ~0u; }
+
+} // namespace
+
+extern "C" int bldpc_rm_select_bits_host(const bldpc_rm *rm, const unsigned *bits, int F, unsigned *tx)
+{
+    int r = check_rm(rm, F, "bldpc_rm_select_bits_host");
+    if (r) return r;
+    if (!bits || !tx) return fail(BLDPC_EINVAL, "bldpc_rm_select_bits_host: null argument");
+    const int W = words_of(F);
+    for (int e = 0; e < rm->E; e++)
+        for (int w = 0; w < W; w++) tx[(size_t)e * W + w] = bits[(size_t)rm->tx_pos[e] * W + w] & (w == W - 1 ? last_mask(F) : ~0u);
+    return BLDPC_OK;
+}
+
+// Position by position and frame by frame: the copies of a position in transmission order, the first unerased one gives the value.
+extern "C" int bldpc_rm_recover_bits_host(const bldpc_rm *rm, const unsigned *rx_bits, const unsigned *rx_erased, int F, unsigned *bits,
+                                          unsigned *erased)
+{
+    int r = check_rm(rm, F, "bldpc_rm_recover_bits_host");
+    if (r) return r;
+    if (!rx_bits || !bits || !erased) return fail(BLDPC_EINVAL, "bldpc_rm_recover_bits_host: null argument");
+    const int W = words_of(F);
+    std::fill_n(bits, (size_t)rm->N * W, 0u);
+    std::fill_n(erased, (size_t)rm->N * W, 0u);
+    for (int n = 0; n < rm->N; n++) {
+        const int b = rm->map[n];
+        if (b == kRmShort) continue; // known 0
+        const int e0 = b < 0 ? rm->E : (b - rm->k0 + rm->Ncb) % rm->Ncb;
+        for (int f = 0; f < F; f++) {
+            const size_t at = (size_t)n * W + f / 32;
+            bool known = false;
+            for (int e = e0; e < rm->E && !known; e += rm->Ncb) {
+                const size_t from = (size_t)e * W + f / 32;
+                if (rx_erased && ((rx_erased[from] >> (f & 31)) & 1u)) continue;
+                known = true;
+                bits[at] |= ((rx_bits[from] >> (f & 31)) & 1u) << (f & 31);
+            }
+            if (!known) erased[at] |= 1u << (f & 31);
+        }
+    }
+    return BLDPC_OK;
+}
+
+extern "C" int bldpc_rm_select_bits(const bldpc_rm *rm, const unsigned *bits, int F, unsigned *tx, void *stream)
+{
+    int r = check_rm(rm, F, "bldpc_rm_select_bits");
+    if (r) return r;
+    if (!bits || !tx) return fail(BLDPC_EINVAL, "bldpc_rm_select_bits: null argument");
+    if ((r = device_tables(rm))) return r;
+    const int W = words_of(F);
+    hipLaunchKernelGGL(k_rm_select_bits, grid_of(W, rm->E), dim3(256), 0, (hipStream_t)stream, rm->d_tx, bits, rm->E, W, last_mask(F), tx);
+    CLDPC_HIP(hipGetLastError(), BLDPC_EHIP);
+    return BLDPC_OK;
+}
+
+extern "C" int bldpc_rm_recover_bits(const bldpc_rm *rm, const unsigned *rx_bits, const unsigned *rx_erased, int F, unsigned *bits, unsigned *erased,
+                                     void *stream)
+{
+    int r = check_rm(rm, F, "bldpc_rm_recover_bits");
+    if (r) return r;
+    if (!rx_bits || !bits || !erased) return fail(BLDPC_EINVAL, "bldpc_rm_recover_bits: null argument");
+    if ((r = device_tables(rm))) return r;
+    const int W = words_of(F);
+    hipLaunchKernelGGL(k_rm_recover_bits, grid_of(W, rm->N), dim3(256), 0, (hipStream_t)stream, rm->d_map, rx_bits, rx_erased, rm->N, rm->Ncb, rm->k0,
+                       rm->E, W, last_mask(F), bits, erased);
+    CLDPC_HIP(hipGetLastError(), BLDPC_EHIP);
+    return BLDPC_OK;
 }

@@ -37,6 +37,10 @@ def bsc_draws_per_frame(N):
     return N       # the binary symmetric channel: one draw per bit (bldpc_bsc_channel_device)
 
 
+def bec_draws_per_frame(N):
+    return N       # the binary erasure channel: one draw per transmitted bit, N or a profile's E (bldpc_bec_channel_device)
+
+
 def nb_draws_per_frame(N, m):
     return 4 * N * m  # Real and Image part, two draws each (LDPC_Encoder.cpp:57-66)
 

@@ -14,6 +14,7 @@ import torch
 from . import sharding
 from ._lib import check, lib
 from .bldpc import (BF_GRADIENT, BF_THRESHOLD, BSCChannel_GPU, Hard_Pack, LDPC_Decoder_BitFlip_GPU,
+                    BECChannel_GPU, Hard_Pack_Int, LDPC_Decoder_Erasure_GPU, RM_Recover_Bits, RM_Select_Bits, Statistic_Bits,
                     EXIT_BATCH_GLOBAL, EXIT_FIXED, EXIT_PER_FRAME, KERNEL_AUTO, STOP_PREFIX, STOP_SYNDROME, AWGNChannel_CPU, AWGNChannel_Fading_GPU,
                     AWGNChannel_GPU, AWGNChannel_QAM_Fading_GPU, AWGNChannel_QAM_GPU, AWGNChannel_RM_Combine_GPU, AWGNChannel_RM_GPU,
                     Decode_Statistic, Demodulate_QAM, Demodulate_QAM_Fading, Fading, Fading_Gains, Frames_Gather, Frames_Scatter, IL_NONE, IL_ROWCOL,
@@ -358,6 +359,85 @@ def sweep_bsc(code, ps, seeds=(173, 173, 173), dist=None, log=print, **kw):
         SIM = SimCounters()
         SIM.SNR = float(p)
         Simulation_BSC_GPU(code, np.array(seeds, np.int32), float(p), SIM, dist=dist, log=log, **kw)
+        out.append(SIM)
+    return out
+
+
+def Simulation_BEC_GPU(code, seed, p, SIM, Num_Frames_OneTime=4096, maxIT=100, PN_Message=0, pn_seed=0, rate_match=None, max_batches=None,
+                       leastErrorFrames=50, leastTestFrames=10000, displayStep=40960, dist=None, device=None, log=print):
+    """One point of an erasure sweep: the binary erasure channel with erasure probability p, then peeling, all on packed words.  A batch
+    is PN_CodeWords (PN_Message=1; the all-zero word otherwise) -> Hard_Pack_Int, and RM_Select_Bits under a profile -> BECChannel_GPU on
+    the N, or the profile's E, transmitted rows -> RM_Recover_Bits under a profile (punctured positions erased, shortened ones known 0)
+    -> LDPC_Decoder_Erasure_GPU with Dbits and Ebits only -> Statistic_Bits, where a position still erased is a bit error.  No int32 D
+    is made.  `seed` (int32[3]) is the RandomModule state, advanced in place by the WHOLE batch on every rank, one draw per transmitted
+    bit (sharding.bec_draws_per_frame); the batch loop, its stop rule and the sharding over ranks are those of Simulation_BSC_GPU.
+    rate_match takes linear and circular profiles; under one the bit error rate divides by the prefix bits that are not shortened, as in
+    Simulation_GPU.  SIM.SNR is printed as it is: the caller may keep p there."""
+    if PN_Message not in (0, 1):
+        raise ValueError("PN_Message must be 0 (all-zero codeword) or 1 (random codewords)")
+    if not (np.isfinite(p) and 0.0 <= p <= 1.0):
+        raise ValueError("p must be an erasure probability in [0, 1], not %r" % (p,))
+    if maxIT < 1:
+        raise ValueError("maxIT must be at least 1")
+    rm = rate_match
+    if rm is not None:
+        if rm.N != code.N:
+            raise ValueError("rate_match is over N=%d positions, the code has N=%d" % (rm.N, code.N))
+        if PN_Message and rm.n_short and not np.isin(rm.shorten, code.info_positions).all():
+            raise ValueError("rate_match shortens a parity position of the code's generator; only information positions (code.info_positions) "
+                             "can be agreed to be 0")
+    rank = dist.get_rank() if dist is not None and dist.is_initialized() else 0
+    world = dist.get_world_size() if dist is not None and dist.is_initialized() else 1
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    F = Num_Frames_OneTime
+    first, count = sharding.shard_frames(F, world, rank)
+    n_tx = rm.E if rm is not None else code.N  # bits per frame that go over the channel
+    per_frame = sharding.bec_draws_per_frame(n_tx)
+    dev_cnt = torch.zeros(5, dtype=torch.int64, device=device)
+    length = code.K
+    ber_bits = length - (int((rm.shorten < length).sum()) if rm is not None else 0)  # the prefix bits that carry information
+    batches = 0
+    while True:
+        SIM.num_Frames += F
+        my_seed = sharding.lcg_jump(seed, first * per_frame)
+        seed[:] = sharding.lcg_jump(seed, F * per_frame)
+        dev_cnt.zero_()
+        if count:
+            cwbits = None
+            if PN_Message:
+                cwbits = Hard_Pack_Int(PN_CodeWords(code, pn_seed, count, first_frame=batches * F + first, device=device, rate_match=rm))
+            tx = RM_Select_Bits(rm, cwbits, count) if (rm is not None and cwbits is not None) else cwbits
+            bits, erased = BECChannel_GPU(my_seed, p, n_tx, count, device=device)  # the mask; the channel's words are those of the all-zero word
+            if tx is not None:
+                bits = tx & ~erased
+            if rm is not None:
+                bits, erased = RM_Recover_Bits(rm, bits, count, rx_erased=erased)
+            r = LDPC_Decoder_Erasure_GPU(code, bits, erased, count, max_iter=maxIT)
+            Statistic_Bits(code, r["Dbits"], count, dev_cnt, Ebits=r["Ebits"], CodeWordBits=cwbits, iters=r["iters"], length=length)
+        sharding.allreduce_counters(dev_cnt, dist)
+        c = dev_cnt.cpu().tolist()
+        SIM.num_Error_Frames += c[0]
+        SIM.num_Error_Bits += c[1]
+        SIM.Total_Iteration += c[2]
+        SIM.num_False_Frames += c[3]
+        SIM.num_Alarm_Frames += c[4]
+        batches += 1
+        stop = SIM.num_Error_Frames >= leastErrorFrames and SIM.num_Frames >= leastTestFrames
+        last = max_batches is not None and batches >= max_batches
+        if rank == 0 and log and (SIM.num_Frames % displayStep == 0 or stop or last):
+            log(" %.4g" % SIM.SNR + format_row(SIM, ber_bits)[len(" %.1f" % SIM.SNR):])  # the row's first column with the digits of a probability
+        if stop or last:
+            return 1 if stop else 0
+
+
+def sweep_bec(code, ps, seeds=(173, 173, 173), dist=None, log=print, **kw):
+    """Simulation_BEC_GPU at every erasure probability of `ps`, seed and counters reset at every point as in `sweep`: a list of
+    SimCounters whose SNR field holds p."""
+    out = []
+    for p in ps:
+        SIM = SimCounters()
+        SIM.SNR = float(p)
+        Simulation_BEC_GPU(code, np.array(seeds, np.int32), float(p), SIM, dist=dist, log=log, **kw)
         out.append(SIM)
     return out
 

@@ -787,6 +787,70 @@ int bldpc_decode_bitflip_host(int J, int L, int Z, const int *H, const unsigned 
 int bldpc_bitflip_info(bldpc_code *code, int info[4]);
 int bldpc_bitflip_plan_host(int J, int L, int Z, const int *H, int info[4]);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * Erasure decoding: a third value on the packed rung, a binary erasure channel, a parallel peeling decoder, rate matching and
+ * statistics on packed words.
+ *
+ * Erased words.  Two packed arrays of the layout above: `bits` uint32 [rows][W] and `erased` of the same shape, 1 = erased.  The value
+ * bit at an erased position carries no meaning: every producer below writes it as 0, every consumer ignores it.  Padding bits of both
+ * arrays are written as 0 and ignored on input.
+ *
+ * Binary erasure channel.  erased[n][f] = (u < p), u the draw f * N + n of the RandomModule stream `seed`: the BSC's indexing, one draw
+ * per bit, the same float compare, so with equal seed and p the mask is the BSC's flip mask.  bits = CodeWord & ~erased (NULL: the
+ * all-zero word).  seed is advanced by N * F draws.  BLDPC_EINVAL: p not finite or outside [0, 1], a seed state outside [0, modulus).
+ *
+ * Peeling.  Per frame, rows and their variables as in bldpc_decode_bitflip: x = bits_in & ~erased_in, er = erased_in.  Iteration
+ * k = 1 .. max_iter decides everything from the state at its start and applies it together:
+ *   1. for every check row c: n_c = the number of erased variables of c, a_c = the XOR of x_v over the known variables of c;
+ *   2. an erased variable v is resolved iff at least one of its checks has n_c == 1; it becomes known with x_v = the OR of a_c over
+ *      those checks (on a consistent word they agree; the OR defines the result when the known bits are not from a codeword);
+ *   3. the iteration is productive for the frame iff it resolved at least one variable.  Once an iteration is unproductive every
+ *      later one is too, and an implementation may stop there.
+ *   Dbits  uint32 [N+1][W]: rows 0 .. N-1 hold x, with 0 at positions still erased; row N is the flag "no erasure left and every check
+ *          sum of x zero"; or NULL
+ *   Ebits  uint32 [N][W], the residual mask, or NULL
+ *   D      int32 [N+1][F], the unpacked Dbits (what bldpc_statistic and bldpc_syndrome take), or NULL
+ *   iters  int32 [F] or NULL: the index of the last productive iteration of frame f, 0 when there was none (a frame without erasures,
+ *          a frame that is stuck from the start)
+ * There is no exit mode: peeling is idempotent after it stalls, so a fixed count and a per-frame exit return the same words.
+ * BLDPC_EINVAL: a null input, F <= 0, max_iter < 1, all of D, Dbits and Ebits null.  BLDPC_EUNSUPPORTED (kept with the code object, the
+ * same text at every call): a code built from an address table; a code whose 32-frame state, 4 (2 N + M) bytes, exceeds the LDS a
+ * workgroup may use (there is no workspace tier).  Block rows of weight 1 and block columns of weight 0, 1 and 16 are taken.  The device
+ * call is asynchronous on `stream` and allocates nothing once its scratch has grown; the _host form is the definition (plain C++, one
+ * frame at a time, at most 16 threads).
+ *
+ * bldpc_erasure_info / bldpc_erasure_plan_host: info[4] = LDS bytes of a workgroup of k_er, threads, frames per workgroup (32), 0; the
+ * first for a code object without a launch, the second without a device.  A code fits when info[0] <= 162816.
+ *
+ * Rate matching on packed words, for linear and circular profiles.  bldpc_rm_select_bits: tx[e] = bits[tx_pos[e]], [N][W] -> [E][W]
+ * (bit for bit bldpc_hard_pack_int of bldpc_rm_select of the unpacked words).  bldpc_rm_recover_bits, [E][W] -> [N][W]: a shortened
+ * position is known 0 (erased 0, bits 0); a punctured or otherwise unsent position is erased (erased 1, bits 0); a position sent once
+ * or several times (the laps of a circular buffer) is known iff any copy arrived unerased, with the value of the first unerased copy in
+ * transmission order.  rx_erased == NULL: nothing was erased.
+ *
+ * Statistics on packed words.  bldpc_statistic_bits accumulates the five counters of bldpc_statistic_per_frame, with the values that
+ * call gives on the unpacked D had every position still erased been replaced by the complement of the sent bit: an unresolved bit is
+ * a bit error.  Row N of Dbits is the flag.  Ebits == NULL: none erased; CodeWordBits == NULL: the all-zero word; iters == NULL: nothing
+ * is added to Total_Iteration; length == 0: the code's K, as bldpc_statistic.  The _host form takes N in place of the code object and a
+ * length in [1, N]. */
+int bldpc_bec_channel_device(int seed[3], float p, const int *CodeWord, int N, int F, unsigned *bits, unsigned *erased, void *stream);
+int bldpc_bec_channel_host(int seed[3], float p, const int *CodeWord, int N, int F, unsigned *bits, unsigned *erased);
+int bldpc_decode_erasure(bldpc_code *code, const unsigned *bits_in, const unsigned *erased_in, int F, int max_iter, int *D, unsigned *Dbits,
+                         unsigned *Ebits, int *iters, void *stream);
+int bldpc_decode_erasure_host(int J, int L, int Z, const int *H, const unsigned *bits_in, const unsigned *erased_in, int F, int max_iter, int *D,
+                              unsigned *Dbits, unsigned *Ebits, int *iters);
+int bldpc_erasure_info(bldpc_code *code, int info[4]);
+int bldpc_erasure_plan_host(int J, int L, int Z, const int *H, int info[4]);
+int bldpc_rm_select_bits(const bldpc_rm *rm, const unsigned *bits, int F, unsigned *tx, void *stream);
+int bldpc_rm_recover_bits(const bldpc_rm *rm, const unsigned *rx_bits, const unsigned *rx_erased, int F, unsigned *bits, unsigned *erased,
+                          void *stream);
+int bldpc_rm_select_bits_host(const bldpc_rm *rm, const unsigned *bits, int F, unsigned *tx);
+int bldpc_rm_recover_bits_host(const bldpc_rm *rm, const unsigned *rx_bits, const unsigned *rx_erased, int F, unsigned *bits, unsigned *erased);
+int bldpc_statistic_bits(const bldpc_code *code, const unsigned *Dbits, const unsigned *Ebits, const unsigned *CodeWordBits, int F, int length,
+                         const int *iters, long long *counters, void *stream);
+int bldpc_statistic_bits_host(int N, const unsigned *Dbits, const unsigned *Ebits, const unsigned *CodeWordBits, int F, int length,
+                              const int *iters, long long *counters);
+
 const char *bldpc_last_error(void);
 
 #ifdef __cplusplus

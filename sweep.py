@@ -9,6 +9,7 @@
     python sweep.py binary --device-channel --quant 6,8,6 --norm8 6 --llr-scale 16 --per-frame --stop-rule syndrome --pn-message --start 2 --stop 3 --step 0.2
     python sweep.py binary --hard gradient --per-frame --pn-message --bsc 0.002,0.004,0.006
     python sweep.py binary --hard threshold --device-channel --per-frame --start 4 --stop 6 --step 0.5
+    python sweep.py binary --erasure --bec 0.08,0.10,0.12,0.14 --pn-message --puncture 2208:2304 --iters 100
     python sweep.py binary --device-channel --per-frame --layered --pn-message --qam 64 --interleave rowcol --fading 16 --harq 0:2160,2160:48,500:2300
     python sweep.py nb --pn-message --qam 64 --fading 16
     python sweep.py nb --device-channel --pn-message --puncture 88:96
@@ -99,6 +100,11 @@ def main():
                     "variables of largest u + e; with --device-channel and --fixed or --per-frame; no --alpha, --stop-rule, --shorten / --puncture, --harq")
     ap.add_argument("--bsc", metavar="P[,P...]", default=None, help="--hard: crossover probabilities of a binary symmetric channel in place of the "
                     "SNR list (Simulation_BSC_GPU; the first column of a row is P)")
+    ap.add_argument("--erasure", action="store_true", help="binary: erasure decoding by parallel peeling (bldpc_decode_erasure) on packed words over "
+                    "a binary erasure channel, with --bec; takes --pn-message, --shorten / --puncture (punctured = erased, shortened = known 0) and "
+                    "--iters; no --hard, --layered, --bp, --quant, --qam, --fading, --harq")
+    ap.add_argument("--bec", metavar="P[,P...]", default=None, help="--erasure: erasure probabilities of the binary erasure channel in place of the "
+                    "SNR list (Simulation_BEC_GPU; the first column of a row is P)")
     ap.add_argument("--alpha", type=float, default=1.0, help="binary: normalisation factor in (0, 1]; with --layered the layered decoder's, without it "
                     "normalised min-sum on the flooding decoders (with --fixed or --per-frame)")
     ap.add_argument("--stop-rule", choices=["prefix", "syndrome"], default=None,
@@ -176,6 +182,20 @@ def main():
             ap.error("--hard without --bsc needs --device-channel")
     elif args.bsc is not None:
         ap.error("--bsc belongs to --hard")
+    bec = None
+    if args.erasure:
+        if (args.which != "binary" or args.hard is not None or args.layered or args.bp or quant is not None or args.qam != 2 or fade is not None
+                or args.harq is not None or args.alpha != 1.0 or args.stop_rule is not None or args.as_written or args.fixed or args.per_frame):
+            ap.error("--erasure belongs to the binary sweep on a QC code, without --hard, --layered, --bp, --quant, --qam, --fading, --harq, --alpha "
+                     "and --stop-rule; peeling has no exit mode, so no --fixed / --per-frame either")
+        try:
+            bec = [float(x) for x in (args.bec or "").split(",")]
+        except ValueError:
+            ap.error("--erasure needs --bec P[,P...], erasure probabilities")
+        if not all(0.0 <= x <= 1.0 for x in bec):
+            ap.error("--bec takes probabilities in [0, 1]")
+    elif args.bec is not None:
+        ap.error("--bec belongs to --erasure")
     rows = args.layered or args.bp or quant is not None  # the row-layered decoders take the same modes and rules
     if args.which == "binary" and rows:
         if args.as_written or not (args.fixed or args.per_frame):
@@ -186,14 +206,14 @@ def main():
         ap.error("--stop-rule belongs to the binary sweep with --layered, --bp or --quant, --alpha to the binary sweep")
     elif args.alpha != 1.0 and not (args.fixed or args.per_frame):
         ap.error("--alpha without --layered (normalised flooding min-sum) needs --fixed or --per-frame")
-    if args.which == "binary" and not rows and args.hard is None and args.pn_message and (not args.fixed or args.as_written):
+    if args.which == "binary" and not rows and args.hard is None and not args.erasure and args.pn_message and (not args.fixed or args.as_written):
         ap.error("--pn-message needs the binary sweep with --fixed (the decoders' early exit tests for the all-zero word) on a QC code")
     if args.which == "binary" and args.qam != 2 and not (args.pn_message and args.device_channel):
         ap.error("binary --qam %d needs --pn-message (a QAM channel is not symmetric: the all-zero word is not representative) and "
                  "--device-channel (there is no host QAM channel on this path)" % args.qam)
     ratematch = args.shorten is not None or args.puncture is not None or args.harq is not None
     if ratematch:
-        if not args.device_channel:
+        if not args.device_channel and not args.erasure:
             ap.error("--shorten / --puncture / --harq need --device-channel")
         try:  # binary: bit positions; nb: symbol positions, checked against N once the matrix header is read
             rm_N = args.L * args.Z if args.which == "binary" else None
@@ -270,6 +290,20 @@ def main():
             sweep_bsc(code, bsc, dist=dist, rule=lay["hard_rule"], Num_Frames_OneTime=args.batch, maxIT=args.iters or 30,
                       exit_mode=C.EXIT_FIXED if args.fixed else C.EXIT_PER_FRAME, max_batches=args.max_batches, displayStep=10 ** 12,
                       PN_Message=1 if args.pn_message else 0, pn_seed=args.pn_seed, log=print if rank == 0 else None)
+            if world > 1:
+                dist.destroy_process_group()
+            return
+        if bec is not None:
+            from cuda_ldpc_amd.simulation import sweep_bec
+            rm = C.RateMatch(code.N, shorten, puncture) if ratematch else None
+            if rank == 0:
+                print("# %s N=%d K=%d, binary erasure channel, peeling, maxIT=%d, batch=%d x %d GPU(s)%s%s" % (
+                    os.path.basename(args.matrix), code.N, code.K, args.iters or 100, args.batch, world,
+                    ", %d shortened, %d punctured, E=%d" % (rm.n_short, rm.n_punct, rm.E) if rm is not None else "",
+                    ", random codewords (PN seed %d)" % args.pn_seed if args.pn_message else ""))
+                print("#   P      NTF   NEF         FER         BER  AverIT       FER_F      FER_A")
+            sweep_bec(code, bec, dist=dist, Num_Frames_OneTime=args.batch, maxIT=args.iters or 100, max_batches=args.max_batches, displayStep=10 ** 12,
+                      PN_Message=1 if args.pn_message else 0, pn_seed=args.pn_seed, rate_match=rm, log=print if rank == 0 else None)
             if world > 1:
                 dist.destroy_process_group()
             return
