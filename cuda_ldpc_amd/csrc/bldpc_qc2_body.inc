@@ -139,7 +139,7 @@ template <typename GM, bool HIST, bool NORM = false> __global__ __launch_bounds_
     // LOC: the same sum with the own block row's R from the register that holds it (slot jj), S kept for the check-node phase
     v2f32 Sloc[LOC ? CPT : 1];
     const int jqs = __builtin_amdgcn_readfirstlane(jq);
-    auto vn_phase_loc = [&](auto JJ, auto ZS, bool (&bad)[NF]) {
+    auto vn_phase_loc = [&](auto JJ, auto ZS, bool (&bad)[NF], auto &&pre_wait) {
         constexpr int jj = decltype(JJ)::value;
         constexpr bool zs = decltype(ZS)::value;
         v2f32 R[CPT][WV - 1];
@@ -167,11 +167,12 @@ template <typename GM, bool HIST, bool NORM = false> __global__ __launch_bounds_
                 bad[1] = bad[1] || (in_len && S.y < 0);
             }
         });
+        pre_wait();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     };
     // The first variable-node phase: every R is +0 (Memory_RQ = 0, LDPC_Decoder.cu:82), so the reference's sum ((0+R_0)+...+R_{w-1})+y
     // is (+0) + y = y + 0.0f bit for bit (y = -0.0f included): no R is read, none had to be zeroed in LDS.
-    auto vn_first = [&](bool (&bad)[NF]) {
+    auto vn_first = [&](bool (&bad)[NF], auto &&pre_wait) {
         static_for<CPT>([&](auto CC) {
             constexpr int cc = decltype(CC)::value;
             const v2f32 S = yreg[cc] + v2f32{0.0f, 0.0f};
@@ -190,10 +191,12 @@ template <typename GM, bool HIST, bool NORM = false> __global__ __launch_bounds_
                 bad[1] = bad[1] || (in_len && S.y < 0);
             }
         });
+        pre_wait();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     };
+    auto no_early = []() {};
     auto vn_any = [&](bool (&bad)[NF]) {
-        if constexpr (LOC) static_for<GM::J>([&](auto JJ) { if (jqs == decltype(JJ)::value) vn_phase_loc(JJ, std::true_type{}, bad); });
+        if constexpr (LOC) static_for<GM::J>([&](auto JJ) { if (jqs == decltype(JJ)::value) vn_phase_loc(JJ, std::true_type{}, bad, no_early); });
         else vn_phase(std::true_type{}, bad);
     };
     auto flags_publish = [&](const bool (&bad)[NF], int it) { // two sets of flag words by iteration parity, see k_qc
@@ -267,6 +270,23 @@ template <typename GM, bool HIST, bool NORM = false> __global__ __launch_bounds_
     done = 0;
     __syncthreads();
 #endif
+    // Scheduling of the local edges (DESIGN 4.1).  The first triple of a half-row's selection network is its local edges (NL >= 3): their
+    // Q = Sloc - R, the triple's lo / mid and the XOR of its sign words need no LDS access.  cn_local computes them between the last S
+    // store of the variable-node phase and its drain wait, where the wave would stand idle, instead of behind the S reads of the
+    // check-node phase: 14.62 -> 15.00 M codewords/s (the same work between the issue of the S reads and their first wait: 14.68;
+    // profiles/r08_qc2_local_sched_ab.txt).  Q replaces R_p in Rr[0][0 .. NL-1] here already.  Only an iteration does this: the final
+    // variable-node phase (vn_any) needs R_p as the last check-node phase left it.  Where retire leaves between the barrier and the
+    // check-node phase the early values are unused: the pair is done, and the next pair's first iteration overwrites them.
+    constexpr int NE = (NL >= 3 && WCH >= 4) ? 3 : 0; // edges handled ahead: the first triple
+    float elo[NF], emid[NF];
+    uint32_t esg[NF];
+    auto cn_local = [&](auto FIRST) {
+        constexpr bool first = decltype(FIRST)::value;
+#pragma unroll
+        for (int i = 0; i < NL; i++) Rr[0][i] = first ? Sloc[LOC ? i : 0] : Sloc[LOC ? i : 0] - Rr[0][i];
+#pragma unroll
+        for (int v = 0; v < NF; v++) cn_lead_triple<2>(reinterpret_cast<const float *>(&Rr[0][0]) + v, elo[v], emid[v], esg[v]);
+    };
     // Iteration it (1 ... max_iter-1): variable-node phase, barrier, check-node phase, barrier.  FIRST (it = 1): every R is +0, the
     // variable-node phase is vn_first and the check-node phase's Q = S - R is Q = S (S - (+0) == S for every S, -0.0f included).
     // True when the per-frame exit has retired every frame of the pair.
@@ -276,8 +296,14 @@ template <typename GM, bool HIST, bool NORM = false> __global__ __launch_bounds_
 #pragma unroll
         for (int v = 0; v < NF; v++) bad[v] = false;
         __builtin_amdgcn_s_setprio(QC_PRIO_VN);
-        if constexpr (first) vn_first(bad);
-        else if constexpr (LOC) vn_phase_loc(JJ, std::bool_constant<HIST>{}, bad); // the loop's sums: from 0 only where emit may read them
+        auto early = [&]() { // between the phase's last S store and its drain wait
+            if constexpr (NE > 0) {
+                cn_local(FIRST);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        };
+        if constexpr (first) vn_first(bad, early);
+        else if constexpr (LOC) vn_phase_loc(JJ, std::bool_constant<HIST>{}, bad, early); // the loop's sums: from 0 only where emit may read them
         else vn_phase(std::bool_constant<HIST>{}, bad);
         if (HIST) flags_publish(bad, it);
         __syncthreads();
@@ -311,11 +337,13 @@ template <typename GM, bool HIST, bool NORM = false> __global__ __launch_bounds_
                         else Sv[i] = lds_ld2(saddr[rr][c0 + i]);
                     }
 #pragma unroll
-                    for (int i = 0; i < CHK && c0 + i < WCH; i++) Rr[rr][c0 + i] = first ? Sv[i] : Sv[i] - Rr[rr][c0 + i]; // Q = S - R  (LDPC_Decoder.cu:206-209), in place of R_p
+                    for (int i = 0; i < CHK && c0 + i < WCH; i++)
+                        if (!(NE > 0 && c0 + i < NL)) Rr[rr][c0 + i] = first ? Sv[i] : Sv[i] - Rr[rr][c0 + i]; // Q = S - R  (LDPC_Decoder.cu:206-209), in place of R_p
                     if (c0 + CHK < WCH) __builtin_amdgcn_sched_barrier(0);
                 }
             }
 #if QC_ACC_RUNNING
+            static_assert(NE == 0, "the running accumulator takes every edge");
 #pragma unroll
             for (int v = 0; v < NF; v++) acc[v].init();
 #pragma unroll
@@ -324,8 +352,14 @@ template <typename GM, bool HIST, bool NORM = false> __global__ __launch_bounds_
                 acc[1].add(Rr[rr][i].y);
             }
 #else
-            cn_two_smallest<WCH, 2>(reinterpret_cast<const float *>(&Rr[rr][0]), acc[0].m1, acc[0].m2, acc[0].sgn);
-            cn_two_smallest<WCH, 2>(reinterpret_cast<const float *>(&Rr[rr][0]) + 1, acc[1].m1, acc[1].m2, acc[1].sgn);
+            if constexpr (NE > 0) {
+#pragma unroll
+                for (int v = 0; v < NF; v++)
+                    cn_two_smallest_lead<WCH, 2>(elo[v], emid[v], esg[v], reinterpret_cast<const float *>(&Rr[rr][NE]) + v, acc[v].m1, acc[v].m2, acc[v].sgn);
+            } else {
+                cn_two_smallest<WCH, 2>(reinterpret_cast<const float *>(&Rr[rr][0]), acc[0].m1, acc[0].m2, acc[0].sgn);
+                cn_two_smallest<WCH, 2>(reinterpret_cast<const float *>(&Rr[rr][0]) + 1, acc[1].m1, acc[1].m2, acc[1].sgn);
+            }
 #endif
             // merge the two halves of the row: the two smallest of {m1,m2} U {m1',m2'}, XOR of the signs
             uint32_t a1 = f2u(acc[0].m1), b1 = f2u(acc[1].m1), a2 = f2u(acc[0].m2), b2 = f2u(acc[1].m2), as = acc[0].sgn, bs = acc[1].sgn;
@@ -342,7 +376,7 @@ template <typename GM, bool HIST, bool NORM = false> __global__ __launch_bounds_
             const uint32_t key[NF] = {keyu, keyv};
             __builtin_amdgcn_s_setprio(LOC ? QC_PRIO_WR_LOC : QC_PRIO_WR);
             static_for<RPT * WCH>([&](auto I) {
-                constexpr int r_ = decltype(I)::value / WCH, i = decltype(I)::value % WCH;
+                constexpr int r_ = decltype(I)::value / WCH, i = (decltype(I)::value % WCH + NL) % WCH; // the stored edges first
                 if (r_ != rr) return;
                 v2f32 Rn;
                 Rn.x = cn_out(Rr[rr][i].x, m2f[0], key[0]);
@@ -352,6 +386,9 @@ template <typename GM, bool HIST, bool NORM = false> __global__ __launch_bounds_
                 if constexpr (!(LOC && i < NL)) lds_st2_imm<(r_ * GJ * WC + i) * Z * MSG>(rbase, Rn); // a local edge's R has no reader but this thread
             });
         }
+        // the local edges' outputs have no store: they stand between the last store and the drain wait, not behind it where the last wave to
+        // reach the barrier spent them after idling (14.39 -> 14.62 M codewords/s; one local edge after every second store: the same)
+        if (NL > 0) __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __syncthreads();
 #ifdef QC_STAMPS
@@ -378,7 +415,7 @@ template <typename GM, bool HIST, bool NORM = false> __global__ __launch_bounds_
 #pragma unroll
         for (int v = 0; v < NF; v++) bad[v] = false;
         if (a.max_iter > 1) vn_any(bad);
-        else vn_first(bad);
+        else vn_first(bad, no_early);
         if (LOC) __syncthreads(); // emit reads S in the natural layout: other threads' stores
         emit(~done, bad);
         flags_publish(bad, a.max_iter);

@@ -47,4 +47,32 @@ template <typename P, int N, typename T> BLDPC_SELECT_FN void two_smallest(const
     }
 }
 
+// The same network entered behind its first triple: lo0 = min3 and mid0 = med3 of the first three values come ready-made, rest holds the
+// other N - 3.  For a caller that has the first triple long before the others (the half-row kernel's local edges, whose values need no
+// LDS read): exactly the operations two_smallest<P, N> spends after its first min3 / med3, in the same grouping, so the same bits.
+template <typename P, int N, typename T> BLDPC_SELECT_FN void two_smallest_lead(T lo0, T mid0, const T (&rest)[N - 3], T &m1, T &m2)
+{
+    static_assert(N >= 4, "the first triple and one value more at least");
+    if constexpr (N == 4) {
+        m2 = P::med3(lo0, mid0, rest[0]);
+        m1 = P::min(lo0, rest[0]);
+    } else {
+        constexpr int K = N / 3, R = N % 3;
+        T low[K + R], mid[K];
+        low[0] = lo0;
+        mid[0] = mid0;
+#pragma unroll
+        for (int k = 1; k < K; k++) {
+            low[k] = P::min3(rest[3 * k - 3], rest[3 * k - 2], rest[3 * k - 1]);
+            mid[k] = P::med3(rest[3 * k - 3], rest[3 * k - 2], rest[3 * k - 1]);
+        }
+#pragma unroll
+        for (int r = 0; r < R; r++) low[K + r] = rest[3 * K - 3 + r];
+        two_smallest<P, K + R, T>(low, m1, m2);
+#pragma unroll
+        for (int k = 0; k + 2 <= K; k += 2) m2 = P::min3(m2, mid[k], mid[k + 1]);
+        if constexpr (K % 2) m2 = P::min(m2, mid[K - 1]);
+    }
+}
+
 } // namespace cldpc
