@@ -137,6 +137,11 @@ lib.bldpc_decode_erasure.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int,
 lib.bldpc_decode_erasure_host.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
 lib.bldpc_erasure_info.argtypes = [c_void_p, c_void_p]
 lib.bldpc_erasure_plan_host.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p]
+lib.bldpc_decode_erasure_ml.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+lib.bldpc_decode_erasure_ml_host.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p]
+lib.bldpc_erasure_ml_info.argtypes = [c_void_p, c_int, c_int, c_void_p]
+lib.bldpc_erasure_ml_plan_host.argtypes = [c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]
 lib.bldpc_rm_select_bits.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p]
 lib.bldpc_rm_recover_bits.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]
 lib.bldpc_rm_select_bits_host.argtypes = [c_void_p, c_void_p, c_int, c_void_p]

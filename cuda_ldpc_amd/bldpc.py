@@ -211,6 +211,13 @@ class BinaryCode:
         check(lib.bldpc_erasure_info(self._h, _np_ptr(d)), "bldpc_erasure_info")
         return dict(lds_bytes=int(d[0]), threads=int(d[1]), frames_per_wg=int(d[2]), fits=int(d[0]) <= ERASURE_LDS_BOUND)
 
+    def erasure_ml_info(self, max_erased=0, tier="auto"):
+        """bldpc_erasure_ml_info: dict(matrix_bytes, threads, tier, slots) of the elimination kernel k_er_ml for this code at max_erased
+        (0: M), without a launch; slots is the workspace tier's at F = 65536."""
+        d = np.zeros(4, np.int32)
+        check(lib.bldpc_erasure_ml_info(self._h, int(max_erased), _ml_tier(tier), _np_ptr(d)), "bldpc_erasure_ml_info")
+        return _ml_info(d)
+
     @property
     def qc_variant(self):
         """Index into qc_variants() of the fused kernel variant this code runs on (-1: the table kernels serve it)."""
@@ -844,6 +851,84 @@ def erasure_plan_host(H, J, L, Z):
     d = np.zeros(4, np.int32)
     check(lib.bldpc_erasure_plan_host(J, L, Z, _np_ptr(H), _np_ptr(d)), "erasure_plan_host")
     return dict(lds_bytes=int(d[0]), threads=int(d[1]), frames_per_wg=int(d[2]), fits=int(d[0]) <= ERASURE_LDS_BOUND)
+
+
+# ---- erasure decoding by elimination (bldpc.h): the maximum-likelihood decoder of the erasure channel ------------------------------------
+ML_NONE, ML_SOLVED, ML_PARTIAL, ML_STUCK, ML_INCONSISTENT, ML_SKIPPED = range(6)  # status of a frame
+ML_TIERS = {"auto": 0, "lds": 1, "workspace": 2}
+
+
+def _ml_tier(tier):
+    if tier not in ML_TIERS:
+        raise ValueError("tier must be one of %s, not %r" % (sorted(ML_TIERS), tier))
+    return ML_TIERS[tier]
+
+
+def _ml_info(d):
+    return dict(matrix_bytes=int(d[0]), threads=int(d[1]), tier={1: "lds", 2: "workspace"}.get(int(d[2])), slots=int(d[3]))
+
+
+def LDPC_Decoder_Erasure_ML_GPU(code, bits, erased, F, max_erased=0, tier="auto", D=None, want_bits=True, want_erased=True, want_D=False,
+                                stream=None):
+    """bldpc_decode_erasure_ml: maximum-likelihood decoding on the erasure channel (semantics in include/bldpc.h): per frame the linear
+    system the erased positions leave is reduced over GF(2), one workgroup a frame (k_er_ml, or k_er_ml_ws with the matrix in a workspace
+    slot).  bits, erased: CUDA int32 [N, ceil(F/32)], typically the first N rows of a peeling Dbits and its Ebits.  Frames with more
+    than max_erased erasures (0: M) are left as they came.  Returns dict(D=int32 [N+1, F] with row N the flag, given or with want_D=True,
+    else None; Dbits=int32 [N+1, ceil(F/32)] or None; Ebits=int32 [N, ceil(F/32)] or None; status=int32 [F], ML_NONE .. ML_SKIPPED;
+    rank=int32 [F], the rank of the frame's system, -1 where skipped)."""
+    if not isinstance(F, (int, np.integer)) or F <= 0:
+        raise ValueError("F must be a positive int")
+    if not (torch.is_tensor(bits) and bits.is_cuda and torch.is_tensor(erased) and erased.is_cuda and erased.device == bits.device):
+        raise ValueError("bits and erased must be CUDA int32 tensors [N, ceil(F/32)] on one device")
+    dev = bits.device
+    _check_bits(bits, code.N, F, dev)
+    _check_bits(erased, code.N, F, dev)
+    t = _ml_tier(tier)
+    if D is not None:
+        _check_D(D, code.N, F, dev)
+    elif want_D:
+        D = torch.empty((code.N + 1, F), dtype=torch.int32, device=dev)
+    elif not (want_bits or want_erased):
+        raise ValueError("the call must have an output: D, want_D, want_bits or want_erased")
+    Dbits = torch.empty((code.N + 1, _words(F)), dtype=torch.int32, device=dev) if want_bits else None
+    Ebits = torch.empty((code.N, _words(F)), dtype=torch.int32, device=dev) if want_erased else None
+    status = torch.empty(F, dtype=torch.int32, device=dev)
+    rank = torch.empty(F, dtype=torch.int32, device=dev)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(dev)).cuda_stream)
+    check(lib.bldpc_decode_erasure_ml(code._h, _dev_ptr(bits), _dev_ptr(erased), int(F), int(max_erased), t, _dev_ptr(D), _dev_ptr(Dbits),
+                                      _dev_ptr(Ebits), _dev_ptr(status), _dev_ptr(rank), st), "LDPC_Decoder_Erasure_ML_GPU")
+    return dict(D=D, Dbits=Dbits, Ebits=Ebits, status=status, rank=rank)
+
+
+def erasure_ml_host(H, J, L, Z, bits, erased, F, max_erased=0):
+    """bldpc_decode_erasure_ml_host: the elimination decoder on the host (no device), the statement of its semantics.  bits, erased:
+    uint32 [N, ceil(F/32)].  Returns dict(D=int32 [N+1, F], Dbits=uint32 [N+1, ceil(F/32)], Ebits=uint32 [N, ceil(F/32)], status=int32
+    [F], rank=int32 [F])."""
+    H = np.ascontiguousarray(H, np.int32)
+    if H.size != J * L:
+        raise ValueError("H must hold J*L shifts")
+    if not isinstance(F, (int, np.integer)) or F <= 0:
+        raise ValueError("F must be a positive int")
+    N = L * Z
+    bits, erased = _check_bits(bits, N, F), _check_bits(erased, N, F)
+    D = np.zeros((N + 1, F), np.int32)
+    Dbits = np.zeros((N + 1, _words(F)), np.uint32)
+    Ebits = np.zeros((N, _words(F)), np.uint32)
+    status, rank = np.zeros(F, np.int32), np.zeros(F, np.int32)
+    check(lib.bldpc_decode_erasure_ml_host(J, L, Z, _np_ptr(H), _np_ptr(bits), _np_ptr(erased), int(F), int(max_erased), _np_ptr(D), _np_ptr(Dbits),
+                                           _np_ptr(Ebits), _np_ptr(status), _np_ptr(rank)), "erasure_ml_host")
+    return dict(D=D, Dbits=Dbits, Ebits=Ebits, status=status, rank=rank)
+
+
+def erasure_ml_plan_host(H, J, L, Z, max_erased=0, tier="auto"):
+    """bldpc_erasure_ml_plan_host: what BinaryCode.erasure_ml_info returns, from the block matrix alone (no device; the 256 compute units
+    of an MI355X).  A refusal (LdpcError) is the one the device call would make."""
+    H = np.ascontiguousarray(H, np.int32)
+    if H.size != J * L:
+        raise ValueError("H must hold J*L shifts")
+    d = np.zeros(4, np.int32)
+    check(lib.bldpc_erasure_ml_plan_host(J, L, Z, _np_ptr(H), int(max_erased), _ml_tier(tier), _np_ptr(d)), "erasure_ml_plan_host")
+    return _ml_info(d)
 
 
 def Statistic_Bits(code, Dbits, F, counters, Ebits=None, CodeWordBits=None, iters=None, length=0, stream=None):

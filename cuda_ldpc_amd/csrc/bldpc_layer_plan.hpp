@@ -12,7 +12,8 @@ struct bldpc_code;
 
 namespace cldpc {
 
-enum LayerSlot { kSlotMinSum, kSlotBp, kSlotQuant, kSlotBitflip, kSlotErasure }; // the code object keeps one plan per layered decoder, one for bit flipping, one for peeling
+// the code object keeps one plan per layered decoder, one for bit flipping, one for peeling, one for elimination
+enum LayerSlot { kSlotMinSum, kSlotBp, kSlotQuant, kSlotBitflip, kSlotErasure, kSlotErasureMl };
 
 struct LayerPlan {
     bool built = false;

@@ -14,7 +14,7 @@ import torch
 from . import sharding
 from ._lib import check, lib
 from .bldpc import (BF_GRADIENT, BF_THRESHOLD, BSCChannel_GPU, Hard_Pack, LDPC_Decoder_BitFlip_GPU,
-                    BECChannel_GPU, Hard_Pack_Int, LDPC_Decoder_Erasure_GPU, RM_Recover_Bits, RM_Select_Bits, Statistic_Bits,
+                    BECChannel_GPU, Hard_Pack_Int, LDPC_Decoder_Erasure_GPU, LDPC_Decoder_Erasure_ML_GPU, RM_Recover_Bits, RM_Select_Bits, Statistic_Bits,
                     EXIT_BATCH_GLOBAL, EXIT_FIXED, EXIT_PER_FRAME, KERNEL_AUTO, STOP_PREFIX, STOP_SYNDROME, AWGNChannel_CPU, AWGNChannel_Fading_GPU,
                     AWGNChannel_GPU, AWGNChannel_QAM_Fading_GPU, AWGNChannel_QAM_GPU, AWGNChannel_RM_Combine_GPU, AWGNChannel_RM_GPU,
                     Decode_Statistic, Demodulate_QAM, Demodulate_QAM_Fading, Fading, Fading_Gains, Frames_Gather, Frames_Scatter, IL_NONE, IL_ROWCOL,
@@ -364,7 +364,8 @@ def sweep_bsc(code, ps, seeds=(173, 173, 173), dist=None, log=print, **kw):
 
 
 def Simulation_BEC_GPU(code, seed, p, SIM, Num_Frames_OneTime=4096, maxIT=100, PN_Message=0, pn_seed=0, rate_match=None, max_batches=None,
-                       leastErrorFrames=50, leastTestFrames=10000, displayStep=40960, dist=None, device=None, log=print):
+                       leastErrorFrames=50, leastTestFrames=10000, displayStep=40960, dist=None, device=None, log=print, ml=False,
+                       ml_max_erased=0, ml_tier="auto"):
     """One point of an erasure sweep: the binary erasure channel with erasure probability p, then peeling, all on packed words.  A batch
     is PN_CodeWords (PN_Message=1; the all-zero word otherwise) -> Hard_Pack_Int, and RM_Select_Bits under a profile -> BECChannel_GPU on
     the N, or the profile's E, transmitted rows -> RM_Recover_Bits under a profile (punctured positions erased, shortened ones known 0)
@@ -372,7 +373,9 @@ def Simulation_BEC_GPU(code, seed, p, SIM, Num_Frames_OneTime=4096, maxIT=100, P
     is made.  `seed` (int32[3]) is the RandomModule state, advanced in place by the WHOLE batch on every rank, one draw per transmitted
     bit (sharding.bec_draws_per_frame); the batch loop, its stop rule and the sharding over ranks are those of Simulation_BSC_GPU.
     rate_match takes linear and circular profiles; under one the bit error rate divides by the prefix bits that are not shortened, as in
-    Simulation_GPU.  SIM.SNR is printed as it is: the caller may keep p there."""
+    Simulation_GPU.  SIM.SNR is printed as it is: the caller may keep p there.  ml=True: after peeling, LDPC_Decoder_Erasure_ML_GPU on
+    peeling's Dbits[:N] and Ebits (frames with more than ml_max_erased erasures left, 0 = M, stay as peeling left them; ml_tier as its
+    tier), and the statistics are taken on the new words with peeling's iteration counts."""
     if PN_Message not in (0, 1):
         raise ValueError("PN_Message must be 0 (all-zero codeword) or 1 (random codewords)")
     if not (np.isfinite(p) and 0.0 <= p <= 1.0):
@@ -413,6 +416,9 @@ def Simulation_BEC_GPU(code, seed, p, SIM, Num_Frames_OneTime=4096, maxIT=100, P
             if rm is not None:
                 bits, erased = RM_Recover_Bits(rm, bits, count, rx_erased=erased)
             r = LDPC_Decoder_Erasure_GPU(code, bits, erased, count, max_iter=maxIT)
+            if ml:
+                r = dict(LDPC_Decoder_Erasure_ML_GPU(code, r["Dbits"][:code.N], r["Ebits"], count, max_erased=ml_max_erased, tier=ml_tier),
+                         iters=r["iters"])
             Statistic_Bits(code, r["Dbits"], count, dev_cnt, Ebits=r["Ebits"], CodeWordBits=cwbits, iters=r["iters"], length=length)
         sharding.allreduce_counters(dev_cnt, dist)
         c = dev_cnt.cpu().tolist()

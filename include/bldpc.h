@@ -851,6 +851,63 @@ int bldpc_statistic_bits(const bldpc_code *code, const unsigned *Dbits, const un
 int bldpc_statistic_bits_host(int N, const unsigned *Dbits, const unsigned *Ebits, const unsigned *CodeWordBits, int F, int length,
                               const int *iters, long long *counters);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * Erasure decoding by elimination: the maximum-likelihood decoder of the binary erasure channel.  Peeling stops at the first
+ * stopping set; what is left is a linear system over GF(2), and this call solves it.  Layouts are those of "erasure decoding".
+ *   bits_in, erased_in  uint32 [N][W]; value bits under an erasure and padding bits are ignored
+ *   Dbits   uint32 [N+1][W], row N the flag "nothing erased and every check sum zero", or NULL
+ *   Ebits   uint32 [N][W], the residual mask, or NULL
+ *   D       int32 [N+1][F], the unpacked Dbits, or NULL
+ *   status, rank  int32 [F] each, or NULL
+ * Outputs must not overlap inputs.  The first N rows of a peeling Dbits together with its Ebits are a valid input pair: that is the
+ * intended use.
+ *
+ * Per frame, independent of any elimination order: x = bits_in & ~erased_in, E the set of erased positions, e = |E|.  One equation per
+ * check row c: the XOR of the unknowns x_v, v in E and in the row, equals a_c, the XOR of the row's known bits.
+ *   BLDPC_ML_NONE          e == 0: x, nothing erased, rank 0
+ *   BLDPC_ML_SKIPPED       e > max_erased: as the input (x, E), flag 0, rank -1
+ *   BLDPC_ML_INCONSISTENT  the system has no solution (the known bits are no part of a codeword): as the input, flag 0, rank = the rank
+ *                          of the coefficient matrix
+ *   BLDPC_ML_SOLVED        rank == e: every unknown becomes known
+ *   BLDPC_ML_PARTIAL       rank < e and some unknown has the same value in every solution
+ *   BLDPC_ML_STUCK         rank < e and no unknown has the same value in every solution
+ * In the three consistent cases an unknown is determined iff it has the same value in every solution (its unit vector is in the row
+ * space of the coefficient matrix; in reduced row echelon form it is a pivot column whose row has no other coefficient).  Determined
+ * unknowns become known with that value; the rest stay erased with value bit 0.  A row with one erasure determines it, so on a word
+ * whose known bits come from a codeword the call gives what peeling followed by the call gives, and never less than peeling.  On an
+ * inconsistent word peeling's OR rule and this call differ on purpose: this call leaves such a word as it came.
+ * max_erased == 0 means M (with more unknowns than equations nothing is solved whole); any value in [1, N] is allowed.
+ *
+ * The device call: a list pass counts e per frame and lists the frames with 0 < e <= max_erased; persistent workgroups of k_er_ml take
+ * one listed frame each, build its augmented matrix (M rows of wpr = ceil((max_erased + 1) / 32) words, the right-hand side in bit e)
+ * and reduce it; a last pass writes the flag row.  tier: BLDPC_ML_LDS keeps the matrix in LDS (it fits when 4 M wpr bytes, two
+ * bitmaps of 4 ceil(N / 32) bytes and the list of erased positions, 4 max_erased bytes, are at most 162816 bytes);
+ * BLDPC_ML_WORKSPACE keeps it in a global slot owned by the workgroup, min(compute units, F, floor(1 GiB / matrix bytes)) slots a
+ * call; BLDPC_ML_AUTO takes LDS when it fits.  bldpc_last_kernel names the tier that ran: "k_er_ml" or "k_er_ml_ws".  Asynchronous
+ * on `stream`; allocates nothing once its scratch has grown.
+ * BLDPC_EINVAL: a null input, F <= 0, max_erased outside [0, N], an unknown tier, all of D, Dbits and Ebits null.
+ * BLDPC_EUNSUPPORTED: a code built from an address table; M above 65536; bitmaps and list above the LDS bound; BLDPC_ML_LDS when the
+ * matrix does not fit (decided at the call: it depends on max_erased); a workspace of which not even one slot fits in 1 GiB.
+ * The _host form is the definition (plain C++, one frame at a time, at most 16 threads) and has no size bound beyond max_erased.
+ *
+ * bldpc_erasure_ml_info / bldpc_erasure_ml_plan_host: info[4] = matrix bytes of a workgroup, threads, the tier taken (-1 when
+ * refused), workspace slots at F = 65536 (0 on the LDS tier); the second without a device, for the 256 compute units of an MI355X. */
+#define BLDPC_ML_NONE 0
+#define BLDPC_ML_SOLVED 1
+#define BLDPC_ML_PARTIAL 2
+#define BLDPC_ML_STUCK 3
+#define BLDPC_ML_INCONSISTENT 4
+#define BLDPC_ML_SKIPPED 5
+#define BLDPC_ML_AUTO 0
+#define BLDPC_ML_LDS 1
+#define BLDPC_ML_WORKSPACE 2
+int bldpc_decode_erasure_ml(bldpc_code *code, const unsigned *bits_in, const unsigned *erased_in, int F, int max_erased, int tier, int *D,
+                            unsigned *Dbits, unsigned *Ebits, int *status, int *rank, void *stream);
+int bldpc_decode_erasure_ml_host(int J, int L, int Z, const int *H, const unsigned *bits_in, const unsigned *erased_in, int F, int max_erased,
+                                 int *D, unsigned *Dbits, unsigned *Ebits, int *status, int *rank);
+int bldpc_erasure_ml_info(bldpc_code *code, int max_erased, int tier, int info[4]);
+int bldpc_erasure_ml_plan_host(int J, int L, int Z, const int *H, int max_erased, int tier, int info[4]);
+
 const char *bldpc_last_error(void);
 
 #ifdef __cplusplus

@@ -10,6 +10,7 @@
     python sweep.py binary --hard gradient --per-frame --pn-message --bsc 0.002,0.004,0.006
     python sweep.py binary --hard threshold --device-channel --per-frame --start 4 --stop 6 --step 0.5
     python sweep.py binary --erasure --bec 0.08,0.10,0.12,0.14 --pn-message --puncture 2208:2304 --iters 100
+    python sweep.py binary --erasure --bec 0.12,0.14,0.16 --ml
     python sweep.py binary --device-channel --per-frame --layered --pn-message --qam 64 --interleave rowcol --fading 16 --harq 0:2160,2160:48,500:2300
     python sweep.py nb --pn-message --qam 64 --fading 16
     python sweep.py nb --device-channel --pn-message --puncture 88:96
@@ -105,6 +106,10 @@ def main():
                     "--iters; no --hard, --layered, --bp, --quant, --qam, --fading, --harq")
     ap.add_argument("--bec", metavar="P[,P...]", default=None, help="--erasure: erasure probabilities of the binary erasure channel in place of the "
                     "SNR list (Simulation_BEC_GPU; the first column of a row is P)")
+    ap.add_argument("--ml", action="store_true", help="--erasure: after peeling, maximum-likelihood decoding by elimination over GF(2) on the frames "
+                    "peeling leaves stuck (bldpc_decode_erasure_ml)")
+    ap.add_argument("--ml-max-erased", type=int, default=0, metavar="E", help="--ml: frames with more than E positions still erased are left as "
+                    "peeling left them (default 0: the number of check rows)")
     ap.add_argument("--alpha", type=float, default=1.0, help="binary: normalisation factor in (0, 1]; with --layered the layered decoder's, without it "
                     "normalised min-sum on the flooding decoders (with --fixed or --per-frame)")
     ap.add_argument("--stop-rule", choices=["prefix", "syndrome"], default=None,
@@ -196,6 +201,12 @@ def main():
             ap.error("--bec takes probabilities in [0, 1]")
     elif args.bec is not None:
         ap.error("--bec belongs to --erasure")
+    if (args.ml or args.ml_max_erased) and not args.erasure:
+        ap.error("--ml and --ml-max-erased belong to --erasure")
+    if args.ml_max_erased and not args.ml:
+        ap.error("--ml-max-erased belongs to --ml")
+    if args.ml_max_erased < 0:
+        ap.error("--ml-max-erased takes a count of erased positions, 0 for the number of check rows")
     rows = args.layered or args.bp or quant is not None  # the row-layered decoders take the same modes and rules
     if args.which == "binary" and rows:
         if args.as_written or not (args.fixed or args.per_frame):
@@ -297,13 +308,15 @@ def main():
             from cuda_ldpc_amd.simulation import sweep_bec
             rm = C.RateMatch(code.N, shorten, puncture) if ratematch else None
             if rank == 0:
-                print("# %s N=%d K=%d, binary erasure channel, peeling, maxIT=%d, batch=%d x %d GPU(s)%s%s" % (
-                    os.path.basename(args.matrix), code.N, code.K, args.iters or 100, args.batch, world,
+                print("# %s N=%d K=%d, binary erasure channel, %s, maxIT=%d, batch=%d x %d GPU(s)%s%s" % (
+                    os.path.basename(args.matrix), code.N, code.K, "peeling + elimination" if args.ml else "peeling", args.iters or 100, args.batch,
+                    world,
                     ", %d shortened, %d punctured, E=%d" % (rm.n_short, rm.n_punct, rm.E) if rm is not None else "",
                     ", random codewords (PN seed %d)" % args.pn_seed if args.pn_message else ""))
                 print("#   P      NTF   NEF         FER         BER  AverIT       FER_F      FER_A")
             sweep_bec(code, bec, dist=dist, Num_Frames_OneTime=args.batch, maxIT=args.iters or 100, max_batches=args.max_batches, displayStep=10 ** 12,
-                      PN_Message=1 if args.pn_message else 0, pn_seed=args.pn_seed, rate_match=rm, log=print if rank == 0 else None)
+                      PN_Message=1 if args.pn_message else 0, pn_seed=args.pn_seed, rate_match=rm, log=print if rank == 0 else None,
+                      **(dict(ml=True, ml_max_erased=args.ml_max_erased) if args.ml else {}))
             if world > 1:
                 dist.destroy_process_group()
             return
