@@ -20,6 +20,7 @@ from .bldpc import (BinaryCode, Get_H, Transform_H, LDPC_Decoder_GPU, Decode_Sta
                     BF_THRESHOLD, BF_GRADIENT, Hard_Pack, Hard_Pack_Int, Hard_Unpack, Hard_Pack_host, Hard_Pack_Int_host, Hard_Unpack_host, BSCChannel_GPU, BSCChannel_CPU, LDPC_Decoder_BitFlip_GPU, bitflip_host, bitflip_plan_host,
                     BECChannel_GPU, BECChannel_CPU, LDPC_Decoder_Erasure_GPU, erasure_host, erasure_plan_host, RM_Select_Bits, RM_Recover_Bits, RM_Select_Bits_host, RM_Recover_Bits_host, Statistic_Bits, Statistic_Bits_host,
                     LDPC_Decoder_Erasure_ML_GPU, erasure_ml_host, erasure_ml_plan_host, ML_NONE, ML_SOLVED, ML_PARTIAL, ML_STUCK, ML_INCONSISTENT, ML_SKIPPED,
+                    LDPC_Decoder_OSD_GPU, osd_host, osd_plan_host,
                     STOP_PREFIX, STOP_SYNDROME, EXIT_FIXED, EXIT_BATCH_GLOBAL, EXIT_PER_FRAME, KERNEL_AUTO, KERNEL_TABLE, KERNEL_QC_LDS)
 
 __all__ = ["BinaryCode", "Get_H", "Transform_H", "LDPC_Decoder_GPU", "Decode_Statistic", "Statistic", "SimCounters", "AWGNChannel_CPU", "AWGNChannel_GPU", "sigma_of",
@@ -35,5 +36,6 @@ __all__ = ["BinaryCode", "Get_H", "Transform_H", "LDPC_Decoder_GPU", "Decode_Sta
            "BF_THRESHOLD", "BF_GRADIENT", "Hard_Pack", "Hard_Pack_Int", "Hard_Unpack", "Hard_Pack_host", "Hard_Pack_Int_host", "Hard_Unpack_host", "BSCChannel_GPU", "BSCChannel_CPU", "LDPC_Decoder_BitFlip_GPU", "bitflip_host", "bitflip_plan_host",
            "BECChannel_GPU", "BECChannel_CPU", "LDPC_Decoder_Erasure_GPU", "erasure_host", "erasure_plan_host", "RM_Select_Bits", "RM_Recover_Bits", "RM_Select_Bits_host", "RM_Recover_Bits_host", "Statistic_Bits", "Statistic_Bits_host",
            "LDPC_Decoder_Erasure_ML_GPU", "erasure_ml_host", "erasure_ml_plan_host", "ML_NONE", "ML_SOLVED", "ML_PARTIAL", "ML_STUCK", "ML_INCONSISTENT", "ML_SKIPPED",
+           "LDPC_Decoder_OSD_GPU", "osd_host", "osd_plan_host",
            "STOP_PREFIX", "STOP_SYNDROME",
            "EXIT_FIXED", "EXIT_BATCH_GLOBAL", "EXIT_PER_FRAME", "KERNEL_AUTO", "KERNEL_TABLE", "KERNEL_QC_LDS"]

@@ -211,6 +211,13 @@ class BinaryCode:
         check(lib.bldpc_erasure_info(self._h, _np_ptr(d)), "bldpc_erasure_info")
         return dict(lds_bytes=int(d[0]), threads=int(d[1]), frames_per_wg=int(d[2]), fits=int(d[0]) <= ERASURE_LDS_BOUND)
 
+    def osd_info(self, tier="auto"):
+        """bldpc_osd_info: dict(lds_bytes, threads, tier, slots) of the reprocessing kernel k_osd for this code, without a launch; slots
+        is the workspace tier's at F = 65536.  Builds the code's generator on first use, for the rank of H."""
+        d = np.zeros(4, np.int32)
+        check(lib.bldpc_osd_info(self._h, _ml_tier(tier), _np_ptr(d)), "bldpc_osd_info")
+        return _osd_info(d)
+
     def erasure_ml_info(self, max_erased=0, tier="auto"):
         """bldpc_erasure_ml_info: dict(matrix_bytes, threads, tier, slots) of the elimination kernel k_er_ml for this code at max_erased
         (0: M), without a launch; slots is the workspace tier's at F = 65536."""
@@ -929,6 +936,72 @@ def erasure_ml_plan_host(H, J, L, Z, max_erased=0, tier="auto"):
     d = np.zeros(4, np.int32)
     check(lib.bldpc_erasure_ml_plan_host(J, L, Z, _np_ptr(H), int(max_erased), _ml_tier(tier), _np_ptr(d)), "erasure_ml_plan_host")
     return _ml_info(d)
+
+
+# ---- ordered-statistics reprocessing (bldpc.h): OSD-0 on the frames a soft decoder leaves with a non-zero syndrome --------------------------
+def _osd_info(d):
+    return dict(lds_bytes=int(d[0]), threads=int(d[1]), tier={1: "lds", 2: "workspace"}.get(int(d[2])), slots=int(d[3]))
+
+
+def LDPC_Decoder_OSD_GPU(code, app, D=None, tier="auto", out=None, stream=None):
+    """bldpc_decode_osd: ordered-statistics reprocessing of order 0 (semantics in include/bldpc.h): per processed frame the least
+    reliable basis of H's columns is found by elimination in the order of |app|, the hard decisions of app are kept outside it and
+    re-derived from the parity checks on it, so the frame comes out a codeword with flag 1; one workgroup a frame (k_osd, or k_osd_ws
+    with the record of the row operations in a workspace slot).  app: CUDA float32 [N, F], a decoder's app or a channel array.  D: a
+    decoder's D, CUDA int32 [N+1, F]: the frames whose flag row is 0 are processed, the others kept; None processes every frame.
+    out: where the result goes, CUDA int32 [N+1, F]; default D itself (in place), or a new tensor when D is None.
+    Returns (D, flips, scanned): the result, and int32 [F] each the number of hard decisions changed (-1 on a kept frame) and the
+    1-based place in the order of reliability of the last basis position (0 on a kept frame)."""
+    if not (torch.is_tensor(app) and app.is_cuda and app.dtype == torch.float32 and app.is_contiguous() and app.dim() == 2
+            and app.shape[0] == code.N and app.shape[1] > 0):
+        raise ValueError("app must be a contiguous CUDA float32 tensor [N=%d, F]" % code.N)
+    dev, F = app.device, int(app.shape[1])
+    t = _ml_tier(tier)
+    if D is not None:
+        _check_D(D, code.N, F, dev)
+    if out is None:
+        out = D if D is not None else torch.empty((code.N + 1, F), dtype=torch.int32, device=dev)
+    else:
+        _check_D(out, code.N, F, dev)
+    flips = torch.empty(F, dtype=torch.int32, device=dev)
+    scanned = torch.empty(F, dtype=torch.int32, device=dev)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream(dev)).cuda_stream)
+    check(lib.bldpc_decode_osd(code._h, _dev_ptr(app), _dev_ptr(D), F, t, _dev_ptr(out), _dev_ptr(flips), _dev_ptr(scanned), st), "LDPC_Decoder_OSD_GPU")
+    return out, flips, scanned
+
+
+def osd_host(H, J, L, Z, app, D=None):
+    """bldpc_decode_osd_host: ordered-statistics reprocessing on the host (no device), the statement of its semantics.  app: float32
+    [N, F]; D: int32 [N+1, F] or None, as in LDPC_Decoder_OSD_GPU (it is not written).  Returns (D int32 [N+1, F], flips int32 [F],
+    scanned int32 [F])."""
+    H = np.ascontiguousarray(H, np.int32)
+    if H.size != J * L:
+        raise ValueError("H must hold J*L shifts")
+    N = L * Z
+    app = np.ascontiguousarray(app)
+    if app.dtype != np.float32 or app.ndim != 2 or app.shape[0] != N or app.shape[1] < 1:
+        raise ValueError("app must be a float32 array [N=%d, F]" % N)
+    F = int(app.shape[1])
+    if D is not None:
+        D = np.ascontiguousarray(D)
+        if D.dtype != np.int32 or D.shape != (N + 1, F):
+            raise ValueError("D must be an int32 array [N+1=%d, F=%d]" % (N + 1, F))
+    out = np.zeros((N + 1, F), np.int32)
+    flips, scanned = np.zeros(F, np.int32), np.zeros(F, np.int32)
+    check(lib.bldpc_decode_osd_host(J, L, Z, _np_ptr(H), _np_ptr(app), None if D is None else _np_ptr(D), F, _np_ptr(out), _np_ptr(flips),
+                                    _np_ptr(scanned)), "osd_host")
+    return out, flips, scanned
+
+
+def osd_plan_host(H, J, L, Z, tier="auto"):
+    """bldpc_osd_plan_host: what BinaryCode.osd_info returns, from the block matrix alone (no device; the 256 compute units of an
+    MI355X).  A refusal (LdpcError) is the one the device call would make."""
+    H = np.ascontiguousarray(H, np.int32)
+    if H.size != J * L:
+        raise ValueError("H must hold J*L shifts")
+    d = np.zeros(4, np.int32)
+    check(lib.bldpc_osd_plan_host(J, L, Z, _np_ptr(H), _ml_tier(tier), _np_ptr(d)), "osd_plan_host")
+    return _osd_info(d)
 
 
 def Statistic_Bits(code, Dbits, F, counters, Ebits=None, CodeWordBits=None, iters=None, length=0, stream=None):
@@ -1756,6 +1829,8 @@ class SimCounters:
     num_Alarm_Frames: int = 0
     SNR: float = 0.0
     _dev: object = field(default=None, repr=False)
+    num_OSD_Frames: int = field(default=0, repr=False, compare=False)   # Simulation_GPU(osd=True): frames reprocessed, and those of
+    num_OSD_Correct: int = field(default=0, repr=False, compare=False)  # them that came out equal to the word sent
 
     def ratios(self, length):
         n = max(self.num_Frames, 1)

@@ -42,14 +42,14 @@ struct bldpc_code {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     EncState *enc = nullptr; // systematic encoder and syndrome tables (bldpc_encode.hip), built on first use
     // the row-layered decoders (bldpc_layered.hip, bldpc_bp.hip, bldpc_quant.hip), the bit-flipping decoder (bldpc_bitflip.hip) and the
-    // peeling decoder (bldpc_erasure.hip) and the elimination decoder (bldpc_erasure_ml.hip): per decoder the edge tables, the tier
-    // choice and its own scratch, built on first use
-    LayerPlan *lay = nullptr, *bp = nullptr, *quant = nullptr, *bitflip = nullptr, *erasure = nullptr, *erasure_ml = nullptr;
+    // peeling decoder (bldpc_erasure.hip), the elimination decoder (bldpc_erasure_ml.hip) and ordered-statistics reprocessing
+    // (bldpc_osd.hip): per decoder the edge tables, the tier choice and its own scratch, built on first use
+    LayerPlan *lay = nullptr, *bp = nullptr, *quant = nullptr, *bitflip = nullptr, *erasure = nullptr, *erasure_ml = nullptr, *osd = nullptr;
 };
 
 LayerView cldpc::layer_view(bldpc_code *c, LayerSlot slot)
 {
-    LayerPlan **plan = slot == kSlotMinSum ? &c->lay : slot == kSlotBp ? &c->bp : slot == kSlotQuant ? &c->quant : slot == kSlotBitflip ? &c->bitflip : slot == kSlotErasure ? &c->erasure : &c->erasure_ml;
+    LayerPlan **plan = slot == kSlotMinSum ? &c->lay : slot == kSlotBp ? &c->bp : slot == kSlotQuant ? &c->quant : slot == kSlotBitflip ? &c->bitflip : slot == kSlotErasure ? &c->erasure : slot == kSlotErasureMl ? &c->erasure_ml : &c->osd;
     return LayerView{c->J, c->L, c->Z, c->N, c->M, c->K, c->has_qc ? c->H.data() : nullptr, plan, &c->last_kernel};
 }
 
@@ -237,6 +237,7 @@ extern "C" int bldpc_code_destroy(bldpc_code *c)
     delete c->bitflip;
     delete c->erasure;
     delete c->erasure_ml;
+    delete c->osd;
     for (hipEvent_t e : c->evr)
         if (e) (void)hipEventDestroy(e);
     delete c;

@@ -12,8 +12,8 @@ struct bldpc_code;
 
 namespace cldpc {
 
-// the code object keeps one plan per layered decoder, one for bit flipping, one for peeling, one for elimination
-enum LayerSlot { kSlotMinSum, kSlotBp, kSlotQuant, kSlotBitflip, kSlotErasure, kSlotErasureMl };
+// the code object keeps one plan per layered decoder, one for bit flipping, one for peeling, one for elimination, one for reprocessing
+enum LayerSlot { kSlotMinSum, kSlotBp, kSlotQuant, kSlotBitflip, kSlotErasure, kSlotErasureMl, kSlotOsd };
 
 struct LayerPlan {
     bool built = false;

@@ -18,7 +18,7 @@ from .bldpc import (BF_GRADIENT, BF_THRESHOLD, BSCChannel_GPU, Hard_Pack, LDPC_D
                     EXIT_BATCH_GLOBAL, EXIT_FIXED, EXIT_PER_FRAME, KERNEL_AUTO, STOP_PREFIX, STOP_SYNDROME, AWGNChannel_CPU, AWGNChannel_Fading_GPU,
                     AWGNChannel_GPU, AWGNChannel_QAM_Fading_GPU, AWGNChannel_QAM_GPU, AWGNChannel_RM_Combine_GPU, AWGNChannel_RM_GPU,
                     Decode_Statistic, Demodulate_QAM, Demodulate_QAM_Fading, Fading, Fading_Gains, Frames_Gather, Frames_Scatter, IL_NONE, IL_ROWCOL,
-                    LDPC_Decoder_BP_GPU, LDPC_Decoder_GPU, LDPC_Decoder_Layered_GPU, LDPC_Decoder_Quant_GPU, Modulate_QAM, PN_CodeWords, Quant,
+                    LDPC_Decoder_BP_GPU, LDPC_Decoder_GPU, LDPC_Decoder_Layered_GPU, LDPC_Decoder_OSD_GPU, LDPC_Decoder_Quant_GPU, Modulate_QAM, PN_CodeWords, Quant,
                     RM_Combine, RM_Demodulate_QAM_Recover, RM_Modulate_QAM, RM_Recover, RM_Select, SimCounters, Syndrome, _dev_ptr, sigma_of)
 from .nbldpc import sigma_of as nb_sigma_of
 
@@ -39,6 +39,27 @@ def _check_schedule(schedule, alpha, quant):
     if quant is not None and alpha != 1.0:
         raise ValueError("schedule='quant' takes its correction from quant.norm8 and quant.offset, not from alpha")
     return bp, layered
+
+
+def _check_osd(osd, schedule, stop_rule):
+    """osd=True against the schedule and the resolved stop rule, as Simulation_GPU and Simulation_HARQ_GPU both refuse it."""
+    if not osd:
+        return
+    if schedule not in ("layered", "bp", "quant"):
+        raise ValueError("osd belongs to schedule='layered', schedule='bp' and schedule='quant': reprocessing orders the positions by a "
+                         "decoder's a-posteriori values")
+    if stop_rule != STOP_SYNDROME:
+        raise ValueError("osd needs stop_rule=STOP_SYNDROME: the frames to reprocess are those whose flag says 'no codeword'")
+
+
+def _osd_reprocess(code, D, app, cw, osd_cnt):
+    """LDPC_Decoder_OSD_GPU on a decoder's D (in place) and app (a quantised app converted to float, which is exact); adds the frames
+    reprocessed and those of them that came out equal to the word sent to osd_cnt (CUDA int64 [2])."""
+    _, flips, _ = LDPC_Decoder_OSD_GPU(code, app if app.dtype == torch.float32 else app.float(), D=D)
+    done = flips >= 0
+    same = ~((D[:code.N] != cw) if cw is not None else (D[:code.N] != 0)).any(0)
+    osd_cnt[0] += done.sum()
+    osd_cnt[1] += (done & same).sum()
 
 
 def _check_qam(n_QAM, CONSTELLATION, PN_Message, interleave):
@@ -113,7 +134,8 @@ def _qam_receive(rm, rx, con_dev, scale, short_llr, interleave, acc=None, done=N
 def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, exit_mode=EXIT_BATCH_GLOBAL, kernel=KERNEL_AUTO,
                    leastErrorFrames=50, leastTestFrames=10000, displayStep=40960, dist=None, device=None, max_batches=None,
                    log=print, device_channel=False, PN_Message=0, pn_seed=0, schedule="flooding", alpha=1.0, stop_rule=None,
-                   n_QAM=2, CONSTELLATION=None, rate_match=None, short_llr=1.0e4, quant=None, interleave=IL_NONE, fading=None, hard_rule=None):
+                   n_QAM=2, CONSTELLATION=None, rate_match=None, short_llr=1.0e4, quant=None, interleave=IL_NONE, fading=None, hard_rule=None,
+                   osd=False):
     """One SNR point (Simulation.cu:12-171).  `seed` (int32[3]) is the AWGN->seed state, advanced in place by the
     WHOLE batch on every rank so that all ranks stay on the reference's single noise stream.
 
@@ -166,7 +188,13 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
     sum-product scale); QAM: AWGNChannel_QAM_Fading_GPU -> Demodulate_QAM_Fading; with rate_match the compositions RM_Select ->
     channel at E -> RM_Recover and RM_Modulate_QAM -> channel -> Demodulate_QAM_Fading at E -> RM_Recover.  E[a^2] = 1, so the caller
     passes the sigma of the AWGN sweep.  Needs device_channel=True and EXIT_FIXED or EXIT_PER_FRAME; fading=None is the AWGN sweep,
-    call for call."""
+    call for call.
+
+    osd=True ("BP + OSD") sends the decoder's D and app through LDPC_Decoder_OSD_GPU before the statistics: the frames the decoder left
+    with a non-zero syndrome are reprocessed (ordered statistics of order 0, include/bldpc.h) and come out codewords with flag 1; the
+    iteration counts stay the decoder's.  schedule 'layered', 'bp' or 'quant' with stop_rule=STOP_SYNDROME; refused elsewhere.
+    SIM.num_OSD_Frames counts the frames reprocessed and SIM.num_OSD_Correct those of them that came out equal to the word sent; the
+    log row ends with both."""
     if PN_Message not in (0, 1):
         raise ValueError("PN_Message must be 0 (all-zero codeword) or 1 (random codewords)")
     bp, layered = _check_schedule(schedule, alpha, quant)
@@ -199,6 +227,7 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
         raise ValueError("PN_Message=1 needs exit_mode=EXIT_FIXED: the decoders' early exit tests for the all-zero word")
     if n_QAM != 2 and PN_Message == 1 and not device_channel:  # every refusal before anything touches the device
         raise ValueError("n_QAM != 2 needs device_channel=True: there is no host QAM channel on this path")
+    _check_osd(osd, schedule, stop_rule)
     qam_m, con = _check_qam(n_QAM, CONSTELLATION, PN_Message, interleave)
     _check_fading(fading, device_channel, exit_mode)
     rm = rate_match
@@ -222,6 +251,7 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
     per_frame = sharding.qam_draws_per_frame(n_tx, qam_m) if qam_m else sharding.binary_draws_per_frame(n_tx)
     con_dev = torch.from_numpy(con).to(device) if qam_m else None
     dev_cnt = torch.zeros(5, dtype=torch.int64, device=device)
+    osd_cnt = torch.zeros(2, dtype=torch.int64, device=device) if osd else None  # frames reprocessed, and of them equal to the word sent
     D = torch.empty((code.N + 1, max(count, 1)), dtype=torch.int32, device=device)
     length = code.K  # Message_CW 0 (define.cuh:61)
     llr_scale = 1.0 if qam_m else 2.0 / (sigma * sigma)  # schedule="bp": what makes the decoder's input a true LLR
@@ -253,6 +283,8 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
             yd = torch.from_numpy(AWGNChannel_CPU(my_seed, sigma, code.N, count, CodeWord=None if cw is None else cw.cpu().numpy())).to(device)
         seed[:] = sharding.lcg_jump(seed, F * per_frame)
         dev_cnt.zero_()
+        if osd:
+            osd_cnt.zero_()
         if count and hard:
             r = LDPC_Decoder_BitFlip_GPU(code, Hard_Pack(yd), count, rule=hard_rule, max_iter=maxIT, exit_mode=exit_mode, D=D)
             st = torch.cuda.current_stream(device).cuda_stream
@@ -260,13 +292,18 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
                   "Statistic")
         elif count and layered:
             if bp:
-                r = LDPC_Decoder_BP_GPU(code, yd, max_iter=maxIT, llr_scale=llr_scale, length=length, exit_mode=exit_mode, stop_rule=stop_rule, D=D)
+                r = LDPC_Decoder_BP_GPU(code, yd, max_iter=maxIT, llr_scale=llr_scale, length=length, exit_mode=exit_mode, stop_rule=stop_rule, D=D,
+                                        want_app=osd)
             elif quant is not None:
-                r = LDPC_Decoder_Quant_GPU(code, yd, quant, max_iter=maxIT, length=length, exit_mode=exit_mode, stop_rule=stop_rule, D=D)
+                r = LDPC_Decoder_Quant_GPU(code, yd, quant, max_iter=maxIT, length=length, exit_mode=exit_mode, stop_rule=stop_rule, D=D,
+                                           want_app=osd)
             else:
-                r = LDPC_Decoder_Layered_GPU(code, yd, max_iter=maxIT, alpha=alpha, length=length, exit_mode=exit_mode, stop_rule=stop_rule, D=D)
+                r = LDPC_Decoder_Layered_GPU(code, yd, max_iter=maxIT, alpha=alpha, length=length, exit_mode=exit_mode, stop_rule=stop_rule, D=D,
+                                             want_app=osd)
             if PN_Message and stop_rule != STOP_SYNDROME:
                 Syndrome(code, D, into_flag_row=True)
+            if osd:
+                _osd_reprocess(code, D, r["app"], cw, osd_cnt)
             st = torch.cuda.current_stream(device).cuda_stream
             check(lib.bldpc_statistic_per_frame(code._h, _dev_ptr(D), _dev_ptr(cw), count, length, _dev_ptr(r["iters"]), _dev_ptr(dev_cnt), st),
                   "Statistic")
@@ -289,11 +326,15 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
         SIM.Total_Iteration += c[2]
         SIM.num_False_Frames += c[3]
         SIM.num_Alarm_Frames += c[4]
+        if osd:
+            o = sharding.allreduce_counters(osd_cnt, dist).cpu().tolist()
+            SIM.num_OSD_Frames += o[0]
+            SIM.num_OSD_Correct += o[1]
         batches += 1
         stop = SIM.num_Error_Frames >= leastErrorFrames and SIM.num_Frames >= leastTestFrames
         last = max_batches is not None and batches >= max_batches
         if rank == 0 and log and (SIM.num_Frames % displayStep == 0 or stop or last):
-            log(format_row(SIM, ber_bits))
+            log(format_row(SIM, ber_bits) + ("  OSD %d %d" % (SIM.num_OSD_Frames, SIM.num_OSD_Correct) if osd else ""))
         if stop or (max_batches is not None and batches >= max_batches):
             return 1 if stop else 0
 
@@ -452,7 +493,8 @@ def sweep_bec(code, ps, seeds=(173, 173, 173), dist=None, log=print, **kw):
 class HarqCounters:
     """What Simulation_HARQ_GPU accumulates over the batches of one SNR point, all exact integers.  acked[t]: frames acknowledged at
     transmission t (0-based); undetected[t]: those of them whose first K bits differ from the word sent; never_acked: frames still
-    unacknowledged after the last transmission; bits_sent: the sum of E_t over the transmissions each frame used."""
+    unacknowledged after the last transmission; bits_sent: the sum of E_t over the transmissions each frame used.  osd_frames and
+    osd_correct (osd=True): the frames reprocessed after the last transmission, and those of them that came out equal to the word sent."""
     num_Frames: int = 0
     acked: list = field(default_factory=list)
     undetected: list = field(default_factory=list)
@@ -460,6 +502,8 @@ class HarqCounters:
     bits_sent: int = 0
     Total_Iteration: int = 0
     SNR: float = 0.0
+    osd_frames: int = field(default=0, repr=False, compare=False)
+    osd_correct: int = field(default=0, repr=False, compare=False)
 
     def ratios(self, info_bits):
         """FER after each transmission (a frame is good once it is acknowledged with the right word), mean transmissions per frame
@@ -481,7 +525,7 @@ def format_harq_row(SIM, info_bits):
 def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, maxIT=50, exit_mode=EXIT_FIXED, kernel=KERNEL_AUTO,
                         leastErrorFrames=50, leastTestFrames=10000, dist=None, device=None, max_batches=None, log=print, PN_Message=0,
                         pn_seed=0, schedule="flooding", alpha=1.0, stop_rule=None, short_llr=1.0e4, compact=True, keep_D=None, quant=None,
-                        n_QAM=2, CONSTELLATION=None, interleave=IL_NONE, fading=None):
+                        n_QAM=2, CONSTELLATION=None, interleave=IL_NONE, fading=None, osd=False):
     """One SNR point of incremental-redundancy HARQ over BPSK, or over n_QAM-QAM, on the device channel.  rvs = [rm_0, ..., rm_{T-1}]: the profile of
     each transmission (RateMatch.circular or RateMatch, all over code.N with the same shortened positions).  SIM is a HarqCounters.
 
@@ -516,7 +560,14 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
     (E_t over BPSK, ceil(E_t / m) over QAM) for all F frames of the batch from the fading stream, fading.seed -- ceil(S_t / Lc) draws
     per frame, owned whether a frame is acknowledged or not, so the stream's position after a batch depends on nothing that happened in
     it -- and runs as the composition RM_Select (or RM_Modulate_QAM) -> the fading channel -> (Demodulate_QAM_Fading ->) RM_Recover
-    for t = 0, RM_Combine under done = D[N] after it.  The noise stream is used exactly as without fading."""
+    for t = 0, RM_Combine under done = D[N] after it.  The noise stream is used exactly as without fading.
+
+    osd=True (schedule 'layered', 'bp' or 'quant' with stop_rule=STOP_SYNDROME; refused elsewhere): after the last transmission of a batch
+    the frames still unacknowledged are reprocessed by LDPC_Decoder_OSD_GPU on the D and app of their last decode, in place, so keep_D
+    receives codewords with flag 1 in their columns.  A reprocessed frame is NOT acknowledged by that: reprocessing always returns a
+    codeword, so its flag says nothing about the word sent.  The acknowledgement stays the decoder's flag, and acked, undetected,
+    never_acked, bits_sent and the iterations are what they are with osd=False; SIM.osd_frames and SIM.osd_correct count the frames
+    reprocessed and those of them that came out equal to the word sent, and the log row ends with both."""
     if PN_Message not in (0, 1):
         raise ValueError("PN_Message must be 0 (all-zero codeword) or 1 (random codewords)")
     bp, layered = _check_schedule(schedule, alpha, quant)
@@ -536,6 +587,7 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
             raise ValueError("PN_Message=1 with per-frame exit needs stop_rule=STOP_SYNDROME: STOP_PREFIX tests for the all-zero word")
     elif PN_Message == 1 and exit_mode != EXIT_FIXED:
         raise ValueError("PN_Message=1 needs exit_mode=EXIT_FIXED: the flooding decoders' early exit tests for the all-zero word")
+    _check_osd(osd, schedule, stop_rule)
     qam_m, con = _check_qam(n_QAM, CONSTELLATION, PN_Message, interleave)
     _check_fading(fading, True, exit_mode)
     rvs = list(rvs) if rvs is not None else []
@@ -564,6 +616,8 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
     N, K = code.N, code.K
     info_bits = K - rvs[0].n_short
     cnt = torch.zeros(2 * T + 3, dtype=torch.int64, device=device)  # acked[T], undetected[T], never, bits, iterations
+    osd_cnt = torch.zeros(2, dtype=torch.int64, device=device) if osd else None
+    last_app = [None]  # osd: the app of the latest decode()
     con_dev = torch.from_numpy(con).to(device) if qam_m else None
     llr_scale = 1.0 if qam_m else 2.0 / (sigma * sigma)  # schedule="bp": what makes the accumulated values true LLRs
     qam_scale = 1.0 / (2.0 * sigma * sigma)
@@ -572,13 +626,16 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
         """Decode y into D, leave the ACK in row N, return the iterations of every frame (int32 [F'])."""
         if layered:
             if bp:
-                r = LDPC_Decoder_BP_GPU(code, y, max_iter=maxIT, llr_scale=llr_scale, length=K, exit_mode=exit_mode, stop_rule=stop_rule, D=D)
+                r = LDPC_Decoder_BP_GPU(code, y, max_iter=maxIT, llr_scale=llr_scale, length=K, exit_mode=exit_mode, stop_rule=stop_rule, D=D,
+                                        want_app=osd)
             elif quant is not None:
-                r = LDPC_Decoder_Quant_GPU(code, y, quant, max_iter=maxIT, length=K, exit_mode=exit_mode, stop_rule=stop_rule, D=D)
+                r = LDPC_Decoder_Quant_GPU(code, y, quant, max_iter=maxIT, length=K, exit_mode=exit_mode, stop_rule=stop_rule, D=D, want_app=osd)
             else:
-                r = LDPC_Decoder_Layered_GPU(code, y, max_iter=maxIT, alpha=alpha, length=K, exit_mode=exit_mode, stop_rule=stop_rule, D=D)
+                r = LDPC_Decoder_Layered_GPU(code, y, max_iter=maxIT, alpha=alpha, length=K, exit_mode=exit_mode, stop_rule=stop_rule, D=D,
+                                             want_app=osd)
             if PN_Message and stop_rule != STOP_SYNDROME:
                 Syndrome(code, D, into_flag_row=True)
+            last_app[0] = r["app"]
             return r["iters"]
         r = LDPC_Decoder_GPU(code, y, max_iter=maxIT, length=K, exit_mode=exit_mode, kernel=kernel, D=D, alpha=alpha if norm else None)
         if PN_Message:
@@ -591,6 +648,8 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
     while True:
         SIM.num_Frames += F
         cnt.zero_()
+        if osd:
+            osd_cnt.zero_()
         if count:
             cw = PN_CodeWords(code, pn_seed, count, first_frame=batches * F + first, device=device, rate_match=rvs[0]) if PN_Message else None
             D = torch.empty((N + 1, count), dtype=torch.int32, device=device)
@@ -617,6 +676,7 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
                 else:
                     acc = AWGNChannel_RM_GPU(rm, my_seed, sigma, count, device=device, CodeWord=cw, short_llr=short_llr)
                 iters = decode(acc, D)
+                app = last_app[0]
             else:
                 if fading is not None:
                     RM_Combine(rm, llr, acc, done=D[N], short_llr=short_llr)
@@ -630,8 +690,11 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
                     ia = decode(Frames_Gather(acc, idx), Da)
                     Frames_Scatter(Da, idx, D)
                     Frames_Scatter(ia, idx, iters)
+                    if osd:
+                        Frames_Scatter(last_app[0], idx, app)
                 else:
                     iters = decode(acc, D)
+                    app = last_app[0]
             now = (D[N] != 0) & active
             wrong = ((D[:K] != cw[:K]) if cw is not None else (D[:K] != 0)).any(0)
             cnt[t] += now.sum()
@@ -641,6 +704,8 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
             acked |= now
         if count:
             cnt[2 * T] += (~acked).sum()
+            if osd:  # the flag row has served as the acknowledgement: from here on it says "codeword"
+                _osd_reprocess(code, D, app, cw, osd_cnt)
             if keep_D is not None:
                 keep_D.append(D)
         sharding.allreduce_counters(cnt, dist)
@@ -651,12 +716,16 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
         SIM.never_acked += c[2 * T]
         SIM.bits_sent += c[2 * T + 1]
         SIM.Total_Iteration += c[2 * T + 2]
+        if osd:
+            o = sharding.allreduce_counters(osd_cnt, dist).cpu().tolist()
+            SIM.osd_frames += o[0]
+            SIM.osd_correct += o[1]
         batches += 1
         errors = SIM.never_acked + sum(SIM.undetected)
         stop = errors >= leastErrorFrames and SIM.num_Frames >= leastTestFrames
         last = max_batches is not None and batches >= max_batches
         if rank == 0 and log and (stop or last):
-            log(format_harq_row(SIM, info_bits))
+            log(format_harq_row(SIM, info_bits) + ("  OSD %d %d" % (SIM.osd_frames, SIM.osd_correct) if osd else ""))
         if stop or last:
             return 1 if stop else 0
 

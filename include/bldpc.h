@@ -908,6 +908,54 @@ int bldpc_decode_erasure_ml_host(int J, int L, int Z, const int *H, const unsign
 int bldpc_erasure_ml_info(bldpc_code *code, int max_erased, int tier, int info[4]);
 int bldpc_erasure_ml_plan_host(int J, int L, int Z, const int *H, int max_erased, int tier, int info[4]);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * Ordered-statistics reprocessing of order 0 (OSD-0, "BP + OSD"): what the soft decoders lack after belief propagation.  A frame
+ * that ends with a non-zero syndrome usually has nearly all of its a-posteriori values right and the few wrong ones among the least
+ * reliable; this call trusts the most reliable independent positions and re-derives the rest from the parity checks, so it always
+ * returns a codeword.  It is the soft counterpart of "erasure decoding by elimination".
+ *   app      float [N][F]: any decoder's app, or a channel array (a quantised app converted to float, which is exact)
+ *   D_in     int32 [N+1][F] or NULL.  Only the frames whose flag, row N, is 0 are processed; with NULL every frame is.  A kept frame
+ *            is copied from D_in unchanged (all N+1 rows, whatever they hold), flips = -1, scanned = 0
+ *   D        int32 [N+1][F]; may be D_in itself (any other overlap is undefined).  A processed frame gets c in rows 0 .. N-1 and flag 1
+ *   flips, scanned  int32 [F] each, or NULL
+ *
+ * Per processed frame f, independent of any elimination order:
+ *   y[v] = app[v][f] < 0, so -0.0f gives 0, as in the decoders.
+ *   The reliability of v is key[v], the bit pattern of |app[v][f]| as uint32.  NaN is undefined, as elsewhere.
+ *   The order is the positions ascending by (key[v], v): ties in the value go to the lower position, so the order is total.
+ *   The least reliable basis B: walk the positions in that order; a position joins B iff its column of H is linearly independent
+ *   over GF(2) of the columns already in B.  |B| = rank(H); a weight-0 column never joins; a rank-deficient H is fine.
+ *   scanned is the 1-based place in the order of the last position that joined (0 when rank(H) = 0).
+ *   The result c has c[v] = y[v] outside B, and on B it is the unique solution of H c = 0: c = y xor e with e supported on B and
+ *   H_B e_B = H y, which is always consistent because B spans the column space.  By matroid duality the complement of B holds the
+ *   most reliable independent positions, so this is OSD-0.
+ *   flips is the weight of e.
+ *
+ * The device call: a list pass puts the frames with flag 0 on a list through a counter and copies the kept frames when D != D_in;
+ * persistent workgroups of k_osd take one listed frame each: gather the frame's column of app, sort the 64-bit keys (key << 32) | v in
+ * LDS (bitonic, over the next power of two P >= N, padded with all-ones keys), then eliminate with one barrier per position visited.
+ * The columns of H are not stored; the workgroup keeps the M x M record T of the row operations and the reduced syndrome T (H y) as
+ * one more bit per row, wpr = M / 32 + 1 words a row, and forms the reduced column of a position from T and the position's checks.
+ * It stops after rank(H) pivots (the rank is the one of the code's generator, bldpc_encoder_info, built on first use).
+ * tier: BLDPC_ML_LDS keeps the record in LDS: it fits when 4 M wpr bytes, the keys, 8 P bytes, two bitmaps of 4 ceil(N / 32) bytes and
+ * 4 M bytes of pivot positions are at most 162816 bytes.  BLDPC_ML_WORKSPACE keeps the record in a global slot owned by the workgroup,
+ * min(compute units, F, floor(1 GiB / record bytes)) slots a call, and the rest in LDS.  BLDPC_ML_AUTO takes LDS when it fits.
+ * bldpc_last_kernel names the tier that ran: "k_osd" or "k_osd_ws".  Asynchronous on `stream`; allocates nothing once its scratch has
+ * grown.
+ * BLDPC_EINVAL: a null code, app or D, F <= 0, an unknown tier.
+ * BLDPC_EUNSUPPORTED: a code built from an address table; M above 65536; keys, bitmaps and pivot positions above the LDS bound on
+ * either tier (8 P + 8 ceil(N / 32) + 4 M > 162816: PON_LDPC and J15_L30_Z1280 among the shipped matrices); BLDPC_ML_LDS when the
+ * record does not fit beside them; a workspace of which not even one slot fits in 1 GiB.
+ * The _host form is the definition (plain C++, one frame at a time, at most 16 threads) and has no size bound.
+ *
+ * bldpc_osd_info / bldpc_osd_plan_host: info[4] = LDS bytes of a workgroup on the tier taken (of the LDS tier when refused), threads,
+ * the tier taken (-1 when refused), workspace slots at F = 65536 (0 on the LDS tier); the second without a device, for the 256
+ * compute units of an MI355X. */
+int bldpc_decode_osd(bldpc_code *code, const float *app, const int *D_in, int F, int tier, int *D, int *flips, int *scanned, void *stream);
+int bldpc_decode_osd_host(int J, int L, int Z, const int *H, const float *app, const int *D_in, int F, int *D, int *flips, int *scanned);
+int bldpc_osd_info(bldpc_code *code, int tier, int info[4]);
+int bldpc_osd_plan_host(int J, int L, int Z, const int *H, int tier, int info[4]);
+
 const char *bldpc_last_error(void);
 
 #ifdef __cplusplus

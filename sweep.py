@@ -11,6 +11,7 @@
     python sweep.py binary --hard threshold --device-channel --per-frame --start 4 --stop 6 --step 0.5
     python sweep.py binary --erasure --bec 0.08,0.10,0.12,0.14 --pn-message --puncture 2208:2304 --iters 100
     python sweep.py binary --erasure --bec 0.12,0.14,0.16 --ml
+    python sweep.py binary --device-channel --per-frame --layered --alpha 0.75 --stop-rule syndrome --osd
     python sweep.py binary --device-channel --per-frame --layered --pn-message --qam 64 --interleave rowcol --fading 16 --harq 0:2160,2160:48,500:2300
     python sweep.py nb --pn-message --qam 64 --fading 16
     python sweep.py nb --device-channel --pn-message --puncture 88:96
@@ -110,6 +111,9 @@ def main():
                     "peeling leaves stuck (bldpc_decode_erasure_ml)")
     ap.add_argument("--ml-max-erased", type=int, default=0, metavar="E", help="--ml: frames with more than E positions still erased are left as "
                     "peeling left them (default 0: the number of check rows)")
+    ap.add_argument("--osd", action="store_true", help="binary --layered / --bp / --quant with the syndrome stop rule: ordered-statistics "
+                    "reprocessing of order 0 (bldpc_decode_osd) on the frames the decoder leaves with a non-zero syndrome; the row ends with the "
+                    "frames reprocessed and those of them that came out equal to the word sent")
     ap.add_argument("--alpha", type=float, default=1.0, help="binary: normalisation factor in (0, 1]; with --layered the layered decoder's, without it "
                     "normalised min-sum on the flooding decoders (with --fixed or --per-frame)")
     ap.add_argument("--stop-rule", choices=["prefix", "syndrome"], default=None,
@@ -213,6 +217,10 @@ def main():
             ap.error("--layered / --bp / --quant need a QC code and --fixed or --per-frame")
         if args.pn_message and args.per_frame and args.stop_rule == "prefix":
             ap.error("--pn-message --per-frame needs --stop-rule syndrome (the prefix rule tests for the all-zero word)")
+        if args.osd and (args.stop_rule or ("syndrome" if args.pn_message else "prefix")) != "syndrome":
+            ap.error("--osd needs --stop-rule syndrome (the frames to reprocess are those whose flag says 'no codeword')")
+    elif args.osd:
+        ap.error("--osd belongs to the binary sweep with --layered, --bp or --quant")
     elif args.stop_rule is not None or (args.alpha != 1.0 and args.which != "binary"):
         ap.error("--stop-rule belongs to the binary sweep with --layered, --bp or --quant, --alpha to the binary sweep")
     elif args.alpha != 1.0 and not (args.fixed or args.per_frame):
@@ -289,6 +297,8 @@ def main():
                     lay = dict(schedule="quant", quant=C.Quant(*quant), stop_rule=lay["stop_rule"])
                 except ValueError as e:
                     ap.error("--quant: %s" % e)
+            if args.osd:
+                lay["osd"] = True
         if args.hard is not None:
             lay = dict(schedule="hard", hard_rule=C.BF_GRADIENT if args.hard == "gradient" else C.BF_THRESHOLD)
         if bsc is not None:
@@ -338,8 +348,9 @@ def main():
                                                           "flooding alpha=%g" % args.alpha, "fixed iterations" if args.fixed else "per-frame early exit",
                                                           args.iters or (25 if rows else 50), args.batch, world,
                                                           ", random codewords (PN seed %d)" % args.pn_seed if args.pn_message else "")
-                      + (fade_words if fade is not None else ""))
-                print("# SNR      NTF  FER after each transmission ...  mean transmissions  throughput (information bits per bit sent)  AverIT")
+                      + (fade_words if fade is not None else "") + (", OSD-0 after the last transmission" if args.osd else ""))
+                print("# SNR      NTF  FER after each transmission ...  mean transmissions  throughput (information bits per bit sent)  AverIT"
+                      + ("  OSD reprocessed correct" if args.osd else ""))
             sweep_harq(code, rvs, args.start, args.stop, args.step, snrtype=1 if args.snrtype is None else args.snrtype, dist=dist,
                        Num_Frames_OneTime=args.batch, maxIT=args.iters or (25 if rows else 50),
                        exit_mode=C.EXIT_FIXED if args.fixed else C.EXIT_PER_FRAME, max_batches=args.max_batches, PN_Message=1 if args.pn_message else 0,
@@ -365,8 +376,8 @@ def main():
                   "fixed iterations" if args.fixed else ("per-frame early exit" if args.per_frame else "batch-global early exit"),
                   args.iters or (25 if rows else 30 if args.hard is not None else 50), args.batch, world,
                   ", random codewords (PN seed %d, K'=%d), syndrome flag" % (args.pn_seed, code.K_info) if args.pn_message else "")
-                  + (fade_words if fade is not None else ""))
-            print("# SNR      NTF   NEF         FER         BER  AverIT       FER_F      FER_A")
+                  + (fade_words if fade is not None else "") + (", OSD-0 on the frames left with a non-zero syndrome" if args.osd else ""))
+            print("# SNR      NTF   NEF         FER         BER  AverIT       FER_F      FER_A" + ("  OSD reprocessed correct" if args.osd else ""))
         sweep(code, args.start, args.stop, args.step, snrtype=1 if args.qam == 2 else 0, dist=dist, Num_Frames_OneTime=args.batch, maxIT=args.iters or (25 if rows else 30 if args.hard is not None else 50),
               exit_mode=C.EXIT_FIXED if args.fixed else (C.EXIT_PER_FRAME if args.per_frame else C.EXIT_BATCH_GLOBAL), max_batches=args.max_batches, displayStep=10 ** 12, device_channel=args.device_channel,
               PN_Message=1 if args.pn_message else 0, pn_seed=args.pn_seed, log=print if rank == 0 else None, **lay, **mod, **fad)
