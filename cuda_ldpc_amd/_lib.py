@@ -146,6 +146,11 @@ lib.bldpc_decode_osd.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_v
 lib.bldpc_decode_osd_host.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]
 lib.bldpc_osd_info.argtypes = [c_void_p, c_int, c_void_p]
 lib.bldpc_osd_plan_host.argtypes = [c_int, c_int, c_int, c_void_p, c_int, c_void_p]
+lib.bldpc_decode_osd_w.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+lib.bldpc_decode_osd_w_host.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p]
+lib.bldpc_osd_w_info.argtypes = [c_void_p, c_int, c_int, c_void_p]
+lib.bldpc_osd_w_plan_host.argtypes = [c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]
 lib.bldpc_rm_select_bits.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p]
 lib.bldpc_rm_recover_bits.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]
 lib.bldpc_rm_select_bits_host.argtypes = [c_void_p, c_void_p, c_int, c_void_p]

@@ -211,11 +211,15 @@ class BinaryCode:
         check(lib.bldpc_erasure_info(self._h, _np_ptr(d)), "bldpc_erasure_info")
         return dict(lds_bytes=int(d[0]), threads=int(d[1]), frames_per_wg=int(d[2]), fits=int(d[0]) <= ERASURE_LDS_BOUND)
 
-    def osd_info(self, tier="auto"):
+    def osd_info(self, tier="auto", order=0):
         """bldpc_osd_info: dict(lds_bytes, threads, tier, slots) of the reprocessing kernel k_osd for this code, without a launch; slots
-        is the workspace tier's at F = 65536.  Builds the code's generator on first use, for the rank of H."""
+        is the workspace tier's at F = 65536.  Builds the code's generator on first use, for the rank of H.  order >= 1: bldpc_osd_w_info,
+        the same of k_osd_w at that order."""
         d = np.zeros(4, np.int32)
-        check(lib.bldpc_osd_info(self._h, _ml_tier(tier), _np_ptr(d)), "bldpc_osd_info")
+        if order:
+            check(lib.bldpc_osd_w_info(self._h, _ml_tier(tier), int(order), _np_ptr(d)), "bldpc_osd_w_info")
+        else:
+            check(lib.bldpc_osd_info(self._h, _ml_tier(tier), _np_ptr(d)), "bldpc_osd_info")
         return _osd_info(d)
 
     def erasure_ml_info(self, max_erased=0, tier="auto"):
@@ -943,7 +947,7 @@ def _osd_info(d):
     return dict(lds_bytes=int(d[0]), threads=int(d[1]), tier={1: "lds", 2: "workspace"}.get(int(d[2])), slots=int(d[3]))
 
 
-def LDPC_Decoder_OSD_GPU(code, app, D=None, tier="auto", out=None, stream=None):
+def LDPC_Decoder_OSD_GPU(code, app, D=None, tier="auto", out=None, stream=None, order=0, lam=0, want_metric=False):
     """bldpc_decode_osd: ordered-statistics reprocessing of order 0 (semantics in include/bldpc.h): per processed frame the least
     reliable basis of H's columns is found by elimination in the order of |app|, the hard decisions of app are kept outside it and
     re-derived from the parity checks on it, so the frame comes out a codeword with flag 1; one workgroup a frame (k_osd, or k_osd_ws
@@ -951,7 +955,12 @@ def LDPC_Decoder_OSD_GPU(code, app, D=None, tier="auto", out=None, stream=None):
     decoder's D, CUDA int32 [N+1, F]: the frames whose flag row is 0 are processed, the others kept; None processes every frame.
     out: where the result goes, CUDA int32 [N+1, F]; default D itself (in place), or a new tensor when D is None.
     Returns (D, flips, scanned): the result, and int32 [F] each the number of hard decisions changed (-1 on a kept frame) and the
-    1-based place in the order of reliability of the last basis position (0 on a kept frame)."""
+    1-based place in the order of reliability of the last basis position (0 on a kept frame).
+    order = 1 or 2 (bldpc_decode_osd_w, kernels k_osd_w / k_osd_w_ws): also every single position outside the basis flipped and, at
+    order 2, every pair among the first `lam` of them in the order of reliability; the candidate of least soft metric is the result.
+    Returns (D, flips, scanned, picked, metric): picked int32 [2, F], the positions flipped outside the basis or -1 (-1, -1 on a kept
+    frame), metric float32 [F], the metric of the candidate chosen (not written on a kept frame).  want_metric=True takes order 0
+    through the same call, for its metric."""
     if not (torch.is_tensor(app) and app.is_cuda and app.dtype == torch.float32 and app.is_contiguous() and app.dim() == 2
             and app.shape[0] == code.N and app.shape[1] > 0):
         raise ValueError("app must be a contiguous CUDA float32 tensor [N=%d, F]" % code.N)
@@ -966,14 +975,21 @@ def LDPC_Decoder_OSD_GPU(code, app, D=None, tier="auto", out=None, stream=None):
     flips = torch.empty(F, dtype=torch.int32, device=dev)
     scanned = torch.empty(F, dtype=torch.int32, device=dev)
     st = ctypes.c_void_p((stream or torch.cuda.current_stream(dev)).cuda_stream)
+    if order or want_metric:
+        picked = torch.empty((2, F), dtype=torch.int32, device=dev)
+        metric = torch.empty(F, dtype=torch.float32, device=dev)
+        check(lib.bldpc_decode_osd_w(code._h, _dev_ptr(app), _dev_ptr(D), F, t, int(order), int(lam), _dev_ptr(out), _dev_ptr(flips),
+                                     _dev_ptr(scanned), _dev_ptr(picked), _dev_ptr(metric), st), "LDPC_Decoder_OSD_GPU")
+        return out, flips, scanned, picked, metric
     check(lib.bldpc_decode_osd(code._h, _dev_ptr(app), _dev_ptr(D), F, t, _dev_ptr(out), _dev_ptr(flips), _dev_ptr(scanned), st), "LDPC_Decoder_OSD_GPU")
     return out, flips, scanned
 
 
-def osd_host(H, J, L, Z, app, D=None):
+def osd_host(H, J, L, Z, app, D=None, order=0, lam=0, want_metric=False):
     """bldpc_decode_osd_host: ordered-statistics reprocessing on the host (no device), the statement of its semantics.  app: float32
     [N, F]; D: int32 [N+1, F] or None, as in LDPC_Decoder_OSD_GPU (it is not written).  Returns (D int32 [N+1, F], flips int32 [F],
-    scanned int32 [F])."""
+    scanned int32 [F]); with order >= 1 or want_metric (bldpc_decode_osd_w_host) also picked int32 [2, F] and metric float32 [F], which
+    is zero on a kept frame."""
     H = np.ascontiguousarray(H, np.int32)
     if H.size != J * L:
         raise ValueError("H must hold J*L shifts")
@@ -988,18 +1004,26 @@ def osd_host(H, J, L, Z, app, D=None):
             raise ValueError("D must be an int32 array [N+1=%d, F=%d]" % (N + 1, F))
     out = np.zeros((N + 1, F), np.int32)
     flips, scanned = np.zeros(F, np.int32), np.zeros(F, np.int32)
+    if order or want_metric:
+        picked, metric = np.zeros((2, F), np.int32), np.zeros(F, np.float32)
+        check(lib.bldpc_decode_osd_w_host(J, L, Z, _np_ptr(H), _np_ptr(app), None if D is None else _np_ptr(D), F, int(order), int(lam), _np_ptr(out),
+                                          _np_ptr(flips), _np_ptr(scanned), _np_ptr(picked), _np_ptr(metric)), "osd_host")
+        return out, flips, scanned, picked, metric
     check(lib.bldpc_decode_osd_host(J, L, Z, _np_ptr(H), _np_ptr(app), None if D is None else _np_ptr(D), F, _np_ptr(out), _np_ptr(flips),
                                     _np_ptr(scanned)), "osd_host")
     return out, flips, scanned
 
 
-def osd_plan_host(H, J, L, Z, tier="auto"):
+def osd_plan_host(H, J, L, Z, tier="auto", order=0):
     """bldpc_osd_plan_host: what BinaryCode.osd_info returns, from the block matrix alone (no device; the 256 compute units of an
-    MI355X).  A refusal (LdpcError) is the one the device call would make."""
+    MI355X).  A refusal (LdpcError) is the one the device call would make.  order >= 1: bldpc_osd_w_plan_host."""
     H = np.ascontiguousarray(H, np.int32)
     if H.size != J * L:
         raise ValueError("H must hold J*L shifts")
     d = np.zeros(4, np.int32)
+    if order:
+        check(lib.bldpc_osd_w_plan_host(J, L, Z, _np_ptr(H), _ml_tier(tier), int(order), _np_ptr(d)), "osd_plan_host")
+        return _osd_info(d)
     check(lib.bldpc_osd_plan_host(J, L, Z, _np_ptr(H), _ml_tier(tier), _np_ptr(d)), "osd_plan_host")
     return _osd_info(d)
 

@@ -1,5 +1,6 @@
-// bldpc_osd.hip -- ordered-statistics reprocessing of order 0 (include/bldpc.h, "ordered-statistics reprocessing"): the C entry points
-// over the host statement of bldpc_osd_host.hpp and the device entry point over the kernels of bldpc_osd_kernel.hpp.
+// bldpc_osd.hip -- ordered-statistics reprocessing (include/bldpc.h, "ordered-statistics reprocessing" of order 0 and "reprocessing of
+// order 1 and 2"): the C entry points over the host statements of bldpc_osd_host.hpp and bldpc_osd_w_host.hpp and the device entry
+// points over the kernels of bldpc_osd_kernel.hpp.
 #include "../../include/bldpc.h"
 
 #include <cstdlib>
@@ -7,6 +8,7 @@
 #include "bldpc_layer_plan.hpp"
 #include "bldpc_osd_host.hpp"
 #include "bldpc_osd_kernel.hpp"
+#include "bldpc_osd_w_host.hpp"
 #include "common.hpp"
 
 using namespace cldpc;
@@ -18,6 +20,17 @@ extern "C" int bldpc_decode_osd_host(int J, int L, int Z, const int *H, const fl
 }
 
 extern "C" int bldpc_osd_plan_host(int J, int L, int Z, const int *H, int tier, int info[4]) { return osd::plan_host(J, L, Z, H, tier, info); }
+
+extern "C" int bldpc_decode_osd_w_host(int J, int L, int Z, const int *H, const float *app, const int *D_in, int F, int order, int lambda, int *D,
+                                       int *flips, int *scanned, int *picked, float *metric)
+{
+    return osd::decode_w_host(J, L, Z, H, app, D_in, F, order, lambda, D, flips, scanned, picked, metric);
+}
+
+extern "C" int bldpc_osd_w_plan_host(int J, int L, int Z, const int *H, int tier, int order, int info[4])
+{
+    return osd::plan_w_host(J, L, Z, H, tier, order, info);
+}
 
 // ------------------------------------------------------------------------------------------------------ code state
 namespace {
@@ -40,7 +53,8 @@ struct OsdPlan : LayerPlan { // d_edges / d_rowptr: the rows
 
 // As the plan of k_er_ml (bldpc_erasure_ml.hip): the same tables and a slot of its own.  The shape's refusal is made per call, by
 // osd::plan_of, before anything here is built.
-int plan_of(bldpc_code *code, const char *who, int tier, int F, LayerView &v, OsdPlan *&p, osd::Plan &pl)
+// order: -1 for k_osd, else the order asked of k_osd_w.
+int plan_of(bldpc_code *code, const char *who, int tier, int F, LayerView &v, OsdPlan *&p, osd::Plan &pl, int order = -1)
 {
     if (!code) return fail(BLDPC_EINVAL, "%s: null code", who);
     v = layer_view(code, kSlotOsd);
@@ -57,7 +71,11 @@ int plan_of(bldpc_code *code, const char *who, int tier, int F, LayerView &v, Os
         CLDPC_HIP(hipDeviceGetAttribute(&p->units, hipDeviceAttributeMultiprocessorCount, dev), BLDPC_EHIP);
         if (const char *s = getenv("BLDPC_OSD_SLOTS")) p->slot_cap = std::max(atoi(s), 0);
     }
-    if ((r = osd::plan_of(who, v.J, v.L, v.Z, tier, p->units, p->slot_cap, F, pl))) return r;
+    if (order < 0)
+        r = osd::plan_of(who, v.J, v.L, v.Z, tier, p->units, p->slot_cap, F, pl);
+    else
+        r = osd::plan_of_w(who, v.J, v.L, v.Z, tier, order, p->units, p->slot_cap, F, pl);
+    if (r) return r;
     if (p->built) return BLDPC_OK;
     bf::Tables t;
     if ((r = bf::build_tables(who, v.J, v.L, v.Z, v.H, t))) return r;
@@ -66,8 +84,10 @@ int plan_of(bldpc_code *code, const char *who, int tier, int F, LayerView &v, Os
     if (!p->d_rowptr && (r = upload((void **)&p->d_rowptr, t.rows.rowptr.data(), t.rows.rowptr.size() * sizeof(int)))) return r;
     if (!p->d_cedges && (r = upload((void **)&p->d_cedges, t.cedges.data(), t.cedges.size() * sizeof(int)))) return r;
     if (!p->d_colptr && (r = upload((void **)&p->d_colptr, t.colptr.data(), t.colptr.size() * sizeof(int)))) return r;
-    CLDPC_HIP(hipFuncSetAttribute((const void *)k_osd_frames<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)layer::kLdsBytes), BLDPC_EHIP);
-    CLDPC_HIP(hipFuncSetAttribute((const void *)k_osd_frames<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)layer::kLdsBytes), BLDPC_EHIP);
+    CLDPC_HIP(hipFuncSetAttribute((const void *)k_osd_frames<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)layer::kLdsBytes), BLDPC_EHIP);
+    CLDPC_HIP(hipFuncSetAttribute((const void *)k_osd_frames<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)layer::kLdsBytes), BLDPC_EHIP);
+    CLDPC_HIP(hipFuncSetAttribute((const void *)k_osd_frames<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)layer::kLdsBytes), BLDPC_EHIP);
+    CLDPC_HIP(hipFuncSetAttribute((const void *)k_osd_frames<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)layer::kLdsBytes), BLDPC_EHIP);
     p->built = true;
     return BLDPC_OK;
 }
@@ -86,22 +106,20 @@ extern "C" int bldpc_osd_info(bldpc_code *code, int tier, int info[4])
     return r;
 }
 
-extern "C" int bldpc_decode_osd(bldpc_code *code, const float *app, const int *D_in, int F, int tier, int *D, int *flips, int *scanned, void *stream)
+namespace {
+
+// The launches of both device entry points.  W: k_osd_w, with the search's arguments in `a`.
+template <bool W> int launch(const char *who, bldpc_code *code, int tier, int F, int order, OsdArgs a, void *stream)
 {
-    const char *who = "bldpc_decode_osd";
-    if (!code) return fail(BLDPC_EINVAL, "%s: null code", who);
-    int r = osd::check_args(who, app, F, tier, D);
-    if (r) return r;
     LayerView v;
     OsdPlan *p = nullptr;
     osd::Plan pl;
-    if ((r = plan_of(code, who, tier, F, v, p, pl))) return r;
+    int r;
+    if ((r = plan_of(code, who, tier, F, v, p, pl, W ? order : -1))) return r;
     const bool ws = pl.tier == BLDPC_ML_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     CLDPC_HIP(p->list.reserve(((size_t)F + 2) * sizeof(int)), BLDPC_ENOMEM);
     if (ws) CLDPC_HIP(p->ws.reserve((size_t)pl.slots * pl.matrix), BLDPC_ENOMEM);
-    OsdArgs a;
-    a.app = app; a.din = D_in; a.out = D; a.flips = flips; a.scanned = scanned;
     a.cnt = (int *)p->list.p; a.list = a.cnt + 2;
     a.ws = (unsigned *)p->ws.p;
     a.edges = (const int2 *)p->d_edges; a.rowptr = p->d_rowptr;
@@ -110,15 +128,56 @@ extern "C" int bldpc_decode_osd(bldpc_code *code, const float *app, const int *D
     a.wpr = pl.wpr; a.P = pl.P; a.rank = p->rank;
     CLDPC_HIP(hipMemsetAsync(a.cnt, 0, 2 * sizeof(int), st), BLDPC_EHIP);
     const size_t elems = (size_t)(v.N + 1) * F;
-    hipLaunchKernelGGL(k_osd_list, dim3((unsigned)std::min<size_t>((elems + 255) / 256, 8192)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_osd_list<W>, dim3((unsigned)std::min<size_t>((elems + 255) / 256, 8192)), dim3(256), 0, st, a);
     if (ws) {
-        hipLaunchKernelGGL(k_osd_frames<true>, dim3((unsigned)pl.slots), dim3((unsigned)pl.threads), pl.side, st, a);
+        hipLaunchKernelGGL((k_osd_frames<true, W>), dim3((unsigned)pl.slots), dim3((unsigned)pl.threads), pl.side, st, a);
     } else { // as many workgroups as stay resident, each taking frames until the list is used up
         const size_t lds = pl.matrix + pl.side;
         const int per_unit = (int)std::max<size_t>(1, std::min<size_t>({layer::kLdsBytes / lds, (size_t)(2048 / pl.threads), 8}));
-        hipLaunchKernelGGL(k_osd_frames<false>, dim3((unsigned)std::min<long long>(F, (long long)p->units * per_unit)), dim3((unsigned)pl.threads),
+        hipLaunchKernelGGL((k_osd_frames<false, W>), dim3((unsigned)std::min<long long>(F, (long long)p->units * per_unit)), dim3((unsigned)pl.threads),
                            lds, st, a);
     }
-    p->name = ws ? "k_osd_ws" : "k_osd";
+    p->name = W ? (ws ? "k_osd_w_ws" : "k_osd_w") : (ws ? "k_osd_ws" : "k_osd");
     return layer_end(v, *p);
+}
+
+} // namespace
+
+extern "C" int bldpc_decode_osd(bldpc_code *code, const float *app, const int *D_in, int F, int tier, int *D, int *flips, int *scanned, void *stream)
+{
+    const char *who = "bldpc_decode_osd";
+    if (!code) return fail(BLDPC_EINVAL, "%s: null code", who);
+    int r = osd::check_args(who, app, F, tier, D);
+    if (r) return r;
+    OsdArgs a;
+    a.app = app; a.din = D_in; a.out = D; a.flips = flips; a.scanned = scanned;
+    return launch<false>(who, code, tier, F, 0, a, stream);
+}
+
+// ------------------------------------------------------------------------------------------------------ order 1 and 2
+extern "C" int bldpc_osd_w_info(bldpc_code *code, int tier, int order, int info[4])
+{
+    const char *who = "bldpc_osd_w_info";
+    if (!code || !info) return fail(BLDPC_EINVAL, "%s: null argument", who);
+    LayerView v;
+    OsdPlan *p = nullptr;
+    osd::Plan pl;
+    int r = osd::check_order(who, order, 0);
+    if (!r) r = plan_of(code, who, tier, 65536, v, p, pl, order);
+    osd::plan_info(pl, info);
+    return r;
+}
+
+extern "C" int bldpc_decode_osd_w(bldpc_code *code, const float *app, const int *D_in, int F, int tier, int order, int lambda, int *D, int *flips,
+                                  int *scanned, int *picked, float *metric, void *stream)
+{
+    const char *who = "bldpc_decode_osd_w";
+    if (!code) return fail(BLDPC_EINVAL, "%s: null code", who);
+    int r = osd::check_args(who, app, F, tier, D);
+    if (r) return r;
+    if ((r = osd::check_order(who, order, lambda))) return r;
+    OsdArgs a;
+    a.app = app; a.din = D_in; a.out = D; a.flips = flips; a.scanned = scanned;
+    a.picked = picked; a.metric = metric; a.order = order; a.lambda = lambda;
+    return launch<true>(who, code, tier, F, order, a, stream);
 }

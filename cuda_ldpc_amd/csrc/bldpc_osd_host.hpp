@@ -6,6 +6,7 @@
 // columns in the order of reliability and the syndrome of the hard decisions behind them, and a Gauss-Jordan pass from the left over it.
 // The kernel never forms that matrix (it keeps the record of the row operations); the two share the edge walk and nothing else.
 // Nothing here calls HIP: the stand-alone program of tests/cpp includes it under the host sanitizers.
+// bldpc_osd_w_host.hpp builds the statement of order 1 and 2 on eliminate_frame and plan_of.
 #pragma once
 #include "../../include/bldpc.h"
 
@@ -36,8 +37,10 @@ inline int check_args(const char *who, const float *app, int F, int tier, const 
 // Columns are taken from the left: a column with a one in a row that is no pivot row yet is independent of the pivot columns before it,
 // joins the basis and is cleared from every other row.  After the pass row k of the first `rank` rows reads e[basis[k]] = its
 // last bit, because every other basis column is zero in it and e is zero outside the basis.
-inline void reprocess_frame(const bf::Tables &t, int J, int L, int Z, const float *app, int F, int f, std::vector<uint64_t> &keys,
-                            std::vector<uint64_t> &A, std::vector<int> &place, std::vector<int> &c, int &flips, int &scanned)
+// eliminate_frame leaves c = y, the reduced matrix (the reduced column of every place, pivot or not, and the reduced syndrome) and the
+// basis in the order its positions joined; reprocess_frame then takes e on the basis from the syndrome column.
+inline void eliminate_frame(const bf::Tables &t, int J, int L, int Z, const float *app, int F, int f, std::vector<uint64_t> &keys,
+                            std::vector<uint64_t> &A, std::vector<int> &place, std::vector<int> &c, std::vector<int> &basis, int &scanned)
 {
     const int N = L * Z, M = J * Z;
     const layer::RowTable &rt = t.rows;
@@ -66,7 +69,7 @@ inline void reprocess_frame(const bf::Tables &t, int J, int L, int Z, const floa
         }
     int rank = 0;
     scanned = 0;
-    std::vector<int> basis;
+    basis.clear();
     for (int i = 0; i < N && rank < M; i++) {
         const size_t w0 = (size_t)i / 64;
         const uint64_t bit = (uint64_t)1 << (i & 63);
@@ -84,6 +87,16 @@ inline void reprocess_frame(const bf::Tables &t, int J, int L, int Z, const floa
         scanned = i + 1;
         rank++;
     }
+}
+
+inline void reprocess_frame(const bf::Tables &t, int J, int L, int Z, const float *app, int F, int f, std::vector<uint64_t> &keys,
+                            std::vector<uint64_t> &A, std::vector<int> &place, std::vector<int> &c, int &flips, int &scanned)
+{
+    const int N = L * Z;
+    const size_t wpr = (size_t)N / 64 + 1;
+    std::vector<int> basis;
+    eliminate_frame(t, J, L, Z, app, F, f, keys, A, place, c, basis, scanned);
+    const int rank = (int)basis.size();
     flips = 0;
     for (int k = 0; k < rank; k++)
         if ((A[(size_t)k * wpr + N / 64] >> (N & 63)) & 1u) {

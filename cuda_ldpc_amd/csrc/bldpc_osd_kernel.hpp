@@ -1,6 +1,6 @@
 // bldpc_osd_kernel.hpp -- the device side of ordered-statistics reprocessing (include/bldpc.h): k_osd_list (the frames to reprocess,
 // the kept frames copied) and k_osd / k_osd_ws (one workgroup per listed frame, the record of the row operations in LDS or in a global
-// slot of the workgroup).
+// slot of the workgroup); k_osd_w / k_osd_w_ws are the same frame body with the candidate search of order 1 and 2 after the last pivot.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,12 +23,17 @@ struct OsdArgs {
     const int2 *cedges;  // (j*Z, shift) by block column
     const int *colptr;   // [L+1]
     int F, J, L, Z, N, M, wpr, P, rank; // P: the power of two the sort runs over; rank of H
+    // k_osd_w only
+    int *picked = nullptr;   // [2][F] or nullptr
+    float *metric = nullptr; // [F] or nullptr
+    int order = 0, lambda = 0;
 };
 
 // ---------------------------------------------------------------------------------------------------------------- the list pass
 // A thread per element of D, striding: the elements of the flag row put their frame on the list through the call's counter or write
-// flips = -1, scanned = 0; with D apart from D_in every element of a kept frame is copied.
-__global__ __launch_bounds__(256) void k_osd_list(const OsdArgs a)
+// flips = -1, scanned = 0 (W, the list pass of k_osd_w: and picked = -1, -1); with D apart from D_in every element of a kept frame is
+// copied.
+template <bool W> __global__ __launch_bounds__(256) void k_osd_list(const OsdArgs a)
 {
     const size_t total = (size_t)(a.N + 1) * a.F, flags = (size_t)a.N * a.F;
     const bool copy = a.din && a.din != a.out;
@@ -40,10 +45,73 @@ __global__ __launch_bounds__(256) void k_osd_list(const OsdArgs a)
         if (kept) {
             if (a.flips) a.flips[f] = -1;
             if (a.scanned) a.scanned[f] = 0;
+            if constexpr (W)
+                if (a.picked) a.picked[f] = a.picked[(size_t)a.F + f] = -1;
         } else {
             a.list[atomicAdd(&a.cnt[0], 1)] = f;
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the search
+// What k_osd_w adds after the last pivot (include/bldpc.h, "reprocessing of order 1 and 2").  The elimination has left, in the sorted
+// keys, a pivot's entry as (|app| bits << 32) | 0x80000000 | its row, every other place as it was, so a walk over the places meets
+// the pivots in joining order with their weights beside them and tells the positions outside B by bit 31.
+__device__ __forceinline__ unsigned osd_metric_bits(float m) { return m != m ? 0x7fffffffu : __float_as_uint(m); }
+
+// Row r of the reduced column of position v: the XOR of T[r][c] over the checks c of v.
+__device__ __forceinline__ unsigned osd_reduced(const OsdArgs &a, const unsigned *A, int v, int r)
+{
+    const int Z = a.Z, l = v / Z, t = v - l * Z;
+    const int e1 = a.colptr[l + 1];
+    unsigned x = 0;
+    for (int k = a.colptr[l]; k < e1; k++) {
+        const int2 ed = a.cedges[k];
+        int c = t - ed.y;
+        c += c < 0 ? Z : 0;
+        c += ed.x;
+        x ^= A[(size_t)(c >> 5) * a.M + r] >> (c & 31);
+    }
+    return x;
+}
+
+// e at the pivot of row r for the candidate of positions v1, v2 (-1: absent)
+__device__ __forceinline__ unsigned osd_e_bit(const OsdArgs &a, const unsigned *A, int v1, int v2, int r)
+{
+    unsigned x = A[(size_t)(a.M >> 5) * a.M + r] >> (a.M & 31);
+    if (v1 >= 0) x ^= osd_reduced(a, A, v1, r);
+    if (v2 >= 0) x ^= osd_reduced(a, A, v2, r);
+    return x & 1u;
+}
+
+// One candidate, by a whole wave: the places p1 < p2 of S (-1: absent).  64 places a step: a lane whose place is a pivot forms e there,
+// a ballot gives the ones in joining order, and every lane adds their weights in that order, as the definition sums them.  Every term
+// is non-negative, so a partial sum above the metric of `best` ends the candidate: the result is then ~0, which wins nothing.
+// Returns (metric bits << 32) | (p1 + 1) << 16 | (p2 + 1): places are below 2^14, because the keys fit in LDS.
+__device__ unsigned long long osd_candidate(const OsdArgs &a, const unsigned long long *keys, const unsigned *A, int last, int lane, int p1, int p2,
+                                            unsigned long long best)
+{
+    const int v1 = p1 >= 0 ? __builtin_amdgcn_readfirstlane((int)(unsigned)keys[p1]) : -1;
+    const int v2 = p2 >= 0 ? __builtin_amdgcn_readfirstlane((int)(unsigned)keys[p2]) : -1;
+    const unsigned bound = (unsigned)(best >> 32);
+    float m = 0.0f;
+    for (int i0 = 0; i0 < last; i0 += 64) {
+        const int i = i0 + lane;
+        unsigned bit = 0;
+        if (i < last) {
+            const unsigned lo = (unsigned)keys[i];
+            if (lo & 0x80000000u) bit = osd_e_bit(a, A, v1, v2, (int)(lo & 0x7fffffffu));
+        }
+        unsigned long long ones = __ballot(bit != 0);
+        while (ones) {
+            m += __uint_as_float((unsigned)(keys[i0 + __ffsll((long long)ones) - 1] >> 32));
+            ones &= ones - 1;
+        }
+        if (osd_metric_bits(m) > bound) return ~0ull;
+    }
+    if (p1 >= 0) m += __uint_as_float((unsigned)(keys[p1] >> 32));
+    if (p2 >= 0) m += __uint_as_float((unsigned)(keys[p2] >> 32));
+    return ((unsigned long long)osd_metric_bits(m) << 32) | ((unsigned long long)(p1 + 1) << 16) | (unsigned long long)(p2 + 1);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the frame
@@ -57,7 +125,15 @@ __global__ __launch_bounds__(256) void k_osd_list(const OsdArgs a)
 // goes through sh_piv, three slots in rotation; after it the pivot row is read by all and written by none until the next barrier.
 // Every other row that has the column takes the pivot row, pivot rows of earlier positions included, so after the last pivot a pivot
 // row reads "e at my position = my syndrome bit".
-template <bool WS> __global__ __launch_bounds__(1024) void k_osd_frames(const OsdArgs a)
+//
+// W (k_osd_w): the pivot's owner also leaves the pivot's row in the pivot's entry of the keys, and after the last pivot the waves share
+// the candidates: a wave takes the places wave, wave + waves, ... outside B as singles and, below the place after the lambda-th such
+// position, each of them with every later one as a pair; it keeps the least key it met and the workgroup takes the least of those by
+// an LDS atomicMin.  The least key is the same whoever evaluates what first, because the triple is a total order.  fp32 addition of
+// non-negative terms is monotone, so a candidate's metric is at least the sum of the weights of S alone: a wave leaves a loop at the
+// first place at which that sum is above its best metric, since the weights ascend with the place.  e of the winner is then formed
+// once, a thread per place.
+template <bool WS, bool W> __global__ __launch_bounds__(1024) void k_osd_frames(const OsdArgs a)
 {
     extern __shared__ __align__(16) unsigned long long osd_lds[];
     __shared__ int sh_piv[3];
@@ -171,6 +247,7 @@ template <bool WS> __global__ __launch_bounds__(1024) void k_osd_frames(const Os
                     used |= 1ull << q;
                     pivpos[r] = v;
                     sh_last = i + 1;
+                    if constexpr (W) ((unsigned *)keys)[2 * i] = 0x80000000u | (unsigned)p; // every thread read keys[i] before the barrier
                     continue;
                 }
                 if (!((has >> q) & 1ull)) continue;
@@ -181,11 +258,70 @@ template <bool WS> __global__ __launch_bounds__(1024) void k_osd_frames(const Os
 
         // e on the basis: a pivot row's syndrome bit, at the position that made it a pivot row
         int fl = 0;
-        for (int r = tid; r < M; r += T) {
-            const int v = pivpos[r];
-            if (v >= 0 && (A[(size_t)sw * M + r] & sbit)) {
-                atomicOr(&eb[v >> 5], 1u << (v & 31));
-                fl++;
+        if constexpr (W) {
+            __shared__ unsigned long long sh_best;
+            const int last = sh_last, wave = tid >> 6, waves = T >> 6;
+            if (tid == 0) sh_best = ~0ull;
+            int lim = 0; // pairs: both places below it
+            if (a.order >= 2 && a.lambda > 0) {
+                lim = N;
+                int seen = 0;
+                for (int i0 = 0; i0 < N; i0 += 64) {
+                    const int i = i0 + lane;
+                    unsigned long long out = __ballot(i < N && !((unsigned)keys[i] & 0x80000000u));
+                    const int here = __popcll(out);
+                    if (seen + here >= a.lambda) {
+                        for (int skip = a.lambda - seen - 1; skip > 0; skip--) out &= out - 1;
+                        lim = i0 + __ffsll((long long)out);
+                        break;
+                    }
+                    seen += here;
+                }
+            }
+            unsigned long long best = osd_candidate(a, keys, A, last, lane, -1, -1, ~0ull);
+            if (a.order >= 1)
+                for (int i = wave; i < N; i += waves) { // a metric is at least the sum over S, and the weights ascend with the place
+                    const unsigned long long ki = keys[i];
+                    if ((unsigned)ki & 0x80000000u) continue;
+                    const float wi = __uint_as_float((unsigned)(ki >> 32));
+                    if (osd_metric_bits(wi) > (unsigned)(best >> 32)) break; // nor can any later candidate of this wave win
+                    best = min(best, osd_candidate(a, keys, A, last, lane, i, -1, best));
+                    for (int j = i + 1; j < lim; j++) {
+                        const unsigned long long kj = keys[j];
+                        if ((unsigned)kj & 0x80000000u) continue;
+                        if (osd_metric_bits(wi + __uint_as_float((unsigned)(kj >> 32))) > (unsigned)(best >> 32)) break;
+                        best = min(best, osd_candidate(a, keys, A, last, lane, i, j, best));
+                    }
+                }
+            __syncthreads();
+            if (lane == 0) atomicMin(&sh_best, best);
+            __syncthreads();
+            const unsigned long long win = sh_best;
+            const int p1 = (int)((win >> 16) & 0xffffu) - 1, p2 = (int)(win & 0xffffu) - 1;
+            const int v1 = p1 >= 0 ? (int)(unsigned)keys[p1] : -1, v2 = p2 >= 0 ? (int)(unsigned)keys[p2] : -1;
+            for (int i = tid; i < last; i += T) {
+                const unsigned lo = (unsigned)keys[i];
+                if (!(lo & 0x80000000u)) continue;
+                const int r = (int)(lo & 0x7fffffffu);
+                if (osd_e_bit(a, A, v1, v2, r)) {
+                    const int v = pivpos[r];
+                    atomicOr(&eb[v >> 5], 1u << (v & 31));
+                    fl++;
+                }
+            }
+            if (tid == 0) {
+                if (v1 >= 0) atomicOr(&eb[v1 >> 5], 1u << (v1 & 31)), fl++;
+                if (v2 >= 0) atomicOr(&eb[v2 >> 5], 1u << (v2 & 31)), fl++;
+                if (a.picked) a.picked[f] = v1, a.picked[(size_t)F + f] = v2;
+                if (a.metric) a.metric[f] = __uint_as_float((unsigned)(win >> 32));
+            }
+        } else {
+            for (int r = tid; r < M; r += T) {
+                const int v = pivpos[r];
+                if (v >= 0 && (A[(size_t)sw * M + r] & sbit)) {
+                    atomicOr(&eb[v >> 5], 1u << (v & 31));
+                    fl++;
+                }
             }
         }
 #pragma unroll

@@ -41,10 +41,15 @@ def _check_schedule(schedule, alpha, quant):
     return bp, layered
 
 
-def _check_osd(osd, schedule, stop_rule):
-    """osd=True against the schedule and the resolved stop rule, as Simulation_GPU and Simulation_HARQ_GPU both refuse it."""
+def _check_osd(osd, schedule, stop_rule, osd_order=0, osd_lambda=0):
+    """osd=True against the schedule and the resolved stop rule, as Simulation_GPU and Simulation_HARQ_GPU both refuse it; osd_order
+    and osd_lambda (bldpc_decode_osd_w) belong to osd=True."""
     if not osd:
+        if osd_order or osd_lambda:
+            raise ValueError("osd_order and osd_lambda belong to osd=True")
         return
+    if osd_order not in (0, 1, 2) or int(osd_lambda) != osd_lambda or osd_lambda < 0:
+        raise ValueError("osd_order must be 0, 1 or 2 and osd_lambda a non-negative integer")
     if schedule not in ("layered", "bp", "quant"):
         raise ValueError("osd belongs to schedule='layered', schedule='bp' and schedule='quant': reprocessing orders the positions by a "
                          "decoder's a-posteriori values")
@@ -52,10 +57,10 @@ def _check_osd(osd, schedule, stop_rule):
         raise ValueError("osd needs stop_rule=STOP_SYNDROME: the frames to reprocess are those whose flag says 'no codeword'")
 
 
-def _osd_reprocess(code, D, app, cw, osd_cnt):
+def _osd_reprocess(code, D, app, cw, osd_cnt, osd_order=0, osd_lambda=0):
     """LDPC_Decoder_OSD_GPU on a decoder's D (in place) and app (a quantised app converted to float, which is exact); adds the frames
     reprocessed and those of them that came out equal to the word sent to osd_cnt (CUDA int64 [2])."""
-    _, flips, _ = LDPC_Decoder_OSD_GPU(code, app if app.dtype == torch.float32 else app.float(), D=D)
+    flips = LDPC_Decoder_OSD_GPU(code, app if app.dtype == torch.float32 else app.float(), D=D, order=osd_order, lam=osd_lambda)[1]
     done = flips >= 0
     same = ~((D[:code.N] != cw) if cw is not None else (D[:code.N] != 0)).any(0)
     osd_cnt[0] += done.sum()
@@ -135,7 +140,7 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
                    leastErrorFrames=50, leastTestFrames=10000, displayStep=40960, dist=None, device=None, max_batches=None,
                    log=print, device_channel=False, PN_Message=0, pn_seed=0, schedule="flooding", alpha=1.0, stop_rule=None,
                    n_QAM=2, CONSTELLATION=None, rate_match=None, short_llr=1.0e4, quant=None, interleave=IL_NONE, fading=None, hard_rule=None,
-                   osd=False):
+                   osd=False, osd_order=0, osd_lambda=0):
     """One SNR point (Simulation.cu:12-171).  `seed` (int32[3]) is the AWGN->seed state, advanced in place by the
     WHOLE batch on every rank so that all ranks stay on the reference's single noise stream.
 
@@ -194,7 +199,8 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
     with a non-zero syndrome are reprocessed (ordered statistics of order 0, include/bldpc.h) and come out codewords with flag 1; the
     iteration counts stay the decoder's.  schedule 'layered', 'bp' or 'quant' with stop_rule=STOP_SYNDROME; refused elsewhere.
     SIM.num_OSD_Frames counts the frames reprocessed and SIM.num_OSD_Correct those of them that came out equal to the word sent; the
-    log row ends with both."""
+    log row ends with both.  osd_order = 1 or 2 with osd_lambda (bldpc_decode_osd_w): the reprocessing also tries every single trusted
+    position flipped and, at order 2, the pairs among the osd_lambda least reliable of them; an error without osd=True."""
     if PN_Message not in (0, 1):
         raise ValueError("PN_Message must be 0 (all-zero codeword) or 1 (random codewords)")
     bp, layered = _check_schedule(schedule, alpha, quant)
@@ -227,7 +233,7 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
         raise ValueError("PN_Message=1 needs exit_mode=EXIT_FIXED: the decoders' early exit tests for the all-zero word")
     if n_QAM != 2 and PN_Message == 1 and not device_channel:  # every refusal before anything touches the device
         raise ValueError("n_QAM != 2 needs device_channel=True: there is no host QAM channel on this path")
-    _check_osd(osd, schedule, stop_rule)
+    _check_osd(osd, schedule, stop_rule, osd_order, osd_lambda)
     qam_m, con = _check_qam(n_QAM, CONSTELLATION, PN_Message, interleave)
     _check_fading(fading, device_channel, exit_mode)
     rm = rate_match
@@ -303,7 +309,7 @@ def Simulation_GPU(code, seed, sigma, SIM, Num_Frames_OneTime=4096, maxIT=50, ex
             if PN_Message and stop_rule != STOP_SYNDROME:
                 Syndrome(code, D, into_flag_row=True)
             if osd:
-                _osd_reprocess(code, D, r["app"], cw, osd_cnt)
+                _osd_reprocess(code, D, r["app"], cw, osd_cnt, osd_order, osd_lambda)
             st = torch.cuda.current_stream(device).cuda_stream
             check(lib.bldpc_statistic_per_frame(code._h, _dev_ptr(D), _dev_ptr(cw), count, length, _dev_ptr(r["iters"]), _dev_ptr(dev_cnt), st),
                   "Statistic")
@@ -525,7 +531,8 @@ def format_harq_row(SIM, info_bits):
 def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, maxIT=50, exit_mode=EXIT_FIXED, kernel=KERNEL_AUTO,
                         leastErrorFrames=50, leastTestFrames=10000, dist=None, device=None, max_batches=None, log=print, PN_Message=0,
                         pn_seed=0, schedule="flooding", alpha=1.0, stop_rule=None, short_llr=1.0e4, compact=True, keep_D=None, quant=None,
-                        n_QAM=2, CONSTELLATION=None, interleave=IL_NONE, fading=None, osd=False):
+                        n_QAM=2, CONSTELLATION=None, interleave=IL_NONE, fading=None, osd=False, osd_order=0,
+                        osd_lambda=0):
     """One SNR point of incremental-redundancy HARQ over BPSK, or over n_QAM-QAM, on the device channel.  rvs = [rm_0, ..., rm_{T-1}]: the profile of
     each transmission (RateMatch.circular or RateMatch, all over code.N with the same shortened positions).  SIM is a HarqCounters.
 
@@ -567,7 +574,8 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
     receives codewords with flag 1 in their columns.  A reprocessed frame is NOT acknowledged by that: reprocessing always returns a
     codeword, so its flag says nothing about the word sent.  The acknowledgement stays the decoder's flag, and acked, undetected,
     never_acked, bits_sent and the iterations are what they are with osd=False; SIM.osd_frames and SIM.osd_correct count the frames
-    reprocessed and those of them that came out equal to the word sent, and the log row ends with both."""
+    reprocessed and those of them that came out equal to the word sent, and the log row ends with both.  osd_order and osd_lambda are
+    those of Simulation_GPU."""
     if PN_Message not in (0, 1):
         raise ValueError("PN_Message must be 0 (all-zero codeword) or 1 (random codewords)")
     bp, layered = _check_schedule(schedule, alpha, quant)
@@ -587,7 +595,7 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
             raise ValueError("PN_Message=1 with per-frame exit needs stop_rule=STOP_SYNDROME: STOP_PREFIX tests for the all-zero word")
     elif PN_Message == 1 and exit_mode != EXIT_FIXED:
         raise ValueError("PN_Message=1 needs exit_mode=EXIT_FIXED: the flooding decoders' early exit tests for the all-zero word")
-    _check_osd(osd, schedule, stop_rule)
+    _check_osd(osd, schedule, stop_rule, osd_order, osd_lambda)
     qam_m, con = _check_qam(n_QAM, CONSTELLATION, PN_Message, interleave)
     _check_fading(fading, True, exit_mode)
     rvs = list(rvs) if rvs is not None else []
@@ -705,7 +713,7 @@ def Simulation_HARQ_GPU(code, seed, sigma, SIM, rvs, Num_Frames_OneTime=4096, ma
         if count:
             cnt[2 * T] += (~acked).sum()
             if osd:  # the flag row has served as the acknowledgement: from here on it says "codeword"
-                _osd_reprocess(code, D, app, cw, osd_cnt)
+                _osd_reprocess(code, D, app, cw, osd_cnt, osd_order, osd_lambda)
             if keep_D is not None:
                 keep_D.append(D)
         sharding.allreduce_counters(cnt, dist)

@@ -956,6 +956,56 @@ int bldpc_decode_osd_host(int J, int L, int Z, const int *H, const float *app, c
 int bldpc_osd_info(bldpc_code *code, int tier, int info[4]);
 int bldpc_osd_plan_host(int J, int L, int Z, const int *H, int tier, int info[4]);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * Reprocessing of order 1 and 2 (OSD-1, and the "combination sweep" OSD-CS): order 0 trusts every position outside B; these calls
+ * also try the words in which one trusted position, or a pair among the least reliable trusted positions, is flipped, and keep the
+ * candidate with the least soft metric.  app, D_in, D, flips, scanned, the order of the positions ("place": a position's index in
+ * it), the basis B, y, scanned and the kept frames are exactly those of bldpc_decode_osd.
+ *   order    0, 1 or 2;  lambda >= 0, read at order 2 only
+ *   picked   int32 [2][F] or NULL: the positions (not places) of the set S chosen, in ascending place, -1 where absent
+ *   metric   float [F] or NULL: the metric of the candidate chosen; a NaN has an unspecified payload
+ * A kept frame gets flips = -1, scanned = 0, picked = -1, -1 and leaves metric unwritten.
+ *
+ * Per processed frame f: B[0 .. rank-1] are the basis positions in the order they joined, w[v] the float whose bits are
+ * bits(app[v][f]) & 0x7fffffff.
+ *   A candidate is a set S of at most `order` positions outside B.  Its error pattern e has e[v] = 1 on S, and on B it is the unique
+ *   solution of H_B e_B = H y xor H_S 1 (always consistent, because B spans the column space); its word is c = y xor e, a codeword.
+ *   Its metric, in fp32: m = +0.0f; for k = 0 .. rank-1 in that order m += w[B[k]] where e[B[k]] = 1; then m += w[v] for the
+ *   positions of S in ascending place.  No term is skipped or reassociated and there is no multiply to fuse.  Every term is
+ *   non-negative, so m is +0.0, positive, +inf or NaN and its bit pattern orders as an unsigned integer; a NaN of any payload
+ *   compares as 0x7fffffff.
+ *   order 0: the empty set only; D, flips and scanned are those of bldpc_decode_osd, bit for bit.
+ *   order 1: also every single position outside B, the dependent positions before `scanned` included: N - rank of them.
+ *   order 2: also every pair among the first min(lambda, N - rank) positions outside B in ascending place; lambda = 0 is order 1.
+ *   The result is the candidate with the least triple (metric bits, place of the first position of S + 1, place of the second + 1),
+ *   a component being 0 where S has no such position: an exact tie stays with order 0, then goes to the single of lowest place, then
+ *   to pairs.  The triple is a total order, so the result does not depend on who evaluates what first.
+ *   D gets the word and flag 1; flips is the weight of the whole e, S included.
+ *
+ * The device call is the one of bldpc_decode_osd up to the last pivot (the same frame body, instantiated with the search), with one
+ * addition: the thread that owns a pivot's row puts 0x80000000 | row into the lower half of the pivot's sort key, whose upper half
+ * is bits(w) already.  The sorted keys are then the pivot list in joining order with its weights, the basis bitmap (bit 31) and the
+ * positions outside B at once, so the search takes no LDS beyond k_osd's and the plan, the tier and the refusals of a shape are
+ * those of bldpc_osd_info at every order.  One wave per candidate: 64 places a step, a lane whose place is a pivot XORs the reduced
+ * columns of S at its row (from T and the checks of the positions, as the elimination does) into its syndrome bit, a ballot gives
+ * the ones in joining order and the fp32 sum runs over them; a partial sum above the wave's best metric ends the candidate, which
+ * loses nothing because every term is non-negative; for the same reason a wave stops at the first place whose weight alone, or whose
+ * weight with that of the pair's first position, is above its best metric (the weights ascend with the place).  Wave i of the workgroup takes the places i, i + waves, ... outside B as
+ * singles and each with the later places below the lambda-th as pairs; the least 64-bit key (metric bits, place + 1, place + 1 in
+ * 16 bits each) of the waves goes through one LDS atomicMin per wave, and e of the winner is formed once.
+ * bldpc_last_kernel names "k_osd_w" or "k_osd_w_ws".  Asynchronous on `stream`; allocates nothing once its scratch has grown.
+ * BLDPC_EINVAL: what bldpc_decode_osd refuses, an order outside 0 .. 2, a negative lambda.
+ * BLDPC_EUNSUPPORTED: what bldpc_osd_info refuses.
+ * The _host form is the definition (plain C++, one frame at a time, at most 16 threads) and has no size bound.
+ *
+ * bldpc_osd_w_info / bldpc_osd_w_plan_host: info[4] as bldpc_osd_info gives it, for the order asked. */
+int bldpc_decode_osd_w(bldpc_code *code, const float *app, const int *D_in, int F, int tier, int order, int lambda, int *D, int *flips,
+                       int *scanned, int *picked, float *metric, void *stream);
+int bldpc_decode_osd_w_host(int J, int L, int Z, const int *H, const float *app, const int *D_in, int F, int order, int lambda, int *D,
+                            int *flips, int *scanned, int *picked, float *metric);
+int bldpc_osd_w_info(bldpc_code *code, int tier, int order, int info[4]);
+int bldpc_osd_w_plan_host(int J, int L, int Z, const int *H, int tier, int order, int info[4]);
+
 const char *bldpc_last_error(void);
 
 #ifdef __cplusplus

@@ -114,6 +114,9 @@ def main():
     ap.add_argument("--osd", action="store_true", help="binary --layered / --bp / --quant with the syndrome stop rule: ordered-statistics "
                     "reprocessing of order 0 (bldpc_decode_osd) on the frames the decoder leaves with a non-zero syndrome; the row ends with the "
                     "frames reprocessed and those of them that came out equal to the word sent")
+    ap.add_argument("--osd-order", type=int, choices=(0, 1, 2), default=0, help="--osd: also every single trusted position flipped (1) and the pairs "
+                    "among the --osd-lambda least reliable of them (2), the candidate of least soft metric kept (bldpc_decode_osd_w)")
+    ap.add_argument("--osd-lambda", type=int, default=0, metavar="L", help="--osd --osd-order 2: pairs among the first L positions outside the basis")
     ap.add_argument("--alpha", type=float, default=1.0, help="binary: normalisation factor in (0, 1]; with --layered the layered decoder's, without it "
                     "normalised min-sum on the flooding decoders (with --fixed or --per-frame)")
     ap.add_argument("--stop-rule", choices=["prefix", "syndrome"], default=None,
@@ -223,6 +226,10 @@ def main():
         ap.error("--osd belongs to the binary sweep with --layered, --bp or --quant")
     elif args.stop_rule is not None or (args.alpha != 1.0 and args.which != "binary"):
         ap.error("--stop-rule belongs to the binary sweep with --layered, --bp or --quant, --alpha to the binary sweep")
+    if (args.osd_order or args.osd_lambda) and not args.osd:
+        ap.error("--osd-order and --osd-lambda belong to --osd")
+    if args.osd_lambda < 0:
+        ap.error("--osd-lambda must not be negative")
     elif args.alpha != 1.0 and not (args.fixed or args.per_frame):
         ap.error("--alpha without --layered (normalised flooding min-sum) needs --fixed or --per-frame")
     if args.which == "binary" and not rows and args.hard is None and not args.erasure and args.pn_message and (not args.fixed or args.as_written):
@@ -298,7 +305,7 @@ def main():
                 except ValueError as e:
                     ap.error("--quant: %s" % e)
             if args.osd:
-                lay["osd"] = True
+                lay.update(osd=True, osd_order=args.osd_order, osd_lambda=args.osd_lambda)
         if args.hard is not None:
             lay = dict(schedule="hard", hard_rule=C.BF_GRADIENT if args.hard == "gradient" else C.BF_THRESHOLD)
         if bsc is not None:
@@ -348,7 +355,7 @@ def main():
                                                           "flooding alpha=%g" % args.alpha, "fixed iterations" if args.fixed else "per-frame early exit",
                                                           args.iters or (25 if rows else 50), args.batch, world,
                                                           ", random codewords (PN seed %d)" % args.pn_seed if args.pn_message else "")
-                      + (fade_words if fade is not None else "") + (", OSD-0 after the last transmission" if args.osd else ""))
+                      + (fade_words if fade is not None else "") + (", OSD-%d after the last transmission" % args.osd_order if args.osd else ""))
                 print("# SNR      NTF  FER after each transmission ...  mean transmissions  throughput (information bits per bit sent)  AverIT"
                       + ("  OSD reprocessed correct" if args.osd else ""))
             sweep_harq(code, rvs, args.start, args.stop, args.step, snrtype=1 if args.snrtype is None else args.snrtype, dist=dist,
@@ -376,7 +383,7 @@ def main():
                   "fixed iterations" if args.fixed else ("per-frame early exit" if args.per_frame else "batch-global early exit"),
                   args.iters or (25 if rows else 30 if args.hard is not None else 50), args.batch, world,
                   ", random codewords (PN seed %d, K'=%d), syndrome flag" % (args.pn_seed, code.K_info) if args.pn_message else "")
-                  + (fade_words if fade is not None else "") + (", OSD-0 on the frames left with a non-zero syndrome" if args.osd else ""))
+                  + (fade_words if fade is not None else "") + (", OSD-%d on the frames left with a non-zero syndrome" % args.osd_order if args.osd else ""))
             print("# SNR      NTF   NEF         FER         BER  AverIT       FER_F      FER_A" + ("  OSD reprocessed correct" if args.osd else ""))
         sweep(code, args.start, args.stop, args.step, snrtype=1 if args.qam == 2 else 0, dist=dist, Num_Frames_OneTime=args.batch, maxIT=args.iters or (25 if rows else 30 if args.hard is not None else 50),
               exit_mode=C.EXIT_FIXED if args.fixed else (C.EXIT_PER_FRAME if args.per_frame else C.EXIT_BATCH_GLOBAL), max_batches=args.max_batches, displayStep=10 ** 12, device_channel=args.device_channel,
